@@ -14,13 +14,17 @@ two-stream pipeline (forward k+1 beside NMS k); --serial runs forward and NMS
 back to back on one stream.
 Data-parallel: every rank processes its own batch of 32 (weak scaling).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
-Prints ONE JSON line on rank 0 (fields per the driver contract), including
-`roofline` (dominant kernel family: the dense 3x3 implicit-GEMM convs, timed
-with HIP events per launch on the forward's stream) and `cpu_baseline` (the CPU
-oracle, fp32 forward + NMS, on the host cores, N=1 only).
+Prints ONE JSON line on rank 0 (fields per the driver contract). A plain run sets
+up, warms up, times the K steps and prints the line. --dump-outputs DIR also
+writes the last timed step's detections as DIR/dets.npy and DIR/counts.npy
+(float32; the inputs are seeded, so two builds can be compared output for output).
+--full adds what takes runs of its own: `roofline` (dominant kernel family: the
+dense 3x3 implicit-GEMM convs, timed with HIP events per launch on the forward's
+stream) and `cpu_baseline` (the CPU oracle, fp32 forward + NMS, on the host cores,
+N=1 only); both fields are null without it.
 """
 import argparse
 import json
@@ -210,6 +214,21 @@ def cpu_baseline(args, runs=3):
                        f"{threads} threads, torch.inference_mode()")
 
 
+def dump_outputs(path, dets, counts):
+    """--dump-outputs: what a caller of the timed path receives for its last step, as
+    <path>/dets.npy ((images, max_det, 6) float32: x1 y1 x2 y2 score class) and <path>/counts.npy
+    ((images,) float32, exact: counts <= max_det). Under a process group `dets` / `counts` are the
+    rows gathered on rank 0, every rank's images in rank order. Rows past an image's count are
+    not part of the result (their content is unspecified); they are stored as zeros."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    c = counts.detach().cpu().long()
+    d = dets.detach().float().cpu().clone()
+    d[torch.arange(d.shape[1])[None, :] >= c[:, None]] = 0
+    np.save(os.path.join(path, "dets.npy"), d.numpy())
+    np.save(os.path.join(path, "counts.npy"), c.to(torch.float32).numpy())
+
+
 def visible_gpus_without_hip():
     """GPUs this process could use, counted without initialising HIP (the self-launch parent must
     not: the ranks it spawns then start from a clean driver state). KFD topology nodes with SIMDs
@@ -261,9 +280,14 @@ def main():
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--dtype", default="bf16", choices=sorted(DTYPES))
-    ap.add_argument("--profile-steps", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's detections to DIR/dets.npy and DIR/counts.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel roofline profile and the CPU baseline "
+                         "(runs of their own; a plain run reports neither)")
+    ap.add_argument("--profile-steps", type=int, default=None, help="with --full: forwards of the roofline profile")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline profile")
     ap.add_argument("--lanes", type=int, default=3,
                     help="forward lanes: engines whose forwards of consecutive batches overlap "
                          "(measured r01, v11_n b32: 1 -> 20.3k, 2 -> 23.2k, 3 -> 27.2k, 4 -> 25.2k img/s)")
@@ -277,6 +301,8 @@ def main():
                     help="no HIP: gloo on the CPU and a stub step (the gather of empty detection buffers); "
                          "checks the launcher, rank layout, timing and JSON line without a GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         ngpu = None if args.dry_run else visible_gpus_without_hip()
@@ -387,14 +413,22 @@ def main():
         from yolo_hip.dist import pack
         gather_check = bool(torch.equal(extra[0], pack(dets, counts)))
 
+    if args.dump_outputs and rank == 0:
+        if dist:   # what rank 0 receives: every rank's packed rows (dets, then the count)
+            rows = torch.cat([p.cpu() for p in extra], 0)
+            dump_outputs(args.dump_outputs, rows[:, :-1].reshape(rows.shape[0], -1, 6), rows[:, -1])
+        else:
+            dump_outputs(args.dump_outputs, dets, counts)
+
+    # runs of their own, after the timed steps and only with --full
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         if rank == 0:
             log(f"per-class kernel time (HIP events, {args.profile_steps or args.steps} forwards, batch {B}):")
         roof = roofline(eng, args, B, args.profile_steps or args.steps, x, y)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if rank == 0:

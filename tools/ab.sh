@@ -14,8 +14,8 @@ B=exp_lib/base/libyolo_hip.so
 YH_LIB=$B timeout -k 10 200 python -u tools/op_profile.py n 640 32 bf16 10 > $O/op_base.txt 2>&1 || { echo OPB_FAIL; tail $O/op_base.txt; exit 1; }
 timeout -k 10 200 python -u tools/op_profile.py n 640 32 bf16 10 > $O/op_new.txt 2>&1 || { echo OPN_FAIL; tail $O/op_new.txt; exit 1; }
 for r in 1 2; do
-  YH_LIB=$B timeout -k 10 300 python -u bench.py --no-cpu-baseline > $O/b_base$r.json 2>$O/b_base$r.err || { echo BB_FAIL; tail $O/b_base$r.err; exit 1; }
-  timeout -k 10 300 python -u bench.py --no-cpu-baseline > $O/b_new$r.json 2>$O/b_new$r.err || { echo BN_FAIL; tail $O/b_new$r.err; exit 1; }
+  YH_LIB=$B timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $O/b_base$r.json 2>$O/b_base$r.err || { echo BB_FAIL; tail $O/b_base$r.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $O/b_new$r.json 2>$O/b_new$r.err || { echo BN_FAIL; tail $O/b_new$r.err; exit 1; }
 done
 python - "$O" <<'PY'
 import json, sys

@@ -12,7 +12,7 @@ done
 for r in $(seq 1 ${REPS:-1}); do
   for c in "${C[@]}"; do
     n=${c%%:*}; e=${c#*:}
-    env $e timeout -k 10 300 python -u bench.py --no-cpu-baseline > $O/b_${n}_$r.json 2>$O/b_${n}_$r.err || { echo "B_FAIL $n"; tail $O/b_${n}_$r.err; exit 1; }
+    env $e timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $O/b_${n}_$r.json 2>$O/b_${n}_$r.err || { echo "B_FAIL $n"; tail $O/b_${n}_$r.err; exit 1; }
     python -c "import json;r=json.load(open('$O/b_${n}_$r.json'));print('$n', r['value'], r['roofline']['frac'], r['roofline']['forward_kernel_ms'])"
   done
 done

@@ -11,7 +11,7 @@ tail -1 $O/gpu_tests.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { echo SMOKE_FAIL; tail $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 for r in 1 2; do
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/bench20_$r.json 2> $O/bench20_$r.err || { echo BENCH20_FAIL; tail -20 $O/bench20_$r.err; exit 1; }
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/bench20_$r.json 2> $O/bench20_$r.err || { echo BENCH20_FAIL; tail -20 $O/bench20_$r.err; exit 1; }
 python -c "import json;d=json.load(open('$O/bench20_$r.json'));print('bench20', d['value'], d['roofline']['frac'])"
 done
 bash tools/prof_round.sh $T/prof > $O/prof.log 2>&1 || { echo PROF_FAIL; tail -20 $O/prof.log; exit 1; }

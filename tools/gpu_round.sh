@@ -8,5 +8,5 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout
 tail -2 "$OUT/tests.log"
 bash tools/ft.sh "$(basename $OUT)/ft" > /dev/null || { echo "TRACE FAILED"; exit 1; }
 head -2 "$OUT/ft/ops.txt"
-timeout -k 10 400 python bench.py --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "BENCH FAILED"; tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 400 python bench.py --full --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "BENCH FAILED"; tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
