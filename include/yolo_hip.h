@@ -17,6 +17,8 @@
  *   yh_forward_u8       main.py:265-267     uint8 -> dtype, / 255 preprocessing fused into yh_forward's stem
  *   yh_nms              utils/util.py:123-169 non_max_suppression (+ torchvision.ops.nms, util.py:162)
  *   yh_nms_host         the same for head outputs on the CPU device (main.py:20 device fallback)
+ *   yh_match            utils/util.py:99-120 compute_metric for a whole batch (main.py:275-294 loop)
+ *   yh_match_host       the same in host memory
  *   yh_letterbox        utils/dataset.py:95-103, 292-313, 86-88: eval-mode load_image resize
  *                       (cv2 INTER_LINEAR) + zero border + HWC->CHW, BGR->RGB, on the device
  *   yh_letterbox_host   the same on the host (Dataset.__getitem__ in the loader workers)
@@ -44,7 +46,7 @@
 extern "C" {
 #endif
 
-#define YH_ABI_VERSION 5
+#define YH_ABI_VERSION 6
 
 /* status codes */
 #define YH_OK 0
@@ -156,6 +158,41 @@ int yh_nms(int dtype, const void* y, int batch, int num_classes, int anchors,
 int yh_nms_host(int dtype, const void* y, int batch, int num_classes, int anchors,
                 float conf_threshold, double iou_threshold, int max_det, int max_nms,
                 float max_wh, float* dets, int* counts, int threads);
+
+/* Largest max_det yh_match / yh_match_host accept: the kernel keeps 12 bytes of LDS per
+ * detection slot plus a 6 KiB label chunk (54 KiB at the cap). */
+#define YH_MATCH_MAX_DET 4096
+
+/* Match a whole batch's detections to its labels (compute_metric, utils/util.py:99-120, for
+ * every image and every IoU threshold) in one launch, straight from yh_nms's output.
+ *   dets (batch, max_det, 6), counts (batch): as yh_nms writes them. counts is clamped to
+ *       [0, max_det]; rows at or beyond counts[b] may be uninitialised and are never read.
+ *   labels (N, 5) f32 [cls, x1, y1, x2, y2] in pixels, grouped by image; label_offsets
+ *       (batch + 1) int32 ascending: image b owns rows offsets[b] .. offsets[b + 1]. The caller
+ *       guarantees 0 <= offsets <= N; any number of labels per image.
+ *   iou_v (num_iou) f32 thresholds, 1 <= num_iou <= 32.
+ *   tp (batch, max_det, num_iou) uint8 0/1: every byte is written, rows beyond counts[b] are 0.
+ *   score_cls (batch, max_det, 2) f32, optional (NULL): columns 4, 5 of the valid rows, 0 beyond.
+ *   counts_out (batch) int32, optional (NULL): the clamped counts.
+ * Per image: best[d] = the label of equal class (f32 ==) with the highest IoU, the lower label
+ * index on ties, biou[d] that IoU; tp[d, t] = 1 iff d has a best label, biou[d] >= iou_v[t] and
+ * no e < d has best[e] == best[d] and biou[e] >= iou_v[t]. The IoU is fp32, bit-identical to
+ * yolo_hip.metrics._iou: inter = max(0, iw) * max(0, ih), inter / (((areaA + areaB) - inter) + 1e-7f).
+ * Box coordinates must be finite (device and host agree on any input; torch's min / max
+ * propagate NaN, these do not).
+ * yh_match: device pointers, asynchronous on `stream`, allocates nothing, never synchronises.
+ * yh_match_host: the same for host pointers, images in parallel over `threads` (<= 0: all
+ * hardware threads), synchronous.
+ * YH_EINVAL (message in yh_last_error()): num_iou outside [1, 32], a negative size, max_det
+ * above YH_MATCH_MAX_DET, a NULL required pointer. */
+int yh_match(const float* dets, const int* counts, int batch, int max_det,
+             const float* labels, const int* label_offsets,
+             const float* iou_v, int num_iou,
+             uint8_t* tp, float* score_cls, int* counts_out, void* stream);
+int yh_match_host(const float* dets, const int* counts, int batch, int max_det,
+                  const float* labels, const int* label_offsets,
+                  const float* iou_v, int num_iou,
+                  uint8_t* tp, float* score_cls, int* counts_out, int threads);
 
 /* Letterbox geometry of one image for a square canvas of `size` (dataset.py:95-103,
  * 292-313): resized height / width (int(h * r), int(w * r) with r = size / max(h, w);

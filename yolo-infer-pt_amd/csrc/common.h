@@ -309,5 +309,9 @@ int launch_attention(int dtype, const AttnArgs& a, int B, hipStream_t s);
 int launch_decode(int dtype, const DecodeArgs& a, hipStream_t s);
 int launch_set_io(void** io, const void* x, void* y, hipStream_t s);
 int launch_nms(int dtype, const NmsArgs& a, hipStream_t s);
+// match.hip: detections x labels -> true-positive bytes for a whole batch (yh_match)
+int launch_match(const float* dets, const int* counts, int batch, int max_det, const float* labels,
+                 const int* label_offsets, const float* iou_v, int num_iou, uint8_t* tp, float* score_cls,
+                 int* counts_out, hipStream_t s);
 
 }  // namespace yh

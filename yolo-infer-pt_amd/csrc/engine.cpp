@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "conv_mx.h"
+#include "match_host.h"
 #include "yolo_hip.h"
 
 
@@ -2519,6 +2520,30 @@ int yh_nms(int dtype, const void* y, int batch, int num_classes, int anchors, fl
         a.ndet = counts;
         const int rc = yh::launch_nms(dtype, a, (hipStream_t)stream);
         if (rc != 0) throw Fail(YH_EHIP, std::string("NMS launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_match(const float* dets, const int* counts, int batch, int max_det, const float* labels,
+             const int* label_offsets, const float* iou_v, int num_iou, uint8_t* tp, float* score_cls,
+             int* counts_out, void* stream) {
+    return guarded([&] {
+        static_assert(YH_MATCH_MAX_DET >= 1024, "the ABI promises at least 1024");
+        const char* bad = yh_match_check(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp);
+        yh::require(!bad, bad ? bad : "");
+        const int rc = yh::launch_match(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp,
+                                        score_cls, counts_out, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("match launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_match_host(const float* dets, const int* counts, int batch, int max_det, const float* labels,
+                  const int* label_offsets, const float* iou_v, int num_iou, uint8_t* tp, float* score_cls,
+                  int* counts_out, int threads) {
+    return guarded([&] {
+        const char* bad = yh_match_check(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp);
+        yh::require(!bad, bad ? bad : "");
+        yh_match_host_run(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp, score_cls,
+                          counts_out, threads);
     });
 }
 

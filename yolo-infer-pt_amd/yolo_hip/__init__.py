@@ -1,7 +1,8 @@
 """MI355X (gfx950) HIP runtime of the YOLOv11 inference path.
 
 `Engine` wraps one yh_handle (include/yolo_hip.h); `nms` is the on-device
-non_max_suppression. The drop-in module API lives in `nets.nn` / `utils.util`.
+non_max_suppression; `Evaluator` (yolo_hip.evaluate) is the batched mAP
+evaluation over those detections. The drop-in module API lives in `nets.nn` / `utils.util`.
 """
 from .variants import VARIANTS, Variant, lookup  # noqa: F401
 
@@ -11,4 +12,7 @@ def __getattr__(name):
     if name in ("Engine", "nms"):
         from . import engine
         return getattr(engine, name)
+    if name == "Evaluator":
+        from . import evaluate
+        return evaluate.Evaluator
     raise AttributeError(name)

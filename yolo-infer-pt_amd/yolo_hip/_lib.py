@@ -16,7 +16,7 @@ if os.environ.get("YH_LIB"):
     LIB_PATH = os.environ["YH_LIB"]
 
 YH_F32, YH_F16, YH_BF16 = 0, 1, 2
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class YhVariant(ctypes.Structure):
@@ -60,6 +60,10 @@ _PROTOS = {
                              POINTER(c_double), POINTER(c_int)]),
     "yh_nms_host": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_float, c_double, c_int, c_int, c_float,
                             c_void_p, c_void_p, c_int]),
+    "yh_match": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "yh_match_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                              c_void_p, c_void_p, c_void_p, c_int]),
     "yh_letterbox_geometry": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_letterbox": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "yh_letterbox_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),

@@ -4,9 +4,13 @@ The reference's eval loop (main.py:264-273) runs `model(samples)` and then
 `util.non_max_suppression(outputs)` back to back for every batch. Both stay
 exactly the same computations here; only their scheduling changes:
 
-* the forward (yh_forward, a replayed HIP graph) runs on a lane stream of its own, after an
-  event recorded on the caller's stream at submit() (so it sees everything the caller
-  queued before, e.g. the copy that filled x);
+* the forward (yh_forward, a replayed HIP graph) runs on a lane stream of its own. When the
+  caller's stream still has work pending at submit(), an event recorded there makes the
+  forward wait for it (so it sees everything the caller queued before, e.g. the copy that
+  filled x). With idle_skip (the default) no event is recorded when the caller's stream is
+  already idle at submit(): everything queued before has then completed, so the order holds
+  without a marker. Work the caller queues on its stream AFTER submit() is never ordered
+  against the batch;
 * the NMS (yh_nms) of the same batch - and, data-parallel, the RCCL gather of
   its fixed-size results - runs on a second stream after an event;
 * the head output (B, 4+nc, A) is double-buffered: forward k+2 writes the
@@ -24,6 +28,13 @@ gather is issued in the same order on every rank).
 
 Results are identical to the sequential order: every batch gets the full
 forward and the full NMS, on its own buffers.
+
+result_ring=True trades that last guarantee for no per-batch allocation: dets / counts
+live in `slots` = max(depth, 2 x lanes) buffer pairs allocated once, batch k in slot
+k % slots. Batch k's results are valid from its `done` event until batch k + slots is
+submitted; that batch's NMS overwrites them, and nothing detects a caller that still holds
+them. Consume a batch inside that window, or in-stream through `post` (which runs on the NMS
+stream right behind the batch's NMS, e.g. yolo_hip.evaluate.Evaluator.post).
 """
 import torch
 
@@ -45,10 +56,21 @@ class DetectPipeline:
     `post` (optional) is called on the NMS stream with (dets, counts) - e.g. the
     data-parallel gather - and its return value (`extra`) is kept with the batch.
 
-    Stream safety: dets / counts (and the tensors in `extra`) are allocated on the
-    NMS stream; submit() marks them used on the caller's stream (record_stream), so
-    once the caller drops them the caching allocator does not hand their blocks to a
-    later batch's NMS before the caller's queued reads have run.
+    Stream safety, result_ring=False (default): dets / counts (and the tensors in `extra`)
+    are allocated per batch on the NMS stream; submit() marks them used on the caller's
+    stream (record_stream), so once the caller drops them the caching allocator does not
+    hand their blocks to a later batch's NMS before the caller's queued reads have run.
+
+    result_ring=True: dets / counts are slot k % slots of a ring allocated once (slots =
+    max(depth, 2 x lanes)); nothing is allocated or record_stream'ed per batch except the
+    tensors in `extra`. The returned tensors are valid from `done` until the submit() of
+    batch k + slots, whose NMS overwrites them silently - that NMS is ordered after what the
+    caller had queued on its stream before that submit(), not after later reads. Holding
+    results for longer reads another batch's detections.
+
+    idle_skip=True (default): the forward waits for the caller's stream only if that stream
+    has work pending at submit(); when it is idle no marker event is queued there (see the
+    module docstring). idle_skip=False always records the marker.
 
     The forward reads x on its lane stream, not on the caller's: nothing the caller queues
     after submit() is ordered after it. x must not be modified in place (nor its storage
