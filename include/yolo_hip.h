@@ -19,6 +19,10 @@
  *   yh_nms_host         the same for head outputs on the CPU device (main.py:20 device fallback)
  *   yh_match            utils/util.py:99-120 compute_metric for a whole batch (main.py:275-294 loop)
  *   yh_match_host       the same in host memory
+ *   yh_merge            no reference counterpart (the reference never leaves the network canvas and
+ *                       has no tiled inference): the inverse of the letterbox of utils/dataset.py:95-103,
+ *                       292-313 per tile, plus a cross-tile greedy NMS under the torchvision.ops.nms contract
+ *   yh_merge_host       the same in host memory
  *   yh_letterbox        utils/dataset.py:95-103, 292-313, 86-88: eval-mode load_image resize
  *                       (cv2 INTER_LINEAR) + zero border + HWC->CHW, BGR->RGB, on the device
  *   yh_letterbox_host   the same on the host (Dataset.__getitem__ in the loader workers)
@@ -46,7 +50,7 @@
 extern "C" {
 #endif
 
-#define YH_ABI_VERSION 6
+#define YH_ABI_VERSION 7
 
 /* status codes */
 #define YH_OK 0
@@ -193,6 +197,55 @@ int yh_match_host(const float* dets, const int* counts, int batch, int max_det,
                   const float* labels, const int* label_offsets,
                   const float* iou_v, int num_iou,
                   uint8_t* tp, float* score_cls, int* counts_out, int threads);
+
+/* Largest max_tiles * max_det yh_merge / yh_merge_host accept: the candidates of one image. The
+ * kernel keeps an 8-byte sort key per candidate in LDS (64 KiB, requested with
+ * hipFuncAttributeMaxDynamicSharedMemorySize) and the candidates themselves in registers, 8 per
+ * thread of a 1024-thread workgroup. */
+#define YH_MERGE_MAX_CAND 8192
+
+/* Map the NMS output of a batch of tiles back to the source images and merge the tiles of each
+ * image, in one launch.
+ *   dets (tiles, max_det, 6), counts (tiles): as yh_nms writes them for the tile batch. counts is
+ *       clamped to [0, max_det]; rows at or beyond counts[t] may be uninitialised and are never read.
+ *   tile_xf (tiles, 6) f32: sx, sy, px, py, ox, oy of each tile (below).
+ *   tile_offsets (images + 1) int32 ascending: image i owns tiles tile_offsets[i] .. tile_offsets[i + 1].
+ *       The tile axis may hold more tiles than the offsets reference (padding of a last partial
+ *       batch): they are never visited. Each range is clamped to [0, tiles] and to max_tiles tiles.
+ *   image_wh (images, 2) f32: W, H of the source image.
+ *   max_tiles: the caller's bound on tiles per image; max_tiles * max_det <= YH_MERGE_MAX_CAND.
+ *   out (images, max_out, 6) f32 = x1, y1, x2, y2, score, class in source pixels; out_counts (images)
+ *       int32. Every byte of both is written; rows beyond an image's count are 0; an image with no
+ *       tiles has count 0.
+ * Per image, identical on device and host bit for bit:
+ *   1. every valid row of every tile of the image is a candidate; its position is (tile, row) in
+ *      input order;
+ *   2. the box is mapped in fp32, one rounding per operation, no FMA: t = x - px; t = t * sx;
+ *      X = t + ox (y with sy, py, oy), then clipped to [0, W] / [0, H]. A row whose clipped box has
+ *      x2 <= x1 or y2 <= y1 is dropped;
+ *   3. an image of exactly one tile writes its surviving rows in input order, up to max_out: the
+ *      plain inverse letterbox, no suppression;
+ *   4. an image of two or more tiles runs a greedy NMS under the torchvision.ops.nms contract
+ *      (yh_nms_host): candidates by score descending, ties to the lower position; a live candidate
+ *      is kept and kills every later candidate of equal class (f32 ==) whose
+ *      inter / (area_i + area_j - inter), in fp32 on the mapped boxes, is as a double >
+ *      iou_threshold; at most max_out are kept. Classes are compared, not offset by max_wh: source
+ *      coordinates of several thousand pixels would lose bits to the offset.
+ * Boxes and scores must be finite. Duplicates are merged by IoU only: there is no
+ * intersection-over-smaller rule and no dropping of boxes that touch an interior tile edge.
+ * yh_merge: device pointers, one workgroup per image, asynchronous on `stream`, allocates nothing,
+ * never synchronises. yh_merge_host: the same for host pointers, images in parallel over `threads`
+ * (<= 0: all hardware threads), synchronous.
+ * YH_EINVAL (message in yh_last_error()): a negative size, max_tiles < 1, max_tiles * max_det above
+ * YH_MERGE_MAX_CAND, a NULL required pointer. */
+int yh_merge(const float* dets, const int* counts, int tiles, int max_det,
+             const float* tile_xf, const int* tile_offsets, const float* image_wh,
+             int images, int max_tiles, double iou_threshold, int max_out,
+             float* out, int* out_counts, void* stream);
+int yh_merge_host(const float* dets, const int* counts, int tiles, int max_det,
+                  const float* tile_xf, const int* tile_offsets, const float* image_wh,
+                  int images, int max_tiles, double iou_threshold, int max_out,
+                  float* out, int* out_counts, int threads);
 
 /* Letterbox geometry of one image for a square canvas of `size` (dataset.py:95-103,
  * 292-313): resized height / width (int(h * r), int(w * r) with r = size / max(h, w);

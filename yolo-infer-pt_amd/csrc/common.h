@@ -313,5 +313,9 @@ int launch_nms(int dtype, const NmsArgs& a, hipStream_t s);
 int launch_match(const float* dets, const int* counts, int batch, int max_det, const float* labels,
                  const int* label_offsets, const float* iou_v, int num_iou, uint8_t* tp, float* score_cls,
                  int* counts_out, hipStream_t s);
+// merge.hip: tile detections -> source-coordinate detections, duplicates across tiles removed (yh_merge)
+int launch_merge(const float* dets, const int* counts, int tiles, int max_det, const float* tile_xf,
+                 const int* tile_offsets, const float* image_wh, int images, int max_tiles, double iou_threshold,
+                 int max_out, float* out, int* out_counts, hipStream_t s);
 
 }  // namespace yh

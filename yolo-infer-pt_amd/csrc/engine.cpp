@@ -19,6 +19,7 @@
 #include "common.h"
 #include "conv_mx.h"
 #include "match_host.h"
+#include "merge_host.h"
 #include "yolo_hip.h"
 
 
@@ -2544,6 +2545,31 @@ int yh_match_host(const float* dets, const int* counts, int batch, int max_det, 
         yh::require(!bad, bad ? bad : "");
         yh_match_host_run(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp, score_cls,
                           counts_out, threads);
+    });
+}
+
+int yh_merge(const float* dets, const int* counts, int tiles, int max_det, const float* tile_xf,
+             const int* tile_offsets, const float* image_wh, int images, int max_tiles, double iou_threshold,
+             int max_out, float* out, int* out_counts, void* stream) {
+    return guarded([&] {
+        const char* bad = yh_merge_check(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images,
+                                         max_tiles, max_out, out, out_counts);
+        yh::require(!bad, bad ? bad : "");
+        const int rc = yh::launch_merge(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images,
+                                        max_tiles, iou_threshold, max_out, out, out_counts, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("merge launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_merge_host(const float* dets, const int* counts, int tiles, int max_det, const float* tile_xf,
+                  const int* tile_offsets, const float* image_wh, int images, int max_tiles, double iou_threshold,
+                  int max_out, float* out, int* out_counts, int threads) {
+    return guarded([&] {
+        const char* bad = yh_merge_check(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images,
+                                         max_tiles, max_out, out, out_counts);
+        yh::require(!bad, bad ? bad : "");
+        yh_merge_host_run(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images, max_tiles,
+                          iou_threshold, max_out, out, out_counts, threads);
     });
 }
 

@@ -2,7 +2,8 @@
 
 `Engine` wraps one yh_handle (include/yolo_hip.h); `nms` is the on-device
 non_max_suppression; `Evaluator` (yolo_hip.evaluate) is the batched mAP
-evaluation over those detections. The drop-in module API lives in `nets.nn` / `utils.util`.
+evaluation over those detections; `Detector` (yolo_hip.detect) returns detections in
+source-image pixels, optionally from tiled inference (`tiles`, `tile_transform`, `merge`). The drop-in module API lives in `nets.nn` / `utils.util`.
 """
 from .variants import VARIANTS, Variant, lookup  # noqa: F401
 
@@ -15,4 +16,10 @@ def __getattr__(name):
     if name == "Evaluator":
         from . import evaluate
         return evaluate.Evaluator
+    if name in ("Detector", "Detections", "merge"):
+        from . import detect
+        return getattr(detect, name)
+    if name in ("tiles", "tile_transform"):
+        from . import detect
+        return getattr(detect, name)
     raise AttributeError(name)

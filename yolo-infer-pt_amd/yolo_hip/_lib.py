@@ -16,7 +16,8 @@ if os.environ.get("YH_LIB"):
     LIB_PATH = os.environ["YH_LIB"]
 
 YH_F32, YH_F16, YH_BF16 = 0, 1, 2
-ABI_VERSION = 6
+ABI_VERSION = 7
+MERGE_MAX_CAND = 8192   # YH_MERGE_MAX_CAND: candidates (max_tiles * max_det) per image of yh_merge
 
 
 class YhVariant(ctypes.Structure):
@@ -64,6 +65,10 @@ _PROTOS = {
                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_match_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                               c_void_p, c_void_p, c_void_p, c_int]),
+    "yh_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                         c_int, c_void_p, c_void_p, c_void_p]),
+    "yh_merge_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                              c_int, c_void_p, c_void_p, c_int]),
     "yh_letterbox_geometry": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_letterbox": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "yh_letterbox_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),

@@ -119,7 +119,10 @@ class DetectPipeline:
         self.idle_skip = idle_skip
         self.k = 0
 
-    def submit(self, x):
+    def submit(self, x, out=None):
+        # out=(dets (batch, max_det, 6) f32, counts (batch,) i32): this batch's NMS writes there
+        # instead of into fresh tensors / the ring slot (yolo_hip.detect.Detector packs every
+        # batch of a call into one tensor). The caller owns their lifetime and stream safety.
         main = torch.cuda.current_stream(self.eng.device)
         i = self.k % len(self.ys)
         lane = self.k % len(self.engs)
@@ -147,7 +150,10 @@ class DetectPipeline:
         ns = self.nms_stream if self.nms_stream is not None else fs
         with torch.cuda.stream(ns):
             ns.wait_event(fwd_done)
-            if self.result_ring:
+            if out is not None:
+                dets, counts = nms(y, out=out, workspace=(self.nms_ws[lane if self.nms_stream is None else 0]
+                                                          if self.result_ring else None), **self.nms_kwargs)
+            elif self.result_ring:
                 # slot i's previous results (batch k - depth) are overwritten here: this NMS runs after
                 # fwd_done, which follows `ready`, i.e. everything the caller queued before this
                 # submit() (its reads of batch k - depth included)
@@ -162,7 +168,7 @@ class DetectPipeline:
         # allocated on the NMS stream, read on the caller's: keep the blocks out of the
         # NMS stream's free pool until the caller's work queued after `done` has run
         if ns is not main:
-            for t in ((*_tensors(extra),) if self.result_ring else (dets, counts, *_tensors(extra))):
+            for t in ((*_tensors(extra),) if self.result_ring or out is not None else (dets, counts, *_tensors(extra))):
                 if t.is_cuda:
                     t.record_stream(main)
         return dets, counts, extra, done
