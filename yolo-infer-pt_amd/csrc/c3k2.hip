@@ -1,6 +1,6 @@
 // Fused C3k2 block (nets/nn.py:66-80, n = 1, csp = False) for the 16-bit handles.
 //
-// One persistent workgroup (8 waves) per CU walks TH x TW output tiles of the block:
+// One persistent workgroup (CSP_THREADS / 64 waves) per CU walks TH x TW output tiles of the block:
 //   P0  input tile with a 2-pixel halo -> LDS (LDS-DMA, zeros outside the image)
 //   P1  conv1 1x1 Cin -> 2c + SiLU on the whole halo tile -> T1 = [a | b]; pixels
 //       outside the image are zeroed (they are the next conv's zero padding)
@@ -54,6 +54,28 @@ __device__ __forceinline__ void cs_glds(const void* src, unsigned lds_addr) {
 #endif
 }
 __device__ __forceinline__ void cs_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// s_waitcnt vmcnt(N) for the largest encodable N <= n of {8, 4, 2, 0} (n wave-uniform)
+__device__ __forceinline__ void cs_wait_vm(int n) {
+    if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else if (n >= 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+#ifdef YH_CSP_TRACE
+// experiments only (-DYH_CSP_TRACE builds; the shipped library has none of this): wave 0 of
+// every workgroup stamps s_memtime per tile, read back by yh_debug_csp_trace
+// (tools/csp_trace.py). Slots: 0 tile top, 1 after the top wait, 2 after the top barrier,
+// 3 / 4 wave 0 done with P1 / after P1's barrier (unset in tail mode), 5 / 6 the same for P2,
+// 7 / 8 for P3, 9 wave 0 done with P4, 10 s_memrealtime at the tile top, 11 = TH | TW << 16 |
+// (tile + 1) << 32. One record per (instantiation, workgroup, k-th tile of the workgroup).
+constexpr int CS_TR = 12, CS_TR_TILES = 16, CS_TR_WG = 256, CS_TR_OPS = 4;
+__device__ unsigned long long csp_trace_buf[CS_TR_OPS * CS_TR_WG * CS_TR_TILES * CS_TR];
+#define CS_STAMP(k) do { if (trp) trp[k] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define CS_STAMP(k) do { } while (0)
+#endif
 
 __device__ __forceinline__ uint4 cs_rd(unsigned addr) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -130,6 +152,37 @@ __device__ __forceinline__ void cs_act(const f32x16& acc, unsigned bias_addr, ui
     o[1] = *reinterpret_cast<const uint4*>(&t[8]);
 }
 
+// A 16-cout layer in a 32-cout tile leaves lane half 1 without outputs. Lane half 0's outputs
+// 8 .. 15 move over to it (v_permlane32_swap: rows 2-3 of the first operand take rows 0-1 of the
+// second), and every lane finishes 8 couts (8 hh .. 8 hh + 7) of its pixel as cs_act does, so the
+// epilogue issues half the exp / rcp. Both lanes of a pixel must be active. bias_addr: cout 0.
+template <typename T>
+__device__ __forceinline__ uint4 cs_act_half(const f32x16& acc, unsigned bias_addr, int hh) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+        v[e] = __uint_as_float(
+            __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[e]), __float_as_uint(acc[8 + e]), false, false)[0]);
+    const float4 b0 = cs_rdf(bias_addr + 32 * hh), b1 = cs_rdf(bias_addr + 32 * hh + 16);
+    v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
+    v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
+    T t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        // the product rounds to f32 before it rounds to T, as in cs_act and conv_mx: keep the
+        // compiler from folding both into one v_fma_mixlo_f16, which rounds once
+        float p = silu<T>(v[i]);
+        asm("" : "+v"(p));
+        t[i] = fromf<T>(p);
+    }
+    return *reinterpret_cast<const uint4*>(&t[0]);
+#else
+    (void)acc; (void)bias_addr; (void)hh;
+    return uint4{};
+#endif
+}
+
 // One conv phase: the NA x nb work items (32-cout A tile a, 32-pixel B tile) of an
 // npx-pixel region go round-robin to the waves; a wave runs two items at once (two
 // independent MFMA chains) while it has two. A image a = aimg + a * NK KB (fragments in lane
@@ -166,6 +219,10 @@ __device__ __forceinline__ void cs_phase(unsigned aimg, int npx, BAddr baddr, Ep
         }
     }
 }
+
+#ifdef YH_CSP_TRACE
+constexpr int cs_trace_op(int ni, int, int no) { return ni == 2 ? 0 : ni == 4 ? 1 : no == 2 ? 2 : 3; }   // YH_CSP_LIST order
+#endif
 
 template <typename T, int NI, int NC, int NO>
 __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
@@ -214,12 +271,35 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
     const int t0 = xcd_remap(blockIdx.x, gridDim.x);
     if (t0 < A.ntiles) load_x(t0);
 
+    // The top-of-tile wait covers the wave's input DMAs only, not the output stores issued after
+    // them: vector-memory operations retire in issue order, so vmcnt(N) is enough when at least N
+    // operations follow the last DMA. Those are the previous tile's P4 stores, two per work item
+    // of this wave (p4_stores) when that tile lay wholly inside the map; a clipped tile may skip
+    // stores, so it counts as none. Tail mode issues its DMA after P4: nothing is younger.
+    const int p4_items = NO * ((NP + 31) >> 5);
+    const int p4_stores = wvu < p4_items ? 2 * ((p4_items - wvu + NWV - 1) / NWV) : 0;
+    int young = 0;
+#ifdef YH_CSP_TRACE
+    int trk = 0;
+#endif
     for (int t = t0; t < A.ntiles; t += gridDim.x) {
         const int n = t / A.tiles, tix = t - n * A.tiles;
         const int ty = tix / A.ntw, tx = tix - ty * A.ntw;
         const int h0 = ty * TH, w0 = tx * TW;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMAs (and stores) done
+#ifdef YH_CSP_TRACE
+        unsigned long long* trp = nullptr;
+        if (threadIdx.x == 0 && blockIdx.x < CS_TR_WG && trk < CS_TR_TILES) {
+            trp = csp_trace_buf + ((size_t)(cs_trace_op(NI, NC, NO) * CS_TR_WG + blockIdx.x) * CS_TR_TILES + trk) * CS_TR;
+            trp[10] = __builtin_amdgcn_s_memrealtime();
+            trp[11] = (unsigned long long)TH | (unsigned long long)TW << 16 | (unsigned long long)(t + 1) << 32;
+        }
+        ++trk;
+#endif
+        CS_STAMP(0);
+        cs_wait_vm(young);   // this wave's input DMAs of this tile have landed
+        CS_STAMP(1);
         cs_barrier();
+        CS_STAMP(2);
 
         // P1: conv1 over the halo tile, X -> T1 (zero outside the image)
         if constexpr (!TAIL) {
@@ -236,7 +316,9 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                     cs_wr(d, o[0]);
                     cs_wr(d + 16, o[1]);
                 });
+        CS_STAMP(3);
         cs_barrier();
+        CS_STAMP(4);
         if (t + (int)gridDim.x < A.ntiles) load_x(t + gridDim.x);   // X is dead: next tile's input
         }
 
@@ -249,6 +331,14 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                 return LT + (unsigned)(((r + kh) * XW + cc + kw) * ST + 16 * NC + 16 * cb + 8 * hh) * 2;
             },
             [&](int, int px, const f32x16& acc) {
+                if constexpr (NH == 1) {   // 16 couts: both lane halves share the epilogue
+                    uint4 o = cs_act_half<T>(acc, lds0 + L.b2, hh);
+                    const int r = px / MW, cc = px - r * MW;
+                    const int gh = h0 - 1 + r, gw = w0 - 1 + cc;
+                    if (!((unsigned)gh < (unsigned)A.H && (unsigned)gw < (unsigned)A.W)) o = make_uint4(0, 0, 0, 0);
+                    cs_wr(LR + (unsigned)(px * SR + 8 * hh) * 2, o);
+                    return;
+                }
                 if (16 * hh >= 16 * NH) return;
                 uint4 o[2];
                 cs_act<T>(acc, lds0 + L.b2 + 16 * hh * 4, o);
@@ -259,7 +349,9 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                 cs_wr(d, o[0]);
                 cs_wr(d + 16, o[1]);
             });
+        CS_STAMP(5);
         cs_barrier();
+        CS_STAMP(6);
 
         // P3: Residual conv2 (3x3, R1 -> C2) + b over the tile
         cs_phase<T, NA3, 9 * NH>(
@@ -270,6 +362,18 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                     return LR + (unsigned)(((r + kh) * MW + cc + kw) * SR + 16 * cb + 8 * hh) * 2;
                 },
                 [&](int a, int px, const f32x16& acc) {
+                    if constexpr (NC == 1) {   // 16 couts: both lane halves share the epilogue
+                        const uint4 o = cs_act_half<T>(acc, lds0 + L.b3, hh);
+                        const int r = px / TW, cc = px - r * TW;
+                        const uint4 rv = cs_rd(LT + (unsigned)(((r + 2) * XW + cc + 2) * ST + 16 * NC + 8 * hh) * 2);
+                        const T* ov = reinterpret_cast<const T*>(&o);
+                        const T* rr = reinterpret_cast<const T*>(&rv);
+                        T s[8];
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) s[e] = fromf<T>(tof(ov[e]) + tof(rr[e]));
+                        cs_wr(LC + (unsigned)(px * SC + 8 * hh) * 2, *reinterpret_cast<const uint4*>(s));
+                        return;
+                    }
                     const int co = 32 * a + 16 * hh;
                     if (co >= 16 * NC) return;
                     uint4 o[2];
@@ -290,7 +394,9 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                     cs_wr(d, o[0]);
                     cs_wr(d + 16, o[1]);
                 });
+        CS_STAMP(7);
         cs_barrier();
+        CS_STAMP(8);
 
         // P4: conv2 over cat [a | b | C2] -> block output
         cs_phase<T, NO, 3 * NC>(
@@ -312,6 +418,8 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                         d[1] = o[1];
                     }
                 });
+        CS_STAMP(9);
+        if constexpr (!TAIL) young = h0 + TH <= A.H && w0 + TW <= A.W ? p4_stores : 0;
         if constexpr (TAIL) {   // T1 is read until here: the next tile's input after a barrier
             cs_barrier();
             if (t + (int)gridDim.x < A.ntiles) load_x(t + gridDim.x);
@@ -363,6 +471,13 @@ int csp_lds(int TH, int TW, int ni, int nc, int no) {
     const int b = cs_tile(TH, TW, ni, nc, no).total;
     return b <= 160 * 1024 ? b : 0;
 }
+
+#ifdef YH_CSP_TRACE
+extern "C" int yh_debug_csp_trace(unsigned long long* dst, int n) {
+    if (n > CS_TR_OPS * CS_TR_WG * CS_TR_TILES * CS_TR) n = CS_TR_OPS * CS_TR_WG * CS_TR_TILES * CS_TR;
+    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(csp_trace_buf), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
+}
+#endif
 
 int launch_csp(int dtype, const CspArgs& a, int grid, hipStream_t s) {
     switch (dtype) {

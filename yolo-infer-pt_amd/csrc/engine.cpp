@@ -232,6 +232,8 @@ struct Net {
     const std::vector<MxChoice>* cur_kern = nullptr;
     int force_kern = -1;   // candidate index (testing); -1 = autotune
     int num_cus = 0;
+    // plan string of every fused C3k2 launch made so far: c3k2_t<TH>x<TW>, per shape and op index
+    std::map<std::pair<GraphKey, int>, std::string> csp_plan;
     // launch units of the forward at the current shape (one op each)
     struct Unit { int first, last; bool level; };
     struct Plan {
@@ -783,18 +785,25 @@ struct Net {
         if (in.size() != 1 || in[0].up || in[0].v.C != logical[0] || logical[0] % 16 || c % 16 || out_ch % 32) return false;
         if (out.coff % 8 || in[0].v.coff % 8) return false;
         int TH, TW;
-        return csp_tile(logical[0] / 16, c / 16, out_ch / 32, 1 << 30, 1 << 30, TH, TW);
+        return csp_tile(logical[0] / 16, c / 16, out_ch / 32, 1, 1 << 30, 1 << 30, 1, TH, TW);
     }
     bool fuse_csp_tail(int c, int out_ch, View out) const {
         if (dtype == F32 || !opt.fuse) return false;
         if (c % 16 || out_ch % 32 || out.coff % 8) return false;
         int TH, TW;
-        return csp_tile(0, c / 16, out_ch / 32, 1 << 30, 1 << 30, TH, TW);
+        return csp_tile(0, c / 16, out_ch / 32, 1, 1 << 30, 1 << 30, 1, TH, TW);
     }
     // tail mode even where the whole block fits one launch (Options::csp_tail, tests)
     bool tail_first() const { return opt.csp_tail; }
-    static bool csp_tile(int ni, int nc, int no, int H, int W, int& TH, int& TW) {
-        // YH_CSP_TILE=<TH>x<TW> (experiments): that tile first where it fits one workgroup
+    // Work items of one tile over P1-P4 (c3k2.hip cs_phase: one 32-cout A tile x one 32-pixel
+    // B tile each); P1 and P2 run on the tile with its 2- / 1-pixel halo.
+    static int csp_items(int TH, int TW, int ni, int nc, int no) {
+        const auto nb = [](int px) { return (px + 31) / 32; };
+        return (ni ? nc * nb((TH + 4) * (TW + 4)) : 0) + nb((TH + 2) * (TW + 2)) + ((nc + 1) / 2 + no) * nb(TH * TW);
+    }
+    // Output tile of a fused C3k2 launch over B maps of H x W on `cus` persistent workgroups.
+    static bool csp_tile(int ni, int nc, int no, int B, int H, int W, int cus, int& TH, int& TW) {
+        // YH_CSP_TILE=<TH>x<TW> (experiments, tests): that tile first where it fits one workgroup
         if (const char* e = getenv("YH_CSP_TILE")) {
             int th = 0, tw = 0;
             if (sscanf(e, "%dx%d", &th, &tw) == 2 && th > 0 && tw > 0 && th <= H && tw <= W &&
@@ -804,17 +813,38 @@ struct Net {
                 return true;
             }
         }
-        // 16-wave workgroups (one per CU): the largest tile that fits (8 x 32 / 16 x 16 against
-        // 8-wave 8 x 16 pairs: bench +2.5 %, net.p3.1 65 -> 62 us, fpn.h2.tail 40 -> 37 us);
-        // 8-wave ones: the largest tile of >= 64 pixels that leaves room for a second workgroup
-        // per CU, else the largest that fits (measured: net.p3.1 at 2x4 tiles, two per CU,
-        // 263 us against 68 us at 8x16, one per CU)
-        static const int cand[][2] = {{8, 32}, {16, 16}, {8, 16}, {8, 8}, {4, 16}, {4, 8}, {2, 8}, {2, 4}};
-        const bool wide = CSP_THREADS >= 1024;
+        if (CSP_THREADS >= 1024) {
+            // 16-wave workgroups, one per CU: the tile that minimises rounds x cycles per tile.
+            // A tile costs CSP_TILE_FIXED cycles (the four phases' single-item latencies, paid
+            // whatever the size) + CSP_TILE_ITEM per work item (the epilogues' exp / rcp issue
+            // slots); both fitted to the per-tile stamps of 8x32, 8x16 and 4x16 tiles in
+            // profiles/csp_phase_stamps.txt (7.1-8.0 k and 200-285 over the three launches).
+            constexpr long long CSP_TILE_FIXED = 7400, CSP_TILE_ITEM = 230;
+            long long best = -1;
+            H = std::min(H, 1 << 12);   // callers that only ask whether a tile exists pass huge maps
+            W = std::min(W, 1 << 12);
+            for (int th : {2, 4, 8, 10, 12, 16}) {
+                if (th > H || (th == 2 && H >= 4)) continue;
+                for (int tw = 4; tw <= W; tw += 4) {
+                    if (csp_lds(th, tw, ni, nc, no) <= 0) break;   // grows with tw
+                    const long long nt = (long long)B * ((H + th - 1) / th) * ((W + tw - 1) / tw);
+                    const long long cost = ((nt + cus - 1) / cus) * (CSP_TILE_FIXED + CSP_TILE_ITEM * csp_items(th, tw, ni, nc, no));
+                    if (best < 0 || cost < best) {
+                        best = cost;
+                        TH = th;
+                        TW = tw;
+                    }
+                    if (nt <= cus) break;   // one round already: a wider tile only idles workgroups
+                }
+            }
+            return best >= 0;
+        }
+        // 8-wave workgroups: the largest tile of >= 64 pixels that leaves room for a second
+        // workgroup per CU, else the largest that fits (measured: net.p3.1 at 2x4 tiles, two per
+        // CU, 263 us against 68 us at 8x16, one per CU)
+        static const int cand[][2] = {{8, 16}, {8, 8}, {4, 16}, {4, 8}, {2, 8}, {2, 4}};
         for (int lim : {80 * 1024, 160 * 1024})
             for (auto& c : cand) {
-                if (wide && lim == 80 * 1024) break;
-                if (!wide && c[0] * c[1] > 128) continue;
                 if (c[0] > H || c[1] > W || (lim == 80 * 1024 && c[0] * c[1] < 64)) continue;
                 const int b = csp_lds(c[0], c[1], ni, nc, no);
                 if (b > 0 && b <= lim) {
@@ -1752,12 +1782,13 @@ struct Net {
                 a.ni = op.cs[0] >= 0 ? convs[op.cs[0]].cin / 16 : 0;
                 a.nc = convs[op.cs[1]].cin / 16;
                 a.no = convs[op.cs[3]].cout / 32;
-                require(csp_tile(a.ni, a.nc, a.no, a.H, a.W, a.TH, a.TW), op.label + ": no LDS tile");
+                if (!num_cus) HIPCHECK(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, device));
+                require(csp_tile(a.ni, a.nc, a.no, B, a.H, a.W, num_cus, a.TH, a.TW), op.label + ": no LDS tile");
+                csp_plan[{GraphKey{B, H, W}, (int)oi}] = "c3k2_t" + std::to_string(a.TH) + "x" + std::to_string(a.TW);
                 a.ntw = (a.W + a.TW - 1) / a.TW;
                 a.tiles = a.ntw * ((a.H + a.TH - 1) / a.TH);
                 a.ntiles = B * a.tiles;
                 a.zero = zero_dev;
-                if (!num_cus) HIPCHECK(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, device));
                 // two workgroups per CU when the LDS allows (measured: net.p2.1 138 -> 103 us at b32)
                 {
                     // persistent workgroups: as many as are resident at once (two per CU where the
@@ -2668,6 +2699,8 @@ int yh_op_kernel(const yh_handle* h, int index, int batch, int height, int width
         const yh::Op& op = n.ops[index];
         if (op.kind != yh::OP_CONV) {
             if (name) *name = yh::op_kind_name(op.kind);
+            auto cp = n.csp_plan.find({yh::GraphKey{batch, height, width}, index});
+            if (name && cp != n.csp_plan.end()) *name = cp->second.c_str();
             return;
         }
         if (n.dtype == yh::F32) {
