@@ -51,16 +51,18 @@ struct FirstConvArgs {
 struct Stem2Args {
     const void* const* io;   // io[0] = x (NCHW, 3 channels; uint8 when in_u8)
     int H, W, Hs, Ws, Ho, Wo, B;
-    const float* w1;         // stem weights [27][c1p] fp32 (k = ci*9 + kh*3 + kw)
-    const float* b1;         // stem bias [c1p]
-    int c1, c1p, c2;         // stem couts, its padded stride in w1, p2.0 couts
+    const float* b1;         // stem bias [c1 padded] fp32
+    int c1, c2;              // stem couts, p2.0 couts
     const void* prm;         // p2.0 fragments (c2/32 tiles x 9*c1/16 steps x 1 KB, MFMA lane order) + fp32 bias
     int prm_bias;            // byte offset of the bias in prm
+    int prm_stem;            // byte offset of the stem's own fragments in prm: c1/16 tiles x 1 KB,
+                             // lane (fr, g) holds cout 16 i + fr, k = 8 g .. 8 g + 7 (zero for k >= 27)
     void* out; int ldo;      // p2.0 output view
     int in_u8;
     int ntw, nth;            // tiles per row / per column (stem2_tiles)
 };
 bool stem2_ok(int c1, int c2);
+bool stem2_size_ok(int H, int W);   // the staging's 32-bit per-lane offsets cover one H x W image
 void stem2_tiles(int Ho, int Wo, int& ntw, int& nth);
 int launch_stem2(int dtype, const Stem2Args& a, hipStream_t s);
 

@@ -635,6 +635,11 @@ __device__ __forceinline__ unsigned s2_pack2(float a, float b) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, t2));
 }
 
+// byte offset of stem tap k = ci*9 + kh*3 + kw in the staged window (0 for the K padding)
+constexpr int s2_tap(int k) {
+    return k < 27 ? 2 * ((k / 9 * S2_IR + k % 9 / 3) * S2_ISEG + k % 3) : 0;
+}
+
 template <typename T, typename U, int C1, int C2>
 __global__ __launch_bounds__(S2_NT) void stem_fused(const Stem2Args p) {
     static_assert(sizeof(T) == 2, "16-bit path");
@@ -642,8 +647,7 @@ __global__ __launch_bounds__(S2_NT) void stem_fused(const Stem2Args p) {
     constexpr int KS = 9 * C1;       // p2.0 K steps
     constexpr int RPW = C2;          // output rows per wave (S2_TH rows x C2 cout tiles over 4 waves)
     static_assert(S2_TH * C2 == 4 * RPW, "4 waves");
-    // + one zero row: the padded K values (k >= 27) read it instead of branching
-    __shared__ __attribute__((aligned(16))) T patch[3 * S2_IR + 1][S2_ISEG];
+    __shared__ __attribute__((aligned(16))) T patch[3 * S2_IR][S2_ISEG];
     __shared__ uint4 sout[S2_NPX * PS];
     // (dispatch order kept: an XCD-aware order cut the input re-reads, 1.40x -> 1.00x of the
     // algorithmic bytes, but ran 75 -> 82 us)
@@ -661,33 +665,49 @@ __global__ __launch_bounds__(S2_NT) void stem_fused(const Stem2Args p) {
 #pragma unroll
         for (int s = 0; s < KS; ++s) af[s] = w2[s * 64];
     }
+    // stem weights / biases (conv_first_tile's fragments, packed at upload: one 16-B load each)
+    const int fr = lane & 15, g = lane >> 4;
+    uint4 wf[C1];
+    float4 bv[C1];
+    {
+        const uint4* w1 = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(p.prm) + p.prm_stem) + lane;
+#pragma unroll
+        for (int i = 0; i < C1; ++i) {
+            wf[i] = w1[i * 64];
+            bv[i] = *reinterpret_cast<const float4*>(p.b1 + 16 * i + 4 * g);
+        }
+    }
 
     // 1. input window: rows 4 ho0 - 3 .., columns 4 wo0 - 32 .. (64-B aligned rows for 16-bit
-    //    input: whole 64-B sectors, no partial-sector fetches at the row ends)
+    //    input: whole 64-B sectors, no partial-sector fetches at the row ends). Chunk c of the
+    //    window is 16-B chunk c of `patch`; a lane addresses image n's three planes with one
+    //    32-bit element offset from their uniform base (launch_stem2 bounds the image size).
     const U* x = reinterpret_cast<const U*>(p.io[0]);
     const int ir0 = 4 * ho0 - 3, ca = 4 * wo0 - 32;
-    const long long plane = (long long)p.H * p.W;
     {
         constexpr int TOT = 3 * S2_IR * S2_ICH;
         constexpr int NCH = (TOT + S2_NT - 1) / S2_NT;
         using Raw = typename std::conditional<sizeof(U) == 1, uint2, uint4>::type;
+        const unsigned plane = (unsigned)p.H * (unsigned)p.W;
+        const U* xn = x + (long long)n * 3 * plane;
         Raw raw[NCH];
         bool ok[NCH];
 #pragma unroll
         for (int u = 0; u < NCH; ++u) {
             const int c = min(tid + u * S2_NT, TOT - 1);
             const int seg = c / S2_ICH, ch = c - seg * S2_ICH;
-            const int ci = seg / S2_IR, rr = seg - ci * S2_IR;
+            const int rr = seg - (seg >= S2_IR ? S2_IR : 0) - (seg >= 2 * S2_IR ? S2_IR : 0);
             const int hi = ir0 + rr, col = ca + 8 * ch;
             ok[u] = hi >= 0 && hi < p.H && col >= 0 && col + 8 <= p.W;
             const int hc = min(max(hi, 0), p.H - 1), cc = min(max(col, 0), p.W - 8);
-            raw[u] = *reinterpret_cast<const Raw*>(x + ((long long)n * 3 + ci) * plane + (long long)hc * p.W + cc);
+            const unsigned off = (seg >= S2_IR ? plane : 0u) + (seg >= 2 * S2_IR ? plane : 0u) +
+                                 __umul24((unsigned)hc, (unsigned)p.W) + (unsigned)cc;
+            raw[u] = *reinterpret_cast<const Raw*>(xn + off);
         }
 #pragma unroll
         for (int u = 0; u < NCH; ++u) {
             const int c = tid + u * S2_NT;
             if (c >= TOT) continue;
-            const int seg = c / S2_ICH, ch = c - seg * S2_ICH;
             uint4 v;
             if constexpr (sizeof(U) == 1) {
                 float f[8];
@@ -698,72 +718,62 @@ __global__ __launch_bounds__(S2_NT) void stem_fused(const Stem2Args p) {
             } else {
                 v = raw[u];
             }
-            *reinterpret_cast<uint4*>(&patch[seg][ch * 8]) = ok[u] ? v : make_uint4(0, 0, 0, 0);
+            reinterpret_cast<uint4*>(&patch[0][0])[c] = ok[u] ? v : make_uint4(0, 0, 0, 0);
         }
     }
-    if (tid < S2_ISEG / 8) *reinterpret_cast<uint4*>(&patch[3 * S2_IR][tid * 8]) = make_uint4(0, 0, 0, 0);
-    // stem weights / biases (conv_first_tile's fragments)
-    const int fr = lane & 15, g = lane >> 4;
-    uint4 wf[C1];
-    float bv[C1][4];
+    // byte offsets of the lane's 8 taps (k = 8 g + j) from a pixel's window corner: constants
+    // selected by g. The padded taps (k >= 27: lanes g == 3, j >= 3) read the corner and are
+    // masked to zero in the packed fragment, as the zero row they used to read gave.
+    int kb[8];
 #pragma unroll
-    for (int i = 0; i < C1; ++i) {
-        float f[8];
-        const int co = 16 * i + fr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int k = 8 * g + j;
-            f[j] = k < 27 ? p.w1[k * p.c1p + co] : 0.f;
-        }
-        wf[i] = f_to_chunk<T>(f).v[0];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bv[i][r] = p.b1[16 * i + 4 * g + r];
-    }
-    int koff[8];
-    bool kok[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int k = 8 * g + j;
-        const int ci = k / 9, kh = (k - ci * 9) / 3, kw = k - ci * 9 - kh * 3;
-        kok[j] = k < 27;
-        koff[j] = kok[j] ? (ci * S2_IR + kh) * S2_ISEG + kw : 0;
-    }
+    for (int j = 0; j < 8; ++j)
+        kb[j] = g == 0 ? s2_tap(j) : g == 1 ? s2_tap(8 + j) : g == 2 ? s2_tap(16 + j) : s2_tap(24 + j);
+    const unsigned km1 = g == 3 ? 0xffffu : ~0u, km23 = g == 3 ? 0u : ~0u;
     __syncthreads();
 
-    // 2. stem pixels of the region: stem row 2 ho0 - 1 + sr, col 2 wo0 - 1 + sc; every group of
-    //    the wave unrolled (the LDS gathers of later groups overlap earlier groups' epilogues)
+    // 2. stem pixels of the region: stem row 2 ho0 - 1 + sr, col 2 wo0 - 1 + sc. Wave w owns
+    //    region columns 16 w .. 16 w + 15, one 16-pixel group per region row: from row to row a
+    //    lane's eight tap addresses and its store address move by constants (instruction
+    //    offsets), and the row's in-map test is uniform. The region's last column (sc = 4 * 16)
+    //    is one more group of wave 3 with lane fr on row fr (lanes past the last row repeat it).
+    //    Every group is unrolled: the LDS gathers of later groups overlap earlier epilogues.
     {
-        const T* pbase = &patch[0][0];
-        constexpr int NG = (S2_NPX + 15) / 16, NIT = (NG + S2_NT / 64 - 1) / (S2_NT / 64);
-        constexpr int ZIDX = 3 * S2_IR * S2_ISEG;   // the zero row
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int gi = wave + it * (S2_NT / 64);
-            if (gi >= NG) break;
-            const int q = min(gi * 16 + fr, S2_NPX - 1);
-            const int sr = q / S2_SC, sc = q - sr * S2_SC;
-            const int b0 = 2 * sr * S2_ISEG + 2 * sc + 29;
+        static_assert(S2_SC == 4 * 16 + 1 && S2_NT == 256 && S2_SR <= 16, "column blocks of the 4 waves");
+        const char* pbase = reinterpret_cast<const char*>(&patch[0][0]);
+        auto group = [&](const char* tap0, bool live, char* so) {
             T xv[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) xv[j] = pbase[kok[j] ? b0 + koff[j] : ZIDX];
-            const uint4 xf = *reinterpret_cast<const uint4*>(xv);
-            const int gs = 2 * ho0 - 1 + sr, gc = 2 * wo0 - 1 + sc;
-            const bool live = gs >= 0 && gs < p.Hs && gc >= 0 && gc < p.Ws;
+            for (int j = 0; j < 8; ++j) xv[j] = *reinterpret_cast<const T*>(tap0 + kb[j]);
+            uint4 xf = *reinterpret_cast<const uint4*>(xv);
+            xf.y &= km1; xf.z &= km23; xf.w &= km23;
 #pragma unroll
             for (int i = 0; i < C1; ++i) {
                 f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
                 Mma<T>::step(acc, &wf[i], &xf);
-                unsigned u[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = acc[r] + bv[i][r];
-                    v = silu<T>(v);
-                    u[r] = live ? (unsigned short)__builtin_bit_cast(short, fromf<T>(v)) : 0u;
-                }
-                if (gi * 16 + fr < S2_NPX)
-                    *reinterpret_cast<uint2*>(reinterpret_cast<char*>(sout) + q * PS * 16 + (16 * i + 4 * g) * 2) =
-                        make_uint2(u[0] | (u[1] << 16), u[2] | (u[3] << 16));
+                const unsigned u01 = s2_pack2<T>(silu<T>(acc[0] + bv[i].x), silu<T>(acc[1] + bv[i].y));
+                const unsigned u23 = s2_pack2<T>(silu<T>(acc[2] + bv[i].z), silu<T>(acc[3] + bv[i].w));
+                *reinterpret_cast<uint2*>(so + 32 * i) = make_uint2(live ? u01 : 0u, live ? u23 : 0u);
             }
+        };
+        // pixel (sr, sc): window corner at byte 2 * (2 sr S2_ISEG + 2 sc + 29), stored at pixel sr S2_SC + sc
+        const int sc = 16 * wave + fr;
+        const char* tap0 = pbase + 2 * (2 * sc + 29);
+        char* so = reinterpret_cast<char*>(sout) + sc * PS * 16 + 4 * g * 2;
+        const bool clive = (unsigned)(2 * wo0 - 1 + sc) < (unsigned)p.Ws;
+#pragma unroll
+        for (int sr = 0; sr < S2_SR; ++sr)
+            group(tap0 + sr * 4 * S2_ISEG, clive && (unsigned)(2 * ho0 - 1 + sr) < (unsigned)p.Hs,
+                  so + sr * S2_SC * PS * 16);
+        if (wave == 3) {
+            // lanes fr >= S2_SR recompute row S2_SR - 1 from the same taps and store the same bits
+            // to the same address as lane fr = S2_SR - 1, within the same store instruction of this
+            // one wave (no other wave touches column S2_SC - 1): whichever lane lands last, the
+            // value is the same. Clamping keeps their tap reads inside `patch`.
+            static_assert(S2_SR - 1 < 16, "the last region row must be a lane's own row");
+            const int sr = min(fr, S2_SR - 1);
+            group(pbase + sr * 4 * S2_ISEG + 2 * (2 * (S2_SC - 1) + 29),
+                  (unsigned)(2 * ho0 - 1 + sr) < (unsigned)p.Hs && (unsigned)(2 * wo0 - 1 + S2_SC - 1) < (unsigned)p.Ws,
+                  reinterpret_cast<char*>(sout) + (sr * S2_SC + S2_SC - 1) * PS * 16 + 4 * g * 2);
         }
     }
     __syncthreads();
@@ -1005,8 +1015,11 @@ void stem2_tiles(int Ho, int Wo, int& ntw, int& nth) {
     nth = (Ho + S2_TH - 1) / S2_TH;
 }
 
+// the staging's per-lane offsets: 32-bit elements within one image, 24-bit row x width product
+bool stem2_size_ok(int H, int W) { return H < (1 << 24) && W < (1 << 24) && 3ll * H * W < (1ll << 32); }
+
 int launch_stem2(int dtype, const Stem2Args& a, hipStream_t s) {
-    if (!stem2_ok(a.c1, a.c2) || a.W % 8 || a.ldo % 8) return (int)hipErrorInvalidValue;
+    if (!stem2_ok(a.c1, a.c2) || a.W % 8 || a.ldo % 8 || !stem2_size_ok(a.H, a.W)) return (int)hipErrorInvalidValue;
     switch (dtype) {
         case F16: return a.in_u8 ? launch_stem2_tu<_Float16, uint8_t>(a, s) : launch_stem2_tu<_Float16, _Float16>(a, s);
         case BF16: return a.in_u8 ? launch_stem2_tu<__bf16, uint8_t>(a, s) : launch_stem2_tu<__bf16, __bf16>(a, s);

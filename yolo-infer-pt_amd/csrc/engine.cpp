@@ -744,21 +744,41 @@ struct Net {
         return ci;
     }
     // the stem and net.p2.0 run fused (conv.hip stem_fused) on 16-bit handles for the
-    // instantiated widths (v11_n 16 -> 32, v11_s 32 -> 64)
+    // instantiated widths (v11_n 16 -> 32, v11_s 32 -> 64). The choice is made when the net is
+    // built, before any input size is known: the kernel addresses one image's three planes with
+    // 32-bit element offsets, so reserve() refuses an input with 3 * H * W >= 2^32 elements
+    // (stem2_size_ok) on a handle that fuses the stem.
     bool fuse_stem(int c0, int c1, int c2) const {
         if (dtype == F32 || !opt.fuse) return false;
         return c0 == 3 && stem2_ok(c1, c2);
     }
     // packed p2.0 parameters of the fused stem: fragments (tile a, step k = cb*9 + tap,
     // lane, j) in MFMA lane order with conv_mx's row permutation, then the fp32 bias
-    const void* stem2_params(const Op& op, int& bias_off) {
+    // and the stem's own fragments (tile i, lane (fr, g), j): cout 16 i + fr, k = 8 g + j of
+    // its 27 taps in conv_first_tile's order, zero for the K padding (cached in p2.0's mx_w;
+    // the stem conv holds a marker, so reloading either rebuilds it)
+    const void* stem2_params(const Op& op, int& bias_off, int& stem_off) {
         ConvDesc& d = convs[op.cs[0]];
+        ConvDesc& d1 = convs[op.conv];
         const int nt = d.cout / 32, nk = 9 * (d.cin / 16);
         bias_off = nt * nk * 1024;
+        stem_off = bias_off + d.cout * 4;
         auto it = d.mx_w.find("stem2");
-        if (it != d.mx_w.end()) return it->second;
-        require(d.loaded, "weights of " + d.name + " not loaded", YH_ESTATE);
-        std::vector<uint8_t> img((size_t)bias_off + (size_t)d.cout * 4, 0);
+        if (it != d.mx_w.end() && d1.mx_w.count("stem2_dep")) return it->second;
+        if (it != d.mx_w.end()) {
+            (void)hipFree(it->second);
+            d.mx_w.erase(it);
+        }
+        require(d.loaded && d1.loaded, "weights of " + d.name + " not loaded", YH_ESTATE);
+        std::vector<uint8_t> img((size_t)stem_off + (size_t)(d1.cout / 16) * 1024, 0);
+        uint16_t* sd = reinterpret_cast<uint16_t*>(img.data() + stem_off);
+        for (int i = 0; i < d1.cout / 16; ++i)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 8; ++j) {
+                    const int k = 8 * (lane >> 4) + j;
+                    const float v = k < 27 ? d1.wf[(size_t)(16 * i + (lane & 15)) * 27 + k] : 0.0f;
+                    sd[((size_t)i * 64 + lane) * 8 + j] = dtype == BF16 ? f2bf(v) : f2h(v);
+                }
         uint16_t* dst = reinterpret_cast<uint16_t*>(img.data());
         for (int a = 0; a < nt; ++a)
             for (int k = 0; k < nk; ++k)
@@ -776,6 +796,7 @@ struct Net {
         HIPCHECK(hipMalloc(&dev, img.size()));
         HIPCHECK(hipMemcpy(dev, img.data(), img.size(), hipMemcpyHostToDevice));
         d.mx_w.emplace("stem2", dev);
+        d1.mx_w.emplace("stem2_dep", nullptr);
         return dev;
     }
     // a C3k2 block with one Residual runs fused (c3k2.hip) on 16-bit handles when its input
@@ -1267,6 +1288,11 @@ struct Net {
     }
     void reserve(int B, int H, int W) {
         require(B > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0, "input height/width must be positive multiples of 32");
+        // the fused stem has no per-layer launch to fall back to: refuse the shape here, before
+        // anything is allocated, not at its launch
+        for (const Op& op : ops)
+            require(op.kind != OP_STEM2 || stem2_size_ok(H, W),
+                    "input image too large for the fused stem (3 * height * width must be below 2^32); set YH_FUSE=0");
         if (ws.base && ws.B == B && ws.H == H && ws.W == W) return;
         std::vector<size_t> offs;
         const size_t need = ws_bytes_for(B, H, W, &offs);
@@ -1756,10 +1782,9 @@ struct Net {
                 Stem2Args a{};
                 a.io = (const void* const*)io_dev;
                 a.H = H; a.W = W; a.Hs = H >> 1; a.Ws = W >> 1; a.Ho = H >> 2; a.Wo = W >> 2; a.B = B;
-                a.w1 = (const float*)d.w_dev;
                 a.b1 = d.b_dev;
-                a.c1 = d.cout; a.c1p = d.cout_p; a.c2 = convs[op.cs[0]].cout;
-                a.prm = stem2_params(op, a.prm_bias);
+                a.c1 = d.cout; a.c2 = convs[op.cs[0]].cout;
+                a.prm = stem2_params(op, a.prm_bias, a.prm_stem);
                 a.out = ptr(op.out);
                 a.ldo = ldc(op.out);
                 a.in_u8 = in_u8;
