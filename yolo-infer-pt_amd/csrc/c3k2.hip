@@ -11,6 +11,12 @@
 // K step) and biases are copied to LDS once per workgroup; the next tile's input DMA
 // runs during P2-P4.
 //
+// Nothing in the tile loop divides or builds a 64-bit address per lane: the DMA descriptors
+// (which chunk of which halo pixel a lane loads) are computed once per kernel, the tile walk
+// is (image, tile row, tile column) stepped with carries, a pixel's row is an exact
+// multiply-shift (cs_index_ok), and the map is addressed through a wave-uniform base per tile
+// plus a 32-bit lane offset (csp_span_ok).
+//
 // Bit-identical to the per-layer conv_mx launches (conv_mx.h): each conv walks its K
 // as  for 16-channel block: for tap: one v_mfma_f32_32x32x16 step  (channels past a
 // layer's width are zero), adds the bias, applies SiLU and rounds once; the residual
@@ -77,10 +83,16 @@ __device__ unsigned long long csp_trace_buf[CS_TR_OPS * CS_TR_WG * CS_TR_TILES *
 #define CS_STAMP(k) do { } while (0)
 #endif
 
+// every LDS address of this file is a multiple of 16 (region offsets, pixel strides of
+// 16 (2 n + 1) bytes, 16-byte channel groups): one ds_read_b128 / ds_write_b128 per access
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 cs_rd(unsigned addr) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(3))) const uint4* lp;
-    return *reinterpret_cast<lp>((size_t)addr);
+    // one native 16-byte vector load: a uint4 (four scalars) is split by the optimiser and put
+    // back together in 8-byte halves
+    typedef __attribute__((address_space(3))) const u32x4* lp;
+    const u32x4 v = *reinterpret_cast<lp>((size_t)addr);
+    return make_uint4(v[0], v[1], v[2], v[3]);
 #else
     (void)addr;
     return uint4{};
@@ -88,11 +100,18 @@ __device__ __forceinline__ uint4 cs_rd(unsigned addr) {
 }
 __device__ __forceinline__ void cs_wr(unsigned addr, uint4 v) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(3))) uint4* lp;
-    *reinterpret_cast<lp>((size_t)addr) = v;
+    typedef __attribute__((address_space(3))) u32x4* lp;
+    *reinterpret_cast<lp>((size_t)addr) = u32x4{v.x, v.y, v.z, v.w};
 #else
     (void)addr; (void)v;
 #endif
+}
+// byte offset of pixel px at a pixel stride of S elements (S * 2 bytes, a multiple of 16): the
+// shift keeps the multiple of 16 visible to the compiler, which the 24-bit multiply hides
+template <int S>
+__device__ __forceinline__ unsigned cs_px(unsigned px) {
+    static_assert(S % 8 == 0, "pixel strides are whole 16-byte chunks");
+    return __umul24(px, S / 8) << 4;
 }
 __device__ __forceinline__ float4 cs_rdf(unsigned addr) {
     const uint4 u = cs_rd(addr);
@@ -131,6 +150,20 @@ __host__ __device__ inline CsTile cs_tile(int TH, int TW, int ni, int nc, int no
     t.lc = t.lr + MP * (16 * nh + 8) * 2;
     t.total = t.lc + NP * (16 * nc + 8) * 2;
     return t;
+}
+
+// Index math of the kernel. px / width runs as hc_q24 at shift CS_DIV_S; a lane keeps the DMA
+// descriptors of at most cs_maxr rounds of CSP_THREADS 16-B chunks in registers (the input
+// region is at most (160 KB - parameters) / 2 whole-block, where T1 is as large again, and
+// about three quarters of it in tail mode). cs_index_ok is the host proof for a tile: csp_lds
+// offers no tile that fails it.
+constexpr int CS_DIV_S = 20;
+__host__ __device__ constexpr int cs_maxr(int ni) { return ni ? 4 : 6; }
+inline bool cs_index_ok(int TH, int TW, int ni, int nc) {
+    const long long XW = TW + 4, MW = TW + 2, XP = (TH + 4) * XW, MP = (TH + 2) * MW, NP = (long long)TH * TW;
+    const long long chunks = XP * ((ni ? 2 * ni : 4 * nc) + 1);
+    return TH + 4 < 0xffff && XW < 0xffff && chunks <= (long long)cs_maxr(ni) * CSP_THREADS &&
+           hc_exact(XP - 1, XW, CS_DIV_S) && hc_exact(MP - 1, MW, CS_DIV_S) && hc_exact(NP - 1, TW, CS_DIV_S);
 }
 
 // 16 consecutive outputs of one pixel (couts co0 .. co0 + 15): bias, SiLU, one rounding
@@ -186,36 +219,49 @@ __device__ __forceinline__ uint4 cs_act_half(const f32x16& acc, unsigned bias_ad
 // One conv phase: the NA x nb work items (32-cout A tile a, 32-pixel B tile) of an
 // npx-pixel region go round-robin to the waves; a wave runs two items at once (two
 // independent MFMA chains) while it has two. A image a = aimg + a * NK KB (fragments in lane
-// order); baddr(px, k) = LDS byte address of the lane's 8 K values of step k for region
-// pixel px; epi(a, px, acc) for pixels < npx.
-template <typename T, int NA, int NK, typename BAddr, typename Epi>
-__device__ __forceinline__ void cs_phase(unsigned aimg, int npx, BAddr baddr, Epi epi) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l32 = lane & 31;
+// order). A region pixel px is (row r, column cc) of a region RW pixels wide: r = px / RW by
+// the exact multiply-shift dv (csp_lds admits only tiles for which it is exact), once per item.
+// prep(px, r, cc) = the item's B base addresses (CsB), baddr(B, k) = LDS byte address of the
+// lane's 8 K values of step k (a base + an offset that is constant once k is unrolled);
+// epi(a, px, r, cc, acc) for pixels < npx. The first K step takes the MFMA's zero C operand.
+struct CsB {
+    unsigned b[3];
+};
+template <typename T, int NA, int NK, typename Prep, typename BAddr, typename Epi>
+__device__ __forceinline__ void cs_phase(unsigned aimg, int npx, HcDiv dv, int RW, Prep prep, BAddr baddr, Epi epi) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l32 = lane & 31;
     const int items = NA * ((npx + 31) >> 5);
+    f32x16 zero;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) zero[e] = 0.f;
     for (int i0 = wv; i0 < items; i0 += 2 * NWV) {
         const int i1 = i0 + NWV;
         const int a0 = i0 % NA, a1 = i1 % NA;
         const int p0 = (i0 / NA) * 32 + l32, p1 = (i1 / NA) * 32 + l32;
         const int c0 = p0 < npx ? p0 : npx - 1, c1 = p1 < npx ? p1 : npx - 1;
+        const int r0 = hc_q24(c0, dv), cc0 = c0 - (int)__umul24(r0, RW);
+        const CsB B0 = prep(c0, r0, cc0);
         const unsigned ai0 = aimg + (unsigned)(a0 * NK * 1024 + lane * 16);
-        const unsigned ai1 = aimg + (unsigned)(a1 * NK * 1024 + lane * 16);
-        f32x16 acc0, acc1;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
         if (i1 < items) {   // wave-uniform
+            const int r1 = hc_q24(c1, dv), cc1 = c1 - (int)__umul24(r1, RW);
+            const CsB B1 = prep(c1, r1, cc1);
+            const unsigned ai1 = aimg + (unsigned)(a1 * NK * 1024 + lane * 16);
+            f32x16 acc0, acc1;
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 const uint4 f0 = cs_rd(ai0 + k * 1024), f1 = NA > 1 ? cs_rd(ai1 + k * 1024) : f0;
-                const uint4 x0 = cs_rd(baddr(c0, k)), x1 = cs_rd(baddr(c1, k));
-                acc0 = CMfma<T>::step(f0, x0, acc0);
-                acc1 = CMfma<T>::step(f1, x1, acc1);
+                const uint4 x0 = cs_rd(baddr(B0, k)), x1 = cs_rd(baddr(B1, k));
+                acc0 = CMfma<T>::step(f0, x0, k ? acc0 : zero);
+                acc1 = CMfma<T>::step(f1, x1, k ? acc1 : zero);
             }
-            if (p0 < npx) epi(a0, p0, acc0);
-            if (p1 < npx) epi(a1, p1, acc1);
+            if (p0 < npx) epi(a0, p0, r0, cc0, acc0);
+            if (p1 < npx) epi(a1, p1, r1, cc1, acc1);
         } else {
+            f32x16 acc0;
 #pragma unroll
-            for (int k = 0; k < NK; ++k) acc0 = CMfma<T>::step(cs_rd(ai0 + k * 1024), cs_rd(baddr(c0, k)), acc0);
-            if (p0 < npx) epi(a0, p0, acc0);
+            for (int k = 0; k < NK; ++k)
+                acc0 = CMfma<T>::step(cs_rd(ai0 + k * 1024), cs_rd(baddr(B0, k)), k ? acc0 : zero);
+            if (p0 < npx) epi(a0, p0, r0, cc0, acc0);
         }
     }
 }
@@ -252,24 +298,50 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
     constexpr int NCH = TAIL ? 4 * NC : 2 * NI;   // 16-B data chunks per pixel
     constexpr int CPX = NCH + 1;                  // + one padding chunk per stored pixel
     const unsigned LD = TAIL ? LT : LX;
-    auto load_x = [&](int t) {
-        const int n = t / A.tiles, tix = t - n * A.tiles;
-        const int ty = tix / A.ntw, tx = tix - ty * A.ntw;
+    // row = px / width of the three regions without a division (hc_q24; exact: csp_lds)
+    const HcDiv dxw = hc_div(XW, CS_DIV_S), dmw = hc_div(MW, CS_DIV_S), dtw = hc_div(TW, CS_DIV_S);
+    // Input DMA descriptors, once per kernel: 16-B chunk q = 1024 j + thread of the halo tile is
+    // chunk c of halo pixel (r, cc) whatever the tile, so the lane keeps its byte offset from
+    // the tile's origin pixel and r | cc << 16 (r = 0xffff for a pad chunk or one past the end,
+    // which no row window contains). At most cs_maxr rounds: csp_lds.
+    constexpr int MAXR = cs_maxr(NI);
+    const int total = XP * CPX;
+    unsigned d_off[MAXR], d_rc[MAXR];
+#pragma unroll
+    for (int j = 0; j < MAXR; ++j) {
+        const int q = j * CSP_THREADS + (int)threadIdx.x;
+        const int px = q / CPX, c = q - px * CPX;
+        const int pc = px < XP ? px : XP - 1;
+        const int r = hc_q24(pc, dxw), cc = pc - (int)__umul24(r, XW);
+        d_rc[j] = q < total && c < NCH ? (unsigned)r | (unsigned)cc << 16 : 0xffffu;
+        d_off[j] = (__umul24(__umul24(r, A.W) + cc, A.ldx) + c * 8) * 2u;
+    }
+    // (n, ty, tx): image, tile row, tile column. The in-image tests are two window compares
+    // against wave-uniform bounds, the source a wave-uniform 64-bit base + the lane's offset.
+    auto load_x = [&](int n, int ty, int tx) {
         const int h0 = ty * TH - 2, w0 = tx * TW - 2;
-        const int total = XP * CPX;
-        for (int i0 = wvu * 64; i0 < total; i0 += CSP_THREADS) {
-            const int q = i0 + lane;
-            const int px = q / CPX, c = q - px * CPX;
-            const int r = px / XW, cc = px - r * XW;
-            const int gh = h0 + r, gw = w0 + cc;
-            const bool ok = q < total && c < NCH && (unsigned)gh < (unsigned)A.H && (unsigned)gw < (unsigned)A.W;
-            const void* src = ok ? (const void*)(x + (((long long)n * A.H + gh) * A.W + gw) * A.ldx + c * 8) : A.zero;
-            cs_glds(src, LD + i0 * 16);
+        const char* base = reinterpret_cast<const char*>(x + (((long long)n * A.H + h0) * A.W + w0) * A.ldx);
+        const unsigned rlo = h0 < 0 ? -h0 : 0, clo = w0 < 0 ? -w0 : 0;
+        const unsigned rn = min(TH + 4, A.H - h0) - rlo, cn = min(XW, A.W - w0) - clo;
+#pragma unroll
+        for (int j = 0; j < MAXR; ++j) {
+            const int i0 = j * CSP_THREADS + wvu * 64;
+            if (i0 < total) {   // wave-uniform
+                const unsigned r = d_rc[j] & 0xffffu, cc = d_rc[j] >> 16;
+                const bool ok = r - rlo < rn && cc - clo < cn;
+                const void* src = ok ? (const void*)(base + d_off[j]) : A.zero;
+                cs_glds(src, LD + i0 * 16);
+            }
         }
     };
     // XCD-aware: the workgroups of one XCD take neighbouring tiles (overlapping halos, one L2)
     const int t0 = xcd_remap(blockIdx.x, gridDim.x);
-    if (t0 < A.ntiles) load_x(t0);
+    // the tile walk t0, t0 + grid, ... as (n, ty, tx) with carries instead of two divisions per
+    // tile: one step is (gn, gty, gtx)
+    const int NG = gridDim.x;
+    const int gn = NG / A.tiles, gty = (NG - gn * A.tiles) / A.ntw, gtx = NG - gn * A.tiles - gty * A.ntw;
+    int n = t0 / A.tiles, ty = (t0 - n * A.tiles) / A.ntw, tx = t0 - n * A.tiles - ty * A.ntw;
+    if (t0 < A.ntiles) load_x(n, ty, tx);
 
     // The top-of-tile wait covers the wave's input DMAs only, not the output stores issued after
     // them: vector-memory operations retire in issue order, so vmcnt(N) is enough when at least N
@@ -282,10 +354,20 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
 #ifdef YH_CSP_TRACE
     int trk = 0;
 #endif
-    for (int t = t0; t < A.ntiles; t += gridDim.x) {
-        const int n = t / A.tiles, tix = t - n * A.tiles;
-        const int ty = tix / A.ntw, tx = tix - ty * A.ntw;
+    for (int t = t0; t < A.ntiles; t += NG) {
         const int h0 = ty * TH, w0 = tx * TW;
+        // the next tile of this workgroup
+        int nn = n + gn, nty = ty + gty, ntx = tx + gtx;
+        if (ntx >= A.ntw) { ntx -= A.ntw; ++nty; }
+        if (nty >= A.nth) { nty -= A.nth; ++nn; }
+        // in-image windows of the three regions (rows / columns r with r - lo < n, unsigned) and
+        // the output base of the tile's origin pixel: all wave-uniform
+        const unsigned rlo2 = h0 < 2 ? 2 - h0 : 0, clo2 = w0 < 2 ? 2 - w0 : 0;
+        const unsigned rn2 = min(TH + 4, A.H - h0 + 2) - rlo2, cn2 = min(XW, A.W - w0 + 2) - clo2;
+        const unsigned rlo1 = h0 < 1 ? 1 : 0, clo1 = w0 < 1 ? 1 : 0;
+        const unsigned rn1 = min(TH + 2, A.H - h0 + 1) - rlo1, cn1 = min(MW, A.W - w0 + 1) - clo1;
+        const unsigned rn0 = min(TH, A.H - h0), cn0 = min(TW, A.W - w0);
+        char* ybase = reinterpret_cast<char*>(y + (((long long)n * A.H + h0) * A.W + w0) * A.ldy);
 #ifdef YH_CSP_TRACE
         unsigned long long* trp = nullptr;
         if (threadIdx.x == 0 && blockIdx.x < CS_TR_WG && trk < CS_TR_TILES) {
@@ -304,48 +386,48 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
         // P1: conv1 over the halo tile, X -> T1 (zero outside the image)
         if constexpr (!TAIL) {
         cs_phase<T, NC, NI>(
-                lds0 + L.w1, XP,
-                [&](int px, int k) { return LX + (unsigned)(px * SX + 16 * k + 8 * hh) * 2; },
-                [&](int a, int px, const f32x16& acc) {
+                lds0 + L.w1, XP, dxw, XW,
+                [&](int px, int, int) { return CsB{{LX + cs_px<SX>(px) + 16 * hh, 0, 0}}; },
+                [&](const CsB& B, int k) { return B.b[0] + 32 * k; },
+                [&](int a, int px, int r, int cc, const f32x16& acc) {
                     uint4 o[2];
                     cs_act<T>(acc, lds0 + L.b1 + (32 * a + 16 * hh) * 4, o);
-                    const int r = px / XW, cc = px - r * XW;
-                    const int gh = h0 - 2 + r, gw = w0 - 2 + cc;
-                    if (!((unsigned)gh < (unsigned)A.H && (unsigned)gw < (unsigned)A.W)) o[0] = o[1] = make_uint4(0, 0, 0, 0);
-                    const unsigned d = LT + (unsigned)(px * ST + 32 * a + 16 * hh) * 2;
+                    if (!((unsigned)r - rlo2 < rn2 && (unsigned)cc - clo2 < cn2)) o[0] = o[1] = make_uint4(0, 0, 0, 0);
+                    const unsigned d = LT + cs_px<ST>(px) + (32 * a + 16 * hh) * 2;
                     cs_wr(d, o[0]);
                     cs_wr(d + 16, o[1]);
                 });
         CS_STAMP(3);
         cs_barrier();
         CS_STAMP(4);
-        if (t + (int)gridDim.x < A.ntiles) load_x(t + gridDim.x);   // X is dead: next tile's input
+        if (t + NG < A.ntiles) load_x(nn, nty, ntx);   // X is dead: next tile's input
         }
 
         // P2: Residual conv1 (3x3, b -> R1) over the 1-pixel halo region
         cs_phase<T, 1, 9 * NC>(
-            lds0 + L.w2, MP,
-            [&](int px, int k) {
-                const int cb = k / 9, tap = k - 9 * (k / 9), kh = tap / 3, kw = tap - 3 * (tap / 3);
-                const int r = px / MW, cc = px - r * MW;
-                return LT + (unsigned)(((r + kh) * XW + cc + kw) * ST + 16 * NC + 16 * cb + 8 * hh) * 2;
+            lds0 + L.w2, MP, dmw, MW,
+            [&](int, int r, int cc) {   // rows r, r + 1, r + 2 of T1 at column cc, the b half
+                const unsigned b0 = LT + cs_px<ST>(__umul24(r, XW) + cc) + (16 * NC + 8 * hh) * 2;
+                const unsigned rs = cs_px<ST>(XW);
+                return CsB{{b0, b0 + rs, b0 + 2 * rs}};
             },
-            [&](int, int px, const f32x16& acc) {
+            [&](const CsB& B, int k) {
+                const int cb = k / 9, tap = k - 9 * (k / 9), kh = tap / 3, kw = tap - 3 * (tap / 3);
+                return B.b[kh] + (kw * ST + 16 * cb) * 2;
+            },
+            [&](int, int px, int r, int cc, const f32x16& acc) {
+                const bool in = (unsigned)r - rlo1 < rn1 && (unsigned)cc - clo1 < cn1;
                 if constexpr (NH == 1) {   // 16 couts: both lane halves share the epilogue
                     uint4 o = cs_act_half<T>(acc, lds0 + L.b2, hh);
-                    const int r = px / MW, cc = px - r * MW;
-                    const int gh = h0 - 1 + r, gw = w0 - 1 + cc;
-                    if (!((unsigned)gh < (unsigned)A.H && (unsigned)gw < (unsigned)A.W)) o = make_uint4(0, 0, 0, 0);
-                    cs_wr(LR + (unsigned)(px * SR + 8 * hh) * 2, o);
+                    if (!in) o = make_uint4(0, 0, 0, 0);
+                    cs_wr(LR + cs_px<SR>(px) + 16 * hh, o);
                     return;
                 }
                 if (16 * hh >= 16 * NH) return;
                 uint4 o[2];
                 cs_act<T>(acc, lds0 + L.b2 + 16 * hh * 4, o);
-                const int r = px / MW, cc = px - r * MW;
-                const int gh = h0 - 1 + r, gw = w0 - 1 + cc;
-                if (!((unsigned)gh < (unsigned)A.H && (unsigned)gw < (unsigned)A.W)) o[0] = o[1] = make_uint4(0, 0, 0, 0);
-                const unsigned d = LR + (unsigned)(px * SR + 16 * hh) * 2;
+                if (!in) o[0] = o[1] = make_uint4(0, 0, 0, 0);
+                const unsigned d = LR + cs_px<SR>(px) + 32 * hh;
                 cs_wr(d, o[0]);
                 cs_wr(d + 16, o[1]);
             });
@@ -355,31 +437,35 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
 
         // P3: Residual conv2 (3x3, R1 -> C2) + b over the tile
         cs_phase<T, NA3, 9 * NH>(
-                lds0 + L.w3, NP,
-                [&](int px, int k) {
-                    const int cb = k / 9, tap = k - 9 * (k / 9), kh = tap / 3, kw = tap - 3 * (tap / 3);
-                    const int r = px / TW, cc = px - r * TW;
-                    return LR + (unsigned)(((r + kh) * MW + cc + kw) * SR + 16 * cb + 8 * hh) * 2;
+                lds0 + L.w3, NP, dtw, TW,
+                [&](int, int r, int cc) {   // rows r, r + 1, r + 2 of R1 at column cc
+                    const unsigned b0 = LR + cs_px<SR>(__umul24(r, MW) + cc) + 16 * hh;
+                    const unsigned rs = cs_px<SR>(MW);
+                    return CsB{{b0, b0 + rs, b0 + 2 * rs}};
                 },
-                [&](int a, int px, const f32x16& acc) {
+                [&](const CsB& B, int k) {
+                    const int cb = k / 9, tap = k - 9 * (k / 9), kh = tap / 3, kw = tap - 3 * (tap / 3);
+                    return B.b[kh] + (kw * SR + 16 * cb) * 2;
+                },
+                [&](int a, int px, int r, int cc, const f32x16& acc) {
+                    // the tile pixel's b in T1 (the residual)
+                    const unsigned tb = LT + cs_px<ST>(__umul24(r + 2, XW) + cc + 2) + 32 * NC;
                     if constexpr (NC == 1) {   // 16 couts: both lane halves share the epilogue
                         const uint4 o = cs_act_half<T>(acc, lds0 + L.b3, hh);
-                        const int r = px / TW, cc = px - r * TW;
-                        const uint4 rv = cs_rd(LT + (unsigned)(((r + 2) * XW + cc + 2) * ST + 16 * NC + 8 * hh) * 2);
+                        const uint4 rv = cs_rd(tb + 16 * hh);
                         const T* ov = reinterpret_cast<const T*>(&o);
                         const T* rr = reinterpret_cast<const T*>(&rv);
                         T s[8];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) s[e] = fromf<T>(tof(ov[e]) + tof(rr[e]));
-                        cs_wr(LC + (unsigned)(px * SC + 8 * hh) * 2, *reinterpret_cast<const uint4*>(s));
+                        cs_wr(LC + cs_px<SC>(px) + 16 * hh, *reinterpret_cast<const uint4*>(s));
                         return;
                     }
                     const int co = 32 * a + 16 * hh;
                     if (co >= 16 * NC) return;
                     uint4 o[2];
                     cs_act<T>(acc, lds0 + L.b3 + co * 4, o);
-                    const int r = px / TW, cc = px - r * TW;
-                    const unsigned rs = LT + (unsigned)(((r + 2) * XW + cc + 2) * ST + 16 * NC + co) * 2;
+                    const unsigned rs = tb + co * 2;
 #pragma unroll
                     for (int hf = 0; hf < 2; ++hf) {
                         const uint4 rv = cs_rd(rs + 16 * hf);
@@ -390,7 +476,7 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                         for (int e = 0; e < 8; ++e) s[e] = fromf<T>(tof(ov[e]) + tof(rr[e]));
                         o[hf] = *reinterpret_cast<const uint4*>(s);
                     }
-                    const unsigned d = LC + (unsigned)(px * SC + co) * 2;
+                    const unsigned d = LC + cs_px<SC>(px) + co * 2;
                     cs_wr(d, o[0]);
                     cs_wr(d + 16, o[1]);
                 });
@@ -400,20 +486,20 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
 
         // P4: conv2 over cat [a | b | C2] -> block output
         cs_phase<T, NO, 3 * NC>(
-                lds0 + L.w4, NP,
-                [&](int px, int k) {
-                    const int r = px / TW, cc = px - r * TW;
-                    return k < 2 * NC ? LT + (unsigned)(((r + 2) * XW + cc + 2) * ST + 16 * k + 8 * hh) * 2
-                                      : LC + (unsigned)(px * SC + 16 * (k - 2 * NC) + 8 * hh) * 2;
+                lds0 + L.w4, NP, dtw, TW,
+                [&](int px, int r, int cc) {   // [a | b] of the tile pixel in T1, its C2
+                    return CsB{{LT + cs_px<ST>(__umul24(r + 2, XW) + cc + 2) + 16 * hh,
+                                LC + cs_px<SC>(px) + 16 * hh, 0}};
                 },
-                [&](int a, int px, const f32x16& acc) {
+                [&](const CsB& B, int k) { return k < 2 * NC ? B.b[0] + 32 * k : B.b[1] + 32 * (k - 2 * NC); },
+                [&](int a, int, int r, int cc, const f32x16& acc) {
                     uint4 o[2];
                     const int co = 32 * a + 16 * hh;
                     cs_act<T>(acc, lds0 + L.b4 + co * 4, o);
-                    const int r = px / TW, cc = px - r * TW;
-                    const int gh = h0 + r, gw = w0 + cc;
-                    if ((unsigned)gh < (unsigned)A.H && (unsigned)gw < (unsigned)A.W) {
-                        uint4* d = reinterpret_cast<uint4*>(y + (((long long)n * A.H + gh) * A.W + gw) * A.ldy + co);
+                    if ((unsigned)r < rn0 && (unsigned)cc < cn0) {
+                        // 32-bit byte offset from the tile's origin pixel (launch_csp_t checks the range)
+                        const unsigned off = (__umul24(__umul24(r, A.W) + cc, A.ldy) + co) * 2u;
+                        uint4* d = reinterpret_cast<uint4*>(ybase + off);
                         d[0] = o[0];
                         d[1] = o[1];
                     }
@@ -422,8 +508,11 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
         if constexpr (!TAIL) young = h0 + TH <= A.H && w0 + TW <= A.W ? p4_stores : 0;
         if constexpr (TAIL) {   // T1 is read until here: the next tile's input after a barrier
             cs_barrier();
-            if (t + (int)gridDim.x < A.ntiles) load_x(t + gridDim.x);
+            if (t + NG < A.ntiles) load_x(nn, nty, ntx);
         }
+        n = nn;
+        ty = nty;
+        tx = ntx;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -436,6 +525,9 @@ template <typename T>
 int launch_csp_t(const CspArgs& a, int grid, hipStream_t s) {
     const int lds = csp_lds(a.TH, a.TW, a.ni, a.nc, a.no);
     if (lds == 0 || grid <= 0 || a.ldx % 8 || a.ldy % 8) return (int)hipErrorInvalidValue;
+    // a lane's 32-bit byte offset from its tile's origin pixel (input halo rows, output rows)
+    // goes through 24-bit multiplies: pixels of TH + 4 map rows below 2^24, bytes below 2^31
+    if (!csp_span_ok(a.TH, a.TW, a.W, a.ldx, a.ldy) || a.nth * a.ntw != a.tiles) return (int)hipErrorInvalidValue;
 #define YH_CSP_CASE(NI, NC, NO)                                                                              \
     if (a.ni == NI && a.nc == NC && a.no == NO) {                                                            \
         static bool attr = false;                                                                            \
@@ -467,7 +559,8 @@ int csp_lds(int TH, int TW, int ni, int nc, int no) {
 #define YH_CSP_HAS(NI, NC, NO) inst = inst || (ni == NI && nc == NC && no == NO);
     YH_CSP_LIST(YH_CSP_HAS)
 #undef YH_CSP_HAS
-    if (!inst || TH < 1 || TW < 1) return 0;
+    if (!inst || TH < 1 || TW < 1 || TH > 4096 || TW > 4096) return 0;
+    if (!cs_index_ok(TH, TW, ni, nc)) return 0;   // exact row / column quotients, descriptor rounds
     const int b = cs_tile(TH, TW, ni, nc, no).total;
     return b <= 160 * 1024 ? b : 0;
 }

@@ -10,6 +10,24 @@ inline int dtype_size(int dt) { return dt == F32 ? 4 : 2; }
 
 enum Act { ACT_ID = 0, ACT_SILU = 1 };
 
+// floor(n / d) for a run-time divisor without a division: (n * m) >> s with
+// m = floor(2^s / d) + 1. Exact for 0 <= n < 2^s / d while n * m < 2^32 (hc_exact is the host
+// proof for a numerator range). hc_q24 is the same quotient through the 24-bit multiplier
+// (full rate): n and m must be below 2^24 as well, which hc_exact(.., 20) implies for d >= 1.
+struct HcDiv {
+    unsigned m;
+    int s;
+};
+__host__ __device__ __forceinline__ HcDiv hc_div(int d, int s) { return HcDiv{(1u << s) / (unsigned)d + 1u, s}; }
+__host__ __device__ __forceinline__ int hc_q(int n, HcDiv f) { return (int)(((unsigned)n * f.m) >> f.s); }
+__device__ __forceinline__ int hc_q24(int n, HcDiv f) { return (int)(__umul24((unsigned)n, f.m) >> f.s); }
+// every hc_q / hc_q24 quotient n / d with 0 <= n <= nmax is exact at shift s (s <= 20 for hc_q24)
+inline bool hc_exact(long long nmax, long long d, int s) {
+    if (d < 1 || nmax < 0 || s > 24) return false;
+    const long long m = (1ll << s) / d + 1;
+    return nmax * d < (1ll << s) && nmax * m < (1ll << 32) && nmax < (1 << 24) && m < (1 << 24);
+}
+
 // Dense conv as an implicit GEMM over NHWC activations.
 //   GEMM rows M  = batch * Ho * Wo (output pixels)
 //   GEMM cols N  = Cout (physical, multiple of 8)
@@ -222,6 +240,7 @@ struct CspArgs {
     const void* prm;                 // packed weight fragments + fp32 biases (csp_prm_bytes)
     int ni, nc, no;                  // Cin / 16, c / 16, cout / 32
     int TH, TW, ntw, tiles, ntiles;  // output tile, tiles per row / per image / in total
+    int nth;                         // tile rows per image (tiles = ntw * nth)
     const void* zero;                // >= 16 zero bytes
 };
 #ifndef YH_CSP_THREADS
@@ -235,6 +254,14 @@ void csp_offsets(int ni, int nc, int no, int (&off)[9]);
 // LDS bytes for a TH x TW tile, 0 if it does not fit or (ni, nc, no) is not instantiated
 int csp_lds(int TH, int TW, int ni, int nc, int no);
 int launch_csp(int dtype, const CspArgs& a, int grid, hipStream_t s);
+// The kernel addresses the map through a wave-uniform 64-bit base per tile (its origin pixel)
+// and a 32-bit byte offset per lane that spans the tile's TH + 4 halo rows of the map. The
+// offset is built with 24-bit multiplies: the pixel offset and the pixel strides stay below
+// 2^24 and the byte offset below 2^31, whatever the map's height and the batch.
+inline bool csp_span_ok(int TH, int TW, int W, int ldx, int ldy) {
+    const long long px = (long long)(TH + 4) * W + TW + 4, ld = ldx > ldy ? ldx : ldy;
+    return W > 0 && ld > 0 && W < (1 << 24) && ld < (1 << 24) && px < (1 << 24) && (px * ld + ld) * 2 < (1ll << 31);
+}
 
 constexpr int BOX_DFL_TPW = 2;       // 32-pixel tiles per wave (4 waves per workgroup; YH_BOXDFL_TPW: 1 / 2 / 4)
 int launch_box_dfl(int dtype, const BoxDflArgs& a, hipStream_t s);

@@ -825,10 +825,12 @@ struct Net {
     // Output tile of a fused C3k2 launch over B maps of H x W on `cus` persistent workgroups.
     static bool csp_tile(int ni, int nc, int no, int B, int H, int W, int cus, int& TH, int& TW) {
         // YH_CSP_TILE=<TH>x<TW> (experiments, tests): that tile first where it fits one workgroup
+        // (a tile larger than the map is clipped like any edge tile). csp_lds admits a tile only
+        // if every multiply-shift quotient of the kernel's index math is exact for it, here and
+        // for the default choice below.
         if (const char* e = getenv("YH_CSP_TILE")) {
             int th = 0, tw = 0;
-            if (sscanf(e, "%dx%d", &th, &tw) == 2 && th > 0 && tw > 0 && th <= H && tw <= W &&
-                csp_lds(th, tw, ni, nc, no) > 0) {
+            if (sscanf(e, "%dx%d", &th, &tw) == 2 && th > 0 && tw > 0 && csp_lds(th, tw, ni, nc, no) > 0) {
                 TH = th;
                 TW = tw;
                 return true;
@@ -837,10 +839,12 @@ struct Net {
         if (CSP_THREADS >= 1024) {
             // 16-wave workgroups, one per CU: the tile that minimises rounds x cycles per tile.
             // A tile costs CSP_TILE_FIXED cycles (the four phases' single-item latencies, paid
-            // whatever the size) + CSP_TILE_ITEM per work item (the epilogues' exp / rcp issue
-            // slots); both fitted to the per-tile stamps of 8x32, 8x16 and 4x16 tiles in
-            // profiles/csp_phase_stamps.txt (7.1-8.0 k and 200-285 over the three launches).
-            constexpr long long CSP_TILE_FIXED = 7400, CSP_TILE_ITEM = 230;
+            // whatever the size) + CSP_TILE_ITEM per work item (LDS fragment reads and the
+            // epilogues' issue slots); both fitted to the per-tile stamps of 16x20, 8x32, 8x16
+            // and 4x16 tiles in profiles/cspidx_phase_stamps.txt (5.5-6.9 k and 150-160 for the
+            // whole-block launches; the tail launch, whose input DMA is not overlapped, is
+            // nearer 5.5 k + 270 and gets the same tile either way).
+            constexpr long long CSP_TILE_FIXED = 6000, CSP_TILE_ITEM = 165;
             long long best = -1;
             H = std::min(H, 1 << 12);   // callers that only ask whether a tile exists pass huge maps
             W = std::min(W, 1 << 12);
@@ -1811,7 +1815,11 @@ struct Net {
                 require(csp_tile(a.ni, a.nc, a.no, B, a.H, a.W, num_cus, a.TH, a.TW), op.label + ": no LDS tile");
                 csp_plan[{GraphKey{B, H, W}, (int)oi}] = "c3k2_t" + std::to_string(a.TH) + "x" + std::to_string(a.TW);
                 a.ntw = (a.W + a.TW - 1) / a.TW;
-                a.tiles = a.ntw * ((a.H + a.TH - 1) / a.TH);
+                // the kernel's per-lane offsets are 32-bit from the tile's origin pixel: a bound on the
+                // map's width only (about 2^20 pixels at these channel counts), not on its size
+                require(csp_span_ok(a.TH, a.TW, a.W, a.ldx, a.ldy), op.label + ": map too wide for 32-bit tile offsets");
+                a.nth = (a.H + a.TH - 1) / a.TH;
+                a.tiles = a.ntw * a.nth;
                 a.ntiles = B * a.tiles;
                 a.zero = zero_dev;
                 // two workgroups per CU when the LDS allows (measured: net.p2.1 138 -> 103 us at b32)

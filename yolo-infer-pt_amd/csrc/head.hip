@@ -121,12 +121,7 @@ __host__ __device__ inline HcLayout hc_layout(int TH, int TW, int C0, int c3) {
 // input pixels are read once and every output row has its own FMA chain (taps row-major).
 // floor(n / d) as (n * m) >> s with m = floor(2^s / d) + 1: exact for 0 <= n < 2^s / d (and
 // n * m < 2^32), which the tile index ranges here satisfy (tiles of at most 24 x 36 pixels)
-struct HcDiv {
-    unsigned m;
-    int s;
-};
-__device__ __forceinline__ HcDiv hc_div(int d, int s) { return HcDiv{(1u << s) / (unsigned)d + 1u, s}; }
-__device__ __forceinline__ int hc_q(int n, HcDiv f) { return (int)(((unsigned)n * f.m) >> f.s); }
+// (HcDiv, hc_div, hc_q: common.h)
 
 template <typename T>
 __device__ __forceinline__ void hc_dw(const T* src, int SW, int ss, T* dst, int DH, int DW, int ds, int c_lo, int C,
