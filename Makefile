@@ -12,14 +12,15 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Iinclude -I$(SRC) \
             -fhip-fp32-correctly-rounded-divide-sqrt -Wno-unused-result $(EXTRA)
 OBJS := $(OBJDIR)/engine.o $(OBJDIR)/conv.o $(OBJDIR)/misc.o $(OBJDIR)/nms.o $(OBJDIR)/conv_mx.o $(OBJDIR)/nms_host.o \
         $(OBJDIR)/preprocess.o $(OBJDIR)/head.o $(OBJDIR)/c3k2.o $(OBJDIR)/conv_rw.o $(OBJDIR)/c3k.o $(OBJDIR)/boxc.o $(OBJDIR)/pwchain.o \
-        $(OBJDIR)/match.o $(OBJDIR)/match_host.o $(OBJDIR)/merge.o $(OBJDIR)/merge_host.o
+        $(OBJDIR)/match.o $(OBJDIR)/match_host.o $(OBJDIR)/merge.o $(OBJDIR)/merge_host.o \
+        $(OBJDIR)/track.o $(OBJDIR)/track_host.o
 
 all: $(OUT)
 
 $(OBJDIR):
 	mkdir -p $(OBJDIR)
 
-$(OBJDIR)/engine.o: $(SRC)/engine.cpp $(SRC)/common.h $(SRC)/conv_mx.h $(SRC)/match_host.h $(SRC)/merge_host.h include/yolo_hip.h | $(OBJDIR)
+$(OBJDIR)/engine.o: $(SRC)/engine.cpp $(SRC)/common.h $(SRC)/conv_mx.h $(SRC)/match_host.h $(SRC)/merge_host.h $(SRC)/track_host.h include/yolo_hip.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(OBJDIR)/conv.o: $(SRC)/conv.hip $(SRC)/common.h $(SRC)/dtypes.h | $(OBJDIR)
@@ -70,6 +71,14 @@ $(OBJDIR)/merge.o: $(SRC)/merge.hip $(SRC)/common.h include/yolo_hip.h | $(OBJDI
 
 # HIP-free translation unit: plain C++, no device pass
 $(OBJDIR)/merge_host.o: $(SRC)/merge_host.cpp $(SRC)/merge_host.h include/yolo_hip.h | $(OBJDIR)
+	$(HIPCC) -x c++ -O3 -fPIC -std=c++17 -Iinclude -I$(SRC) -ffp-contract=off -c $< -o $@
+
+# shares its arithmetic with track_host.o through track_host.h: both without FMA contraction
+$(OBJDIR)/track.o: $(SRC)/track.hip $(SRC)/track_host.h $(SRC)/common.h include/yolo_hip.h | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
+
+# HIP-free translation unit: plain C++, no device pass
+$(OBJDIR)/track_host.o: $(SRC)/track_host.cpp $(SRC)/track_host.h include/yolo_hip.h | $(OBJDIR)
 	$(HIPCC) -x c++ -O3 -fPIC -std=c++17 -Iinclude -I$(SRC) -ffp-contract=off -c $< -o $@
 
 $(OUT): $(OBJS)

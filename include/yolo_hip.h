@@ -247,6 +247,67 @@ int yh_merge_host(const float* dets, const int* counts, int tiles, int max_det,
                   int images, int max_tiles, double iou_threshold, int max_out,
                   float* out, int* out_counts, int threads);
 
+/* Multi-object tracking over video streams, one launch per frame for all streams of a batch
+ * (no reference counterpart: the rules below are the specification; tests/_track_cases.py
+ * restates them in numpy). Row b of the NMS output dets (batch, max_det, 6) / counts (batch) is
+ * the next frame of stream stream_ids[b] (NULL: of stream b); the entries of stream_ids must be
+ * distinct, and a row whose id is outside [0, streams) writes count 0 and zero rows and touches
+ * no state. Frames of one stream must arrive in order.
+ *
+ * `state` is opaque: yh_track_state_bytes(streams, max_tracks) bytes, all-zero = no tracks, frame
+ * 0. It holds no pointers and has the same layout on host and device, so it can be copied
+ * between them (and saved) in the middle of a sequence. A stream owns max_tracks slots; a slot
+ * has a status (0 free, 1 tentative, 2 tracked, 3 lost), an id >= 1, the frame of its last
+ * match, a class and the state of ultralytics' KalmanFilterXYWH, stored as four independent
+ * (position x, velocity v, covariance a = Pxx, b = Pxv, c = Pvv) filters over cx, cy, w, h (its
+ * F, H, Q, R and initial P never couple the components).
+ *
+ * Per stream and call, in fp32 with one rounding per operation and no FMA; wh4 = (w, h, w, h),
+ * sq(c, u) = (c * u) * (c * u):
+ *   1. predict: f += 1; every slot that is not free: v[h] = 0 unless its status is 2; with wh4 of
+ *      the current x: x += v; a = ((a + 2 b) + c) + sq(0.05, wh4); b += c; c += sq(0.00625, wh4).
+ *      Its box is cx -+ w * 0.5, cy -+ h * 0.5.
+ *   2. rows 0 .. min(max(counts, 0), max_det) are read, the others never: "high" rows have
+ *      score >= track_high, "low" rows track_low <= score < track_high.
+ *   3. assoc(slots, rows, thr): the candidate pairs have equal class (f32 ==; not tested when
+ *      class_aware is 0), an intersection != 0 and iou = inter / ((area_t + area_d) - inter)
+ *      >= thr; they are walked by iou descending, then slot, then row ascending, and a pair is
+ *      taken when both sides are unmatched (greedy, not ByteTrack's lapjv). Three calls:
+ *      (status 2 or 3, high, iou_first); (status 2 still unmatched, low, iou_second);
+ *      (status 1, high still unmatched, iou_tentative).
+ *   4. a matched slot is updated with z = (centre, size) of its row: r = sq(0.05, wh4 of the
+ *      predicted x); S = a + r; kx = a / S; kv = b / S; y = z - x; x += kx y; v += kv y;
+ *      (a, b, c) = (a - kx a, b - kx b, c - kv b); its status becomes 2, its last frame f, its
+ *      class the row's. An unmatched status-2 slot becomes 3, an unmatched status-1 slot free;
+ *      then a status-3 slot with f - last frame > max_age becomes free.
+ *   5. births: the unmatched high rows with score >= track_new take, in row order, the free
+ *      slots in slot order (rows left over are dropped): x = z, v = 0, a = sq(0.1, wh4 of z),
+ *      b = 0, c = sq(0.0625, wh4 of z), the next id; status 2 in frame 1, else 1.
+ *   6. output: every slot of status 2 matched or born in this frame, ordered by its row, at most
+ *      max_out: out (batch, max_out, 6) = the box of the updated x, the row's score and class;
+ *      ids (batch, max_out) the track id; det_index (batch, max_out) the row; out_counts (batch).
+ *      Every byte of the four is written, rows beyond the count are 0.
+ * Inputs must be finite.
+ * yh_track: device pointers, one workgroup per batch row, asynchronous on `stream`, allocates
+ * nothing, never synchronises. yh_track_host: the same bytes for host pointers, rows in parallel
+ * over `threads` (<= 0: all hardware threads), synchronous.
+ * YH_EINVAL (message in yh_last_error()): max_tracks above YH_TRACK_MAX_TRACKS or max_det above
+ * YH_TRACK_MAX_DET, a negative size, max_tracks < 1, a NULL required pointer, track_low >
+ * track_high, max_age < 0. */
+#define YH_TRACK_MAX_TRACKS 1024
+#define YH_TRACK_MAX_DET 1024
+typedef struct {
+    float track_high, track_low, track_new, iou_first, iou_second, iou_tentative;
+    int max_age, class_aware;
+} yh_track_params;
+size_t yh_track_state_bytes(int streams, int max_tracks);
+int yh_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+             void* state, int streams, int max_tracks, const yh_track_params* p, int max_out,
+             float* out, int* ids, int* det_index, int* out_counts, void* stream);
+int yh_track_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+                  void* state, int streams, int max_tracks, const yh_track_params* p, int max_out,
+                  float* out, int* ids, int* det_index, int* out_counts, int threads);
+
 /* Letterbox geometry of one image for a square canvas of `size` (dataset.py:95-103,
  * 292-313): resized height / width (int(h * r), int(w * r) with r = size / max(h, w);
  * unchanged when r == 1) and the top / left border. */

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "yolo_hip.h"   // yh_track_params (launch_track)
+
 namespace yh {
 
 enum DType { F32 = 0, F16 = 1, BF16 = 2 };
@@ -346,5 +348,9 @@ int launch_match(const float* dets, const int* counts, int batch, int max_det, c
 int launch_merge(const float* dets, const int* counts, int tiles, int max_det, const float* tile_xf,
                  const int* tile_offsets, const float* image_wh, int images, int max_tiles, double iou_threshold,
                  int max_out, float* out, int* out_counts, hipStream_t s);
+// track.hip: one frame of every stream of a batch through its track table (yh_track); p by value
+int launch_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                 int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
+                 int* det_index, int* out_counts, hipStream_t s);
 
 }  // namespace yh

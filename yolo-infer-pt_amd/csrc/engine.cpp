@@ -20,6 +20,7 @@
 #include "conv_mx.h"
 #include "match_host.h"
 #include "merge_host.h"
+#include "track_host.h"
 #include "yolo_hip.h"
 
 
@@ -2634,6 +2635,36 @@ int yh_merge_host(const float* dets, const int* counts, int tiles, int max_det, 
         yh::require(!bad, bad ? bad : "");
         yh_merge_host_run(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images, max_tiles,
                           iou_threshold, max_out, out, out_counts, threads);
+    });
+}
+
+size_t yh_track_state_bytes(int streams, int max_tracks) {
+    if (streams < 0 || max_tracks < 1) return 0;
+    return (size_t)streams * yh_track_stream_words(max_tracks) * 4;
+}
+
+int yh_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+             int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids, int* det_index,
+             int* out_counts, void* stream) {
+    return guarded([&] {
+        const char* bad = yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
+                                         det_index, out_counts);
+        yh::require(!bad, bad ? bad : "");
+        const int rc = yh::launch_track(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, *p, max_out,
+                                        out, ids, det_index, out_counts, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("track launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_track_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                  int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
+                  int* det_index, int* out_counts, int threads) {
+    return guarded([&] {
+        const char* bad = yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
+                                         det_index, out_counts);
+        yh::require(!bad, bad ? bad : "");
+        yh_track_host_run(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
+                          det_index, out_counts, threads);
     });
 }
 

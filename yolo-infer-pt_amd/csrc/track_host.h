@@ -1,0 +1,168 @@
+// Internal interface of csrc/track_host.cpp (HIP-free): the argument check shared by the device
+// and the host entry point of the tracker, the host tracking loop, and - because the kernel
+// (csrc/track.hip) and the host twin must agree bit for bit - the state layout and the
+// arithmetic of one track, written once for both. The C ABI wrappers live in engine.cpp, which
+// owns yh_last_error()'s message. The semantics are stated in csrc/track_host.cpp.
+#ifndef YH_TRACK_HOST_H
+#define YH_TRACK_HOST_H
+
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+#include "yolo_hip.h"
+
+#ifdef __HIPCC__
+#define YH_TRACK_HD __host__ __device__ inline
+#else
+#define YH_TRACK_HD inline
+#endif
+
+// State of one stream, in 32-bit words (no pointers; host and device use the same bytes):
+//   [0] frame counter f   [1] ids handed out so far (next_id - 1)   [2] [3] zero
+//   then YH_TRACK_FIELDS arrays of max_tracks words, field major: word (field, slot) lies at
+//   YH_TRACK_HDR + field * max_tracks + slot.
+// All-zero bytes are the empty state. A slot that becomes free keeps its other fields (both
+// sides write the same values there), only its status is cleared.
+enum {
+    YH_TRACK_HDR = 4,
+    YH_TRK_STATUS = 0,   // int: 0 free, 1 tentative, 2 tracked, 3 lost
+    YH_TRK_ID = 1,       // int, >= 1
+    YH_TRK_LAST = 2,     // int: frame of the last match (or of the birth)
+    YH_TRK_CLS = 3,      // f32
+    YH_TRK_X = 4,        // f32 x 4 each: cx, cy, w, h
+    YH_TRK_V = 8,
+    YH_TRK_A = 12,       // Pxx
+    YH_TRK_B = 16,       // Pxv
+    YH_TRK_C = 20,       // Pvv
+    YH_TRACK_FIELDS = 24
+};
+
+YH_TRACK_HD size_t yh_track_stream_words(int max_tracks) {
+    return (size_t)YH_TRACK_HDR + (size_t)YH_TRACK_FIELDS * (size_t)max_tracks;
+}
+
+// The Kalman state of one slot: four independent (position, velocity) pairs.
+struct yh_track_kal {
+    float x[4], v[4], a[4], b[4], c[4];
+};
+
+struct yh_track_box {
+    float x1, y1, x2, y2;
+};
+
+// Written as in csrc/merge_host.cpp / csrc/merge.hip.
+YH_TRACK_HD float yh_trk_lesser(float a, float b) { return b < a ? b : a; }
+YH_TRACK_HD float yh_trk_greater(float a, float b) { return a < b ? b : a; }
+YH_TRACK_HD float yh_trk_clamp0(float v) { return v < 0.0f ? 0.0f : v; }
+YH_TRACK_HD float yh_trk_sq(float c, float u) {
+    const float s = c * u;
+    return s * s;
+}
+
+// step 1 of one non-free slot (status: as stored, before this frame)
+YH_TRACK_HD void yh_trk_predict(yh_track_kal& k, int status) {
+    if (status != 2) k.v[3] = 0.0f;
+    const float w = k.x[2], h = k.x[3];
+    for (int i = 0; i < 4; ++i) {
+        const float u = (i & 1) ? h : w;
+        const float qp = yh_trk_sq(0.05f, u);
+        const float qv = yh_trk_sq(0.00625f, u);
+        k.x[i] = k.x[i] + k.v[i];
+        k.a[i] = ((k.a[i] + 2.0f * k.b[i]) + k.c[i]) + qp;
+        k.b[i] = k.b[i] + k.c[i];
+        k.c[i] = k.c[i] + qv;
+    }
+}
+
+// the box of a state (steps 1 and 6)
+YH_TRACK_HD yh_track_box yh_trk_box(const yh_track_kal& k) {
+    const float hw = k.x[2] * 0.5f, hh = k.x[3] * 0.5f;
+    yh_track_box b;
+    b.x1 = k.x[0] - hw;
+    b.x2 = k.x[0] + hw;
+    b.y1 = k.x[1] - hh;
+    b.y2 = k.x[1] + hh;
+    return b;
+}
+
+// the measurement of a detection row
+YH_TRACK_HD void yh_trk_measure(const yh_track_box& d, float z[4]) {
+    z[0] = (d.x1 + d.x2) * 0.5f;
+    z[1] = (d.y1 + d.y2) * 0.5f;
+    z[2] = d.x2 - d.x1;
+    z[3] = d.y2 - d.y1;
+}
+
+// step 4 of a matched slot
+YH_TRACK_HD void yh_trk_update(yh_track_kal& k, const yh_track_box& d) {
+    float z[4];
+    yh_trk_measure(d, z);
+    const float w = k.x[2], h = k.x[3];
+    for (int i = 0; i < 4; ++i) {
+        const float u = (i & 1) ? h : w;
+        const float r = yh_trk_sq(0.05f, u);
+        const float a = k.a[i], b = k.b[i], c = k.c[i];
+        const float S = a + r;
+        const float kx = a / S;
+        const float kv = b / S;
+        const float y = z[i] - k.x[i];
+        k.x[i] = k.x[i] + kx * y;
+        k.v[i] = k.v[i] + kv * y;
+        k.a[i] = a - kx * a;
+        k.b[i] = b - kx * b;
+        k.c[i] = c - kv * b;
+    }
+}
+
+// step 5 of a new slot
+YH_TRACK_HD void yh_trk_birth(yh_track_kal& k, const yh_track_box& d) {
+    float z[4];
+    yh_trk_measure(d, z);
+    for (int i = 0; i < 4; ++i) {
+        const float u = (i & 1) ? z[3] : z[2];
+        k.x[i] = z[i];
+        k.v[i] = 0.0f;
+        k.a[i] = yh_trk_sq(0.1f, u);
+        k.b[i] = 0.0f;
+        k.c[i] = yh_trk_sq(0.0625f, u);
+    }
+}
+
+// step 3: is (slot box t, row box d) a candidate pair at threshold thr, and with which IoU?
+// (the class test is the caller's)
+YH_TRACK_HD bool yh_trk_pair(const yh_track_box& t, const yh_track_box& d, float thr, float& iou) {
+    const float w = yh_trk_clamp0(yh_trk_lesser(t.x2, d.x2) - yh_trk_greater(t.x1, d.x1));
+    const float h = yh_trk_clamp0(yh_trk_lesser(t.y2, d.y2) - yh_trk_greater(t.y1, d.y1));
+    const float inter = w * h;
+    if (inter == 0.0f) return false;
+    const float at = (t.x2 - t.x1) * (t.y2 - t.y1);
+    const float ad = (d.x2 - d.x1) * (d.y2 - d.y1);
+    iou = inter / ((at + ad) - inter);
+    return iou >= thr;
+}
+
+// An unsigned that orders like the float (merge's sort key): the pair order of step 3 is this
+// value descending, then the slot, then the row.
+YH_TRACK_HD uint32_t yh_trk_ord(float v) {
+    uint32_t u;
+#ifdef __HIP_DEVICE_COMPILE__
+    u = __float_as_uint(v);
+#else
+    std::memcpy(&u, &v, 4);
+#endif
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// NULL when the arguments are acceptable, else the message for yh_last_error() (YH_EINVAL).
+const char* yh_track_check(const void* dets, const void* counts, int batch, int max_det, const void* state,
+                           int streams, int max_tracks, const yh_track_params* p, int max_out, const void* out,
+                           const void* ids, const void* det_index, const void* out_counts);
+
+// The host twin proper; arguments already checked. Batch rows (streams) run in parallel over
+// `threads` (<= 0: every hardware thread).
+int yh_track_host_run(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+                      void* state, int streams, int max_tracks, const yh_track_params* p, int max_out, float* out,
+                      int* ids, int* det_index, int* out_counts, int threads);
+
+#endif

@@ -69,6 +69,11 @@ _PROTOS = {
                          c_int, c_void_p, c_void_p, c_void_p]),
     "yh_merge_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
                               c_int, c_void_p, c_void_p, c_int]),
+    "yh_track_state_bytes": (c_size_t, [c_int, c_int]),
+    "yh_track": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "yh_track_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "yh_letterbox_geometry": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_letterbox": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "yh_letterbox_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),

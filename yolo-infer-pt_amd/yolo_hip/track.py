@@ -1,0 +1,234 @@
+"""Object identities across the frames of many video streams, on the device.
+
+`nms` (and `Detector`) return boxes per frame; video users also need to know which box of this
+frame is which box of the last. This module keeps a track table per stream and advances all
+streams of a batch by one frame in a single launch, reading the fixed-size NMS output where it
+lies - no copy to the host, no synchronisation:
+
+  track        yh_track / yh_track_host: one frame of every stream of a batch (functional)
+  track_state  the zeroed state tensor of `streams` streams
+  Tracks       (dets, ids, det_index, counts) of one call
+  Tracker      the state, the thresholds and the buffers of a set of streams; `update` for a
+               caller's loop, `post` as the in-stream hook of a DetectPipeline
+
+The rules are ByteTrack's with ultralytics' KalmanFilterXYWH (a first association of the high
+scores with tracked and lost tracks, a second of the low scores with the tracks still unmatched,
+a third of the remaining high scores with the tentative tracks; new tracks are tentative for a
+frame), with two deliberate differences: the association is a greedy walk over the pairs by
+IoU where ByteTrack solves an assignment (lapjv), and it only pairs equal classes unless
+class_aware is off. Both make it deterministic, parallel and of the same shape as yh_match. There
+is no counterpart in the reference; the semantics are those stated in include/yolo_hip.h, pinned
+by the numpy restatement in tests/_track_cases.py.
+"""
+import ctypes
+from typing import NamedTuple
+
+import torch
+
+MAX_TRACKS = 1024   # YH_TRACK_MAX_TRACKS
+MAX_DET = 1024      # YH_TRACK_MAX_DET
+_HDR, _FIELDS = 4, 24   # state words per stream: _HDR + _FIELDS * max_tracks (csrc/track_host.h)
+
+
+class TrackParams(ctypes.Structure):
+    """yh_track_params"""
+    _fields_ = [("track_high", ctypes.c_float), ("track_low", ctypes.c_float), ("track_new", ctypes.c_float),
+                ("iou_first", ctypes.c_float), ("iou_second", ctypes.c_float), ("iou_tentative", ctypes.c_float),
+                ("max_age", ctypes.c_int), ("class_aware", ctypes.c_int)]
+
+
+def params(track_high=0.25, track_low=0.1, track_new=0.25, iou_first=0.2, iou_second=0.5, iou_tentative=0.3,
+           max_age=30, class_aware=True):
+    """The thresholds of `track` (yh_track_params). IoU thresholds are minimum overlaps: ByteTrack's
+    match_thresh 0.8 is a maximum cost 1 - IoU, i.e. iou_first = 0.2."""
+    return TrackParams(track_high, track_low, track_new, iou_first, iou_second, iou_tentative, int(max_age),
+                       1 if class_aware else 0)
+
+
+def track_state(streams, max_tracks=256, device="cpu"):
+    """The empty state of `streams` streams: (streams, 4 + 24 * max_tracks) int32 zeros. The words are
+    opaque, hold no addresses and mean the same on host and device: .cpu() / .to(device) / a file
+    carry a state over in the middle of a sequence."""
+    streams, max_tracks = int(streams), int(max_tracks)
+    if streams < 0 or not 1 <= max_tracks <= MAX_TRACKS:
+        raise ValueError(f"yolo_hip.track: streams must be >= 0 and max_tracks in [1, {MAX_TRACKS}]")
+    return torch.zeros((streams, _HDR + _FIELDS * max_tracks), dtype=torch.int32, device=device)
+
+
+class Tracks(NamedTuple):
+    """Result of one tracker call: dets (B, max_out, 6) f32 = x1, y1, x2, y2 of the track's filtered
+    box, then the score and class of the detection it was matched to; ids (B, max_out) i32 track
+    ids (>= 1, unique within a stream); det_index (B, max_out) i32 the row of that detection in
+    the input; counts (B,) i32. Rows beyond a count are 0."""
+    dets: torch.Tensor
+    ids: torch.Tensor
+    det_index: torch.Tensor
+    counts: torch.Tensor
+
+    def tolist(self):
+        """Per-stream (dets (k, 6), ids (k,), det_index (k,)) (reads counts on the host: synchronises
+        the current stream)."""
+        return [(self.dets[i, :k], self.ids[i, :k], self.det_index[i, :k]) for i, k in enumerate(self.counts.tolist())]
+
+
+def _check(name, t, shape, dtype, device):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"yolo_hip.track: {name} must be a tensor")
+    if t.dtype != dtype:
+        raise TypeError(f"yolo_hip.track: {name} must be {dtype}, got {t.dtype}")
+    if t.device != device:
+        raise ValueError(f"yolo_hip.track: {name} is on {t.device}, expected {device}")
+    if len(shape) != t.dim() or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+        want = tuple("*" if w is None else w for w in shape)
+        raise ValueError(f"yolo_hip.track: {name} has shape {tuple(t.shape)}, expected {want}")
+    if not t.is_contiguous():
+        raise ValueError(f"yolo_hip.track: {name} must be contiguous")
+
+
+def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, threads=0):
+    """One frame of every stream of a batch, in one launch.
+
+    dets (B, max_det, 6) f32 and counts (B,) i32 as `nms` or `Detector` return them (rows at or
+    beyond counts[b] are never read); state: a `track_state` tensor, advanced in place; p: `params()`
+    (default: its defaults); stream_ids (B,) i32 or None: row b is the next frame of stream
+    stream_ids[b] (None: of stream b). The ids must be distinct; a row whose id is outside
+    [0, streams) gets count 0 and touches no state. All on one device, all contiguous.
+    -> Tracks of (B, max_out, ...) (max_out defaults to max_det); out=(dets, ids, det_index, counts)
+    reuses buffers. Every byte is written.
+
+    cuda tensors run the HIP kernel (yh_track) asynchronously on the current stream, CPU tensors
+    the host twin (yh_track_host, `threads` <= 0: every hardware thread); both give the same bytes,
+    state included. Frames of one stream must be submitted in order on one stream."""
+    from ._lib import check, lib
+    if not isinstance(dets, torch.Tensor) or dets.dim() != 3:
+        raise ValueError("yolo_hip.track: dets must be a (B, max_det, 6) tensor")
+    dev = dets.device
+    B, md = dets.shape[0], dets.shape[1]
+    _check("dets", dets, (B, md, 6), torch.float32, dev)
+    _check("counts", counts, (B,), torch.int32, dev)
+    _check("state", state, (None, None), torch.int32, dev)
+    S, words = state.shape
+    if words < _HDR + _FIELDS or (words - _HDR) % _FIELDS:
+        raise ValueError(f"yolo_hip.track: state has {words} words per stream, expected 4 + 24 * max_tracks")
+    mt = (words - _HDR) // _FIELDS
+    if stream_ids is not None:
+        _check("stream_ids", stream_ids, (B,), torch.int32, dev)
+    max_out = md if max_out is None else int(max_out)
+    if out is None:
+        o = Tracks(torch.empty((B, max(max_out, 0), 6), dtype=torch.float32, device=dev),
+                   torch.empty((B, max(max_out, 0)), dtype=torch.int32, device=dev),
+                   torch.empty((B, max(max_out, 0)), dtype=torch.int32, device=dev),
+                   torch.empty((B,), dtype=torch.int32, device=dev))
+    else:
+        o = Tracks(*out)
+        _check("out dets", o.dets, (B, max_out, 6), torch.float32, dev)
+        _check("out ids", o.ids, (B, max_out), torch.int32, dev)
+        _check("out det_index", o.det_index, (B, max_out), torch.int32, dev)
+        _check("out counts", o.counts, (B,), torch.int32, dev)
+    p = params() if p is None else p
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    L = lib()
+    if mt <= MAX_TRACKS and L.yh_track_state_bytes(S, mt) != state.numel() * 4:
+        raise RuntimeError("yolo_hip.track: the library's state size differs from track_state's")
+    args = (ptr(dets), ptr(counts), B, md, ptr(stream_ids), ptr(state), S, mt, ctypes.byref(p), max_out,
+            ptr(o.dets), ptr(o.ids), ptr(o.det_index), ptr(o.counts))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            check(L.yh_track(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track")
+    elif dev.type == "cpu":
+        check(L.yh_track_host(*args, int(threads)), "track_host")
+    else:
+        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+    return o
+
+
+class Tracker:
+    """The tracks of `streams` video streams on one device.
+
+    update(dets, counts, stream_ids=None) (or update(detections) with a yolo_hip.Detections)
+    advances the streams of the batch by one frame and returns Tracks. stream_ids: None (row b is
+    stream b), a host sequence of ints (checked: distinct and inside [0, streams)) or an int32
+    tensor on the device (not checked: reading it would synchronise; the kernel ignores rows with
+    an id out of range, equal ids in one call are undefined).
+    post(dets, counts) is the same with row b = stream b, shaped as DetectPipeline's `post` hook:
+    it runs on the pipeline's NMS stream right behind each batch's NMS, and the batch's Tracks
+    come back as the `extra` of submit(), valid after `done`.
+    reset(streams=None) forgets every track (and optionally changes the number of streams);
+    `state` is the state tensor (save it, move it, or assign one of the same shape).
+
+    Order. Frames of one stream must reach the tracker in order, and the launches of one Tracker
+    must run on one stream (they update the state in place). update() on the caller's stream does.
+    Inside a DetectPipeline, the default configuration does: every batch's NMS, and with it post(),
+    runs on the single NMS stream in submission order, whatever the number of lanes. nms_on_lane
+    with several lanes does not: each lane's NMS runs on that lane's stream and batch k + 1 may
+    pass batch k. post() raises when it is called on another stream than its first call (reset()
+    clears that). A Tracker is constructed and reset on the current stream; submit() orders the
+    pipeline's work after it.
+
+    Nothing here reads a device value on the host. Outputs are allocated per call on the stream
+    the call runs on (DetectPipeline marks its `extra` for the caller's stream)."""
+
+    def __init__(self, streams, device, max_tracks=256, max_out=None, track_high=0.25, track_low=0.1, track_new=0.25,
+                 iou_first=0.2, iou_second=0.5, iou_tentative=0.3, max_age=30, class_aware=True):
+        self.device = torch.device(device)
+        self.max_tracks = int(max_tracks)
+        self.max_out = None if max_out is None else int(max_out)
+        if track_low > track_high:
+            raise ValueError("yolo_hip.Tracker: track_low must be <= track_high")
+        if max_age < 0:
+            raise ValueError("yolo_hip.Tracker: max_age must be >= 0")
+        self.params = params(track_high, track_low, track_new, iou_first, iou_second, iou_tentative, max_age,
+                             class_aware)
+        self.state = track_state(streams, self.max_tracks, self.device)
+        self._post_stream = None
+
+    @property
+    def streams(self):
+        return self.state.shape[0]
+
+    def reset(self, streams=None):
+        if streams is None or int(streams) == self.streams:
+            self.state.zero_()
+        else:
+            self.state = track_state(streams, self.max_tracks, self.device)
+        self._post_stream = None
+
+    def update(self, dets, counts=None, stream_ids=None, threads=0):
+        if counts is None:                       # a Detections
+            dets, counts = dets.dets, dets.counts
+        if stream_ids is not None and not isinstance(stream_ids, torch.Tensor):
+            host = [int(v) for v in stream_ids]
+            if len(set(host)) != len(host):
+                raise ValueError("yolo_hip.Tracker: stream_ids must be distinct")
+            if any(not 0 <= v < self.streams for v in host):
+                raise ValueError(f"yolo_hip.Tracker: stream_ids must lie in [0, {self.streams})")
+            stream_ids = torch.tensor(host, dtype=torch.int32).to(self.device, non_blocking=True)
+        elif stream_ids is None and isinstance(dets, torch.Tensor) and dets.dim() == 3 and dets.shape[0] > self.streams:
+            raise ValueError(f"yolo_hip.Tracker: a batch of {dets.shape[0]} rows for {self.streams} streams")
+        return track(dets, counts, self.state, self.params, stream_ids=stream_ids, max_out=self.max_out,
+                     threads=threads)
+
+    def post(self, dets, counts):
+        if self.device.type == "cuda":
+            cur = torch.cuda.current_stream(self.device)
+            if self._post_stream is None:
+                self._post_stream = cur
+            elif cur != self._post_stream:
+                raise RuntimeError("yolo_hip.Tracker.post: called on a second stream; frames are only in order on the "
+                                   "pipeline's single NMS stream (nms_on_lane=False, or one lane)")
+        return self.update(dets, counts)
+
+
+class _CallableModule(type(ctypes)):
+    """`yolo_hip.track` is this module as soon as it is imported, and the package also exports the
+    function of that name: calling the module calls the function."""
+
+    def __call__(self, *args, **kwargs):
+        return track(*args, **kwargs)
+
+
+import sys  # noqa: E402
+sys.modules[__name__].__class__ = _CallableModule
