@@ -1,6 +1,6 @@
 """Every conv_mx plan gives bit-identical forwards. Marked gpu.
 
-The per-shape autotuner (csrc/engine.cpp ensure_tuned) picks, per layer, one of
+The per-shape autotuner (csrc/net_launch.cpp ensure_tuned) picks, per layer, one of
 the layer's conv_mx candidate plans (csrc/conv_mx.hip: conv_mx with staged
 weights, conv_mxr with resident weights; csrc/conv_rw.hip: weights in VGPRs with a
 shared patch ring; different tile shapes, cout slices and 16-channel blocks per stage). That is only valid because every plan follows one

@@ -324,3 +324,93 @@ def test_pw_chain_equals_per_layer_launches(gpu, variant, dtype, batch, h, w, nc
     assert len(up) > len(uf)
     assert torch.isfinite(yf.float()).all()
     assert torch.equal(yf, yp), (yf.float() - yp.float()).abs().max().item()
+
+
+def _bare_engine(gpu, env):
+    """v11_n fp16 engine without weights, its environment set at handle creation like _engine()."""
+    from nets import nn
+    from yolo_hip.engine import Engine
+    model = nn.yolo_v11_n(80)
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        eng = Engine(*model._yh_arch, gpu, torch.float16)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+    return eng, model.state_dict()
+
+
+def _load_convs(eng, sd, names):
+    """The named convs of `eng` from state dict `sd`, one Engine._load each (load_state_dict's rule)."""
+    from yolo_hip.engine import _BN
+    for idx, conv in enumerate(eng.convs):
+        name = conv[0]
+        if name not in names:
+            continue
+        if f"{name}.conv.weight" in sd:
+            norm = None
+            if f"{name}.norm.weight" in sd:
+                norm = _BN(sd[f"{name}.norm.weight"], sd[f"{name}.norm.bias"], sd[f"{name}.norm.running_mean"],
+                           sd[f"{name}.norm.running_var"], 1e-3)
+            eng._load(idx, sd[f"{name}.conv.weight"], sd.get(f"{name}.conv.bias"), norm)
+        else:
+            eng._load(idx, sd[f"{name}.weight"], sd.get(f"{name}.bias"), None)
+
+
+@pytest.mark.parametrize("boxchain", [False, True])
+def test_reloaded_weights_reach_the_fused_kernels(gpu, boxchain):
+    """A fused op packs its member convs' weights into one cached device image on its first launch
+    (the fused stem, whole and tail C3k2, C3k, and with YH_BOXCHAIN=1 the box chain), head_cls / box_dfl /
+    the pointwise chains read per-conv device copies, and the captured graph holds all those
+    pointers. Loading weights again, all of them or a single member conv that does not own the
+    cache, must reach the next forward: bit-identical to an engine that only ever saw those weights."""
+    batch, h, w = 2, 96, 160
+    env = {"YH_BOXCHAIN": "1"} if boxchain else {}
+    x = synth.synth_scenes(batch, h, w, seed=53).to(gpu, torch.float16)
+    eng, template = _bare_engine(gpu, env)
+    sd_a = synth.synth_state_dict(template, seed=0)
+    sd_b = synth.synth_state_dict(template, seed=1)
+    every = {c[0] for c in eng.convs}
+
+    # 1. A, one forward: images packed, graph captured
+    _load_convs(eng, sd_a, every)
+    y_a = eng.forward(x).clone()
+    units = eng.units(batch, h, w)
+    kinds, labels = {u["cls"] for u in units}, [u["label"] for u in units]
+    assert {"c3k2", "c3k", "head_cls", "pw_chain"} <= kinds, kinds
+    assert "net.p1.0+p2.0" in labels and "net.p2.1" in labels and "fpn.h2.tail" in labels, labels
+    assert ("box_chain" in kinds and "box_dfl" not in kinds) if boxchain else "box_dfl" in kinds, kinds
+    # 2. B into the same engine
+    _load_convs(eng, sd_b, every)
+    y_b = eng.forward(x).clone()
+    fresh, _ = _bare_engine(gpu, env)
+    _load_convs(fresh, sd_b, every)
+    want_b = fresh.forward(x).clone()
+    assert torch.isfinite(want_b.float()).all()
+    assert torch.equal(y_b, want_b), (y_b.float() - want_b.float()).abs().max().item()
+    assert not torch.equal(y_b, y_a)
+
+    # 3. partial reload: per fused kind one member conv that does not own the cached image
+    #    (stem: the image lives with net.p2.0; whole C3k2: with conv1; tail C3k2 and C3k: with the
+    #    first conv of the op; box chain: with box.l.0), and one conv each of head_cls, box_dfl and
+    #    a pointwise chain
+    some = {"net.p1.0", "net.p2.1.res_m.0.conv2", "fpn.h2.conv2", "net.p4.1.res_m.0.res_m.1.conv1", "head.cls.0.3",
+            "head.box.1.2", "net.p5.2.conv1"}
+    if boxchain:
+        some.add("head.box.0.1")
+    assert some <= every, some - every
+    part, _ = _bare_engine(gpu, env)
+    _load_convs(part, sd_a, every)
+    assert torch.equal(part.forward(x), y_a)
+    _load_convs(part, sd_b, some)
+    y_mix = part.forward(x).clone()
+    mixed, _ = _bare_engine(gpu, env)
+    _load_convs(mixed, sd_a, every - some)
+    _load_convs(mixed, sd_b, some)
+    want_mix = mixed.forward(x).clone()
+    assert torch.equal(y_mix, want_mix), (y_mix.float() - want_mix.float()).abs().max().item()
+    assert not torch.equal(y_mix, y_a) and not torch.equal(y_mix, y_b)

@@ -1,6 +1,6 @@
 // Internal interface of csrc/match_host.cpp (HIP-free): the argument check shared by yh_match
-// and yh_match_host, and the host matching loop. The C ABI wrappers live in engine.cpp, which
-// owns yh_last_error()'s message.
+// and yh_match_host, and the host matching loop. The C ABI wrappers live in post_abi.cpp; host_util.h
+// holds yh_last_error()'s message.
 #ifndef YH_MATCH_HOST_H
 #define YH_MATCH_HOST_H
 

@@ -1,6 +1,6 @@
 // Internal interface of csrc/merge_host.cpp (HIP-free): the argument check shared by yh_merge
-// and yh_merge_host, and the host merge loop. The C ABI wrappers live in engine.cpp, which
-// owns yh_last_error()'s message.
+// and yh_merge_host, and the host merge loop. The C ABI wrappers live in post_abi.cpp; host_util.h
+// holds yh_last_error()'s message.
 #ifndef YH_MERGE_HOST_H
 #define YH_MERGE_HOST_H
 

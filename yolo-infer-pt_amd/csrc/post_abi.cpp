@@ -1,0 +1,179 @@
+// C ABI of the stages after the forward, none of which needs a handle: yh_nms (with its
+// workspace layout), yh_match, yh_merge, yh_track and their *_host twins.
+#include <algorithm>
+
+#include "common.h"
+#include "host_util.h"
+#include "match_host.h"
+#include "merge_host.h"
+#include "track_host.h"
+
+using yh::Fail;
+using yh::guarded;
+
+// NMS workspace: [counts B x i32][hist B x 2048 u32][state][gkeys][ents][mask], the split greedy's
+// first-batch scratch (yh::NmsArgs::state / gkeys / ents / mask), 256-byte aligned sections (no
+// per-candidate key list: the keys are made from the scores where they are needed, nms.hip
+// for_pairs)
+namespace {
+constexpr size_t NMS_STATE_B = 64, NMS_GK_B = 4096 * 8, NMS_ENTS_B = 3 * 4096 * 16, NMS_MASK_B = 64 * 64 * 65 / 2 * 8;
+size_t nms_al(size_t v) { return (v + 255) & ~(size_t)255; }
+size_t nms_off_hist(int B) { return nms_al((size_t)B * 4); }
+size_t nms_off_state(int B) { return nms_al(nms_off_hist(B) + (size_t)B * 2048 * 4); }
+size_t nms_off_gk(int B) { return nms_al(nms_off_state(B) + (size_t)B * NMS_STATE_B); }
+size_t nms_off_ents(int B) { return nms_al(nms_off_gk(B) + (size_t)B * NMS_GK_B); }
+size_t nms_off_mask(int B) { return nms_al(nms_off_ents(B) + (size_t)B * NMS_ENTS_B); }
+// the *_check functions return the complaint, or null
+void checked(const char* bad) { yh::require(!bad, bad ? bad : ""); }
+}  // namespace
+
+extern "C" {
+
+size_t yh_nms_workspace_bytes(int batch, int num_classes, int anchors) {
+    if (batch <= 0 || num_classes <= 0 || anchors <= 0) return 0;
+    return nms_off_mask(batch) + (size_t)batch * NMS_MASK_B;
+}
+
+#ifdef YH_ABLATION
+// Diagnostic builds only (make EXTRA=-DYH_ABLATION; not in the ABI header):
+// yh_debug_nms_trace(buf) makes later yh_nms calls record per-image phase timestamps
+// into the device buffer buf ([batch][16] u64, s_memrealtime ticks at 100 MHz).
+static unsigned long long* nms_trace = nullptr;
+int yh_debug_nms_trace(void* device_buf) {
+    nms_trace = (unsigned long long*)device_buf;
+    return 0;
+}
+#endif
+
+int yh_nms(int dtype, const void* y, int batch, int num_classes, int anchors, float conf_threshold,
+           double iou_threshold, int max_det, int max_nms, float max_wh, void* workspace, size_t workspace_bytes,
+           float* dets, int* counts, void* stream) {
+    return guarded([&] {
+        yh::require(y && dets && counts && workspace, "null argument");
+        yh::require(dtype == YH_F32 || dtype == YH_F16 || dtype == YH_BF16, "bad dtype");
+        yh::require(batch > 0 && anchors > 0 && num_classes > 0, "bad shape");
+        yh::require(max_det > 0 && max_det <= 1024, "max_det must be in [1, 1024]");
+        yh::require(max_nms > 0, "max_nms must be positive");
+        yh::require(conf_threshold >= 0.0f, "conf_threshold must be >= 0");
+        yh::require((long long)anchors * num_classes < (1ll << 26), "anchors * classes exceeds 2^26");
+        yh::require(workspace_bytes >= yh_nms_workspace_bytes(batch, num_classes, anchors), "NMS workspace too small");
+        yh::NmsArgs a{};
+        a.y = y; a.B = batch; a.A = anchors; a.nc = num_classes;
+        // compare in the input dtype: torch rounds the Python-float threshold to
+        // the tensor dtype before comparing (util.py:130,147)
+        float conf = conf_threshold;
+        if (dtype == YH_F16) {
+            const uint16_t hb = yh::f2h(conf);
+            const uint32_t ex = (hb >> 10) & 0x1f, mt = hb & 0x3ff;
+            conf = ex == 0 ? std::ldexp((float)mt, -24)
+                 : ex == 31 ? INFINITY : std::ldexp((float)(mt | 0x400), (int)ex - 25);
+        } else if (dtype == YH_BF16) {
+            const uint32_t u = (uint32_t)yh::f2bf(conf) << 16;
+            std::memcpy(&conf, &u, 4);
+        }
+        a.conf = conf;
+        // largest float <= iou_threshold: for any float ovr, ovr > thr (double) <=> ovr > a.iou
+        float t = (float)iou_threshold;
+        if ((double)t > iou_threshold) t = std::nextafter(t, -INFINITY);
+        a.iou = t;
+        a.max_wh = max_wh;
+        a.max_det = max_det;
+        a.max_nms = max_nms;
+#ifdef YH_ABLATION
+        a.trace = nms_trace;
+        a.dbg = getenv("YH_NMS_DBG") ? atoi(getenv("YH_NMS_DBG")) : 0;
+#endif
+        char* ws = (char*)workspace;
+        a.counts = (int*)ws;
+        a.hist = (unsigned*)(ws + nms_off_hist(batch));
+        a.state = (unsigned long long*)(ws + nms_off_state(batch));
+        a.gkeys = (unsigned long long*)(ws + nms_off_gk(batch));
+        a.ents = (float*)(ws + nms_off_ents(batch));
+        a.mask = (unsigned long long*)(ws + nms_off_mask(batch));
+        {   // lowest bin at the threshold (or 2047 bins below 1.0 for tiny thresholds)
+            uint32_t cb;
+            std::memcpy(&cb, &a.conf, 4);
+            const int one = 0x3F80;
+            a.bin_base = std::max((int)(cb >> 16), one - 2047);
+        }
+        a.dets = dets;
+        a.ndet = counts;
+        const int rc = yh::launch_nms(dtype, a, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("NMS launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_match(const float* dets, const int* counts, int batch, int max_det, const float* labels,
+             const int* label_offsets, const float* iou_v, int num_iou, uint8_t* tp, float* score_cls,
+             int* counts_out, void* stream) {
+    return guarded([&] {
+        static_assert(YH_MATCH_MAX_DET >= 1024, "the ABI promises at least 1024");
+        checked(yh_match_check(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp));
+        const int rc = yh::launch_match(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp,
+                                        score_cls, counts_out, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("match launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_match_host(const float* dets, const int* counts, int batch, int max_det, const float* labels,
+                  const int* label_offsets, const float* iou_v, int num_iou, uint8_t* tp, float* score_cls,
+                  int* counts_out, int threads) {
+    return guarded([&] {
+        checked(yh_match_check(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp));
+        yh_match_host_run(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp, score_cls,
+                          counts_out, threads);
+    });
+}
+
+int yh_merge(const float* dets, const int* counts, int tiles, int max_det, const float* tile_xf,
+             const int* tile_offsets, const float* image_wh, int images, int max_tiles, double iou_threshold,
+             int max_out, float* out, int* out_counts, void* stream) {
+    return guarded([&] {
+        checked(yh_merge_check(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images,
+                               max_tiles, max_out, out, out_counts));
+        const int rc = yh::launch_merge(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images,
+                                        max_tiles, iou_threshold, max_out, out, out_counts, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("merge launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_merge_host(const float* dets, const int* counts, int tiles, int max_det, const float* tile_xf,
+                  const int* tile_offsets, const float* image_wh, int images, int max_tiles, double iou_threshold,
+                  int max_out, float* out, int* out_counts, int threads) {
+    return guarded([&] {
+        checked(yh_merge_check(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images,
+                               max_tiles, max_out, out, out_counts));
+        yh_merge_host_run(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images, max_tiles,
+                          iou_threshold, max_out, out, out_counts, threads);
+    });
+}
+
+size_t yh_track_state_bytes(int streams, int max_tracks) {
+    if (streams < 0 || max_tracks < 1) return 0;
+    return (size_t)streams * yh_track_stream_words(max_tracks) * 4;
+}
+
+int yh_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+             int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids, int* det_index,
+             int* out_counts, void* stream) {
+    return guarded([&] {
+        checked(yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
+                               det_index, out_counts));
+        const int rc = yh::launch_track(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, *p, max_out,
+                                        out, ids, det_index, out_counts, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("track launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_track_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                  int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
+                  int* det_index, int* out_counts, int threads) {
+    return guarded([&] {
+        checked(yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
+                               det_index, out_counts));
+        yh_track_host_run(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
+                          det_index, out_counts, threads);
+    });
+}
+
+}  // extern "C"

@@ -1,8 +1,8 @@
 // Internal interface of csrc/track_host.cpp (HIP-free): the argument check shared by the device
 // and the host entry point of the tracker, the host tracking loop, and - because the kernel
 // (csrc/track.hip) and the host twin must agree bit for bit - the state layout and the
-// arithmetic of one track, written once for both. The C ABI wrappers live in engine.cpp, which
-// owns yh_last_error()'s message. The semantics are stated in csrc/track_host.cpp.
+// arithmetic of one track, written once for both. The C ABI wrappers live in post_abi.cpp; host_util.h
+// holds yh_last_error()'s message. The semantics are stated in csrc/track_host.cpp.
 #ifndef YH_TRACK_HOST_H
 #define YH_TRACK_HOST_H
 
