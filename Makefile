@@ -49,6 +49,8 @@ $(call objs,$(HOSTCXX)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/%.h include/yolo_hip
 $(call objs,conv_mx conv_rw): $(SRC)/conv_mx.h
 # shares its arithmetic with track_host.o through track_host.h
 $(OBJDIR)/track.o: $(SRC)/track_host.h
+# reports its argument errors through host_util.h's guarded()
+$(OBJDIR)/preprocess.o: $(SRC)/host_util.h
 
 $(OUT): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)

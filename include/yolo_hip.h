@@ -26,6 +26,9 @@
  *   yh_letterbox        utils/dataset.py:95-103, 292-313, 86-88: eval-mode load_image resize
  *                       (cv2 INTER_LINEAR) + zero border + HWC->CHW, BGR->RGB, on the device
  *   yh_letterbox_host   the same on the host (Dataset.__getitem__ in the loader workers)
+ *   yh_letterbox_frames no reference counterpart: the same letterbox for video - BGR or NV12 frames
+ *                       onto a square or rectangular canvas (yh_letterbox is this for BGR, square)
+ *   yh_letterbox_frames_host, yh_nv12_to_bgr_host   the same, and the conversion alone, on the host
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -324,6 +327,60 @@ int yh_letterbox_geometry(int height, int width, int size, int* new_h, int* new_
 int yh_letterbox(const void* const* srcs, const int* heights, const int* widths, const int* strides,
                  int batch, int size, void* dst, void* stream);
 int yh_letterbox_host(const void* src, int height, int width, int stride, int size, void* dst, int threads);
+
+/* Video front end: BGR or NV12 frames onto a rectangular canvas, one launch per 32 frames.
+ *
+ *   frames:  host array of `batch` descriptors; the planes are device memory for
+ *            yh_letterbox_frames and host memory for the two _host calls
+ *   dst:     uint8 (batch, 3, canvas_h, canvas_w), RGB, CHW - the input of yh_forward_u8 (which
+ *            needs both canvas sides to be multiples of 32; the letterbox itself needs
+ *            canvas_w % 4 == 0). Every byte is written.
+ * yh_letterbox_frames is asynchronous on `stream`, allocates nothing and never synchronises.
+ * yh_letterbox_frames_host computes the same bytes for one frame (dst (3, canvas_h, canvas_w));
+ * `threads` > 1 splits the rows. yh_letterbox / yh_letterbox_host are these two calls for BGR
+ * frames on a square canvas.
+ *
+ * Geometry (yh_letterbox_geometry2), in double: r = min(canvas_h / height, canvas_w / width);
+ * if r != 1, new_w = (int)(width * r) and new_h = (int)(height * r), else the frame's own size;
+ * top = nearbyint((canvas_h - new_h) / 2.0 - 0.1), left likewise from the widths. For
+ * canvas_h == canvas_w == size, r is the same division as size / max(height, width), so the
+ * result equals yh_letterbox_geometry's exactly.
+ *
+ * NV12 to BGR: integer arithmetic with shift 20, limited range, nearest chroma - pixel (y, x)
+ * uses the U, V pair at (y >> 1, x >> 1). Constants (CY, CUB, CUG, CVG, CVR):
+ *   YH_YUV_BT601  (1220542, 2116026, -409993, -852492, 1673527) = round(c * 2^20) of 1.164,
+ *                 2.018, -0.391, -0.813, 1.596 (OpenCV's published COLOR_YUV2BGR_NV12 constants)
+ *   YH_YUV_BT709  (1220542, 2214593, -223347, -558891, 1880097) = round(c * 2^20) of 1.164,
+ *                 2.112, -0.213, -0.533, 1.793
+ * With yy = max(0, Y - 16) * CY, u = U - 128, v = V - 128:
+ *   R = sat_u8((yy + (1 << 19) + CVR * v) >> 20)
+ *   G = sat_u8((yy + (1 << 19) + CVG * v + CUG * u) >> 20)
+ *   B = sat_u8((yy + (1 << 19) + CUB * u) >> 20)
+ * cv2 is not available to the tests, so parity against cv2 itself is unpinned (as for the resize).
+ *
+ * Composition: for an NV12 frame the canvas is, byte for byte, the BGR letterbox of
+ * yh_nv12_to_bgr_host(frame): resize, INTER_AREA fast path, vector/scalar tail rule, border and
+ * channel flip are those of yh_letterbox. Only the source taps the resize reads are converted;
+ * no BGR image is materialised.
+ *
+ * YH_EINVAL (message in yh_last_error()): an NV12 frame of odd height or width, a stride smaller
+ * than the row, a NULL required plane, an unknown format or matrix, a resized side below 1 or
+ * beyond the canvas, canvas_w % 4 != 0 (yh_letterbox_frames). Nothing is launched then. */
+#define YH_PIX_BGR   0   /* HWC BGR uint8, as yh_letterbox */
+#define YH_PIX_NV12  1   /* plane0 = Y (height x width), plane1 = interleaved U,V (height/2 rows of width bytes) */
+#define YH_YUV_BT601 0   /* limited range; OpenCV's COLOR_YUV2BGR_NV12 */
+#define YH_YUV_BT709 1   /* limited range */
+typedef struct {
+    const void* plane0; const void* plane1;   /* plane1 ignored for BGR */
+    int height, width;                        /* NV12: both even */
+    int stride0, stride1;                     /* bytes per row; 0 = tight */
+    int format, matrix;
+} yh_frame;
+int yh_letterbox_geometry2(int height, int width, int canvas_h, int canvas_w, int* new_h, int* new_w, int* top,
+                           int* left);
+int yh_letterbox_frames(const yh_frame* frames, int batch, int canvas_h, int canvas_w, void* dst, void* stream);
+int yh_letterbox_frames_host(const yh_frame* frame, int canvas_h, int canvas_w, void* dst, int threads);
+int yh_nv12_to_bgr_host(const yh_frame* frame, void* dst_bgr /* height x width x 3, tight */);
 
 /* cv2.resize(src, (new_w, new_h), INTER_LINEAR) of one uint8 HWC 3-channel host image
  * (the resize step alone; dst is new_h x new_w x 3, channel order kept). */

@@ -6,7 +6,8 @@ maps them to ops).
   rocprofv3 --kernel-trace -f csv -d gpurun_out/ft -o run -- python3 tools/fwd_trace.py
   python tools/trace_ops.py gpurun_out/ft
 
-Env: YH_VARIANT (n), YH_SIZE (640), YH_BATCH (32), YH_DTYPE (bf16), YH_FWD (5 forwards).
+Env: YH_VARIANT (n), YH_SIZE (640), YH_HEIGHT / YH_WIDTH (YH_SIZE: a rectangular input),
+YH_BATCH (32), YH_DTYPE (bf16), YH_FWD (5 forwards).
 Writes the op list to $YH_OPS_OUT (default gpurun_out/ft_ops.json).
 """
 import json
@@ -28,6 +29,7 @@ DT = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 def main():
     v = os.environ.get("YH_VARIANT", "n")
     size = int(os.environ.get("YH_SIZE", "640"))
+    H, W = int(os.environ.get("YH_HEIGHT", size)), int(os.environ.get("YH_WIDTH", size))
     B = int(os.environ.get("YH_BATCH", "32"))
     dt = DT[os.environ.get("YH_DTYPE", "bf16")]
     nf = int(os.environ.get("YH_FWD", "5"))
@@ -39,7 +41,7 @@ def main():
     dev = torch.device("cuda", 0)
     eng = Engine(*model._yh_arch, dev, dt)
     eng.load_module(model)
-    x = synth.synth_scenes(B, size, size, seed=100).to(dev, dt)
+    x = synth.synth_scenes(B, H, W, seed=100).to(dev, dt)
     y = eng.forward(x)          # autotune + graph capture
     for _ in range(3):
         eng.forward(x, out=y)
@@ -53,7 +55,7 @@ def main():
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as f:
         json.dump(dict(forwards=nf, ops=[dict(label=o["label"], cls=o["cls"], bytes=o["bytes"], flops=o["flops"],
-                                              kernel=o["kernel"]) for o in (u["ops"][0] for u in eng.units(B, size, size))]), f)
+                                              kernel=o["kernel"]) for o in (u["ops"][0] for u in eng.units(B, H, W))]), f)
     print("fwd_trace done", flush=True)
 
 

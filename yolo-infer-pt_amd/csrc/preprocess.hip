@@ -1,5 +1,6 @@
 // Eval-mode image preprocessing of the reference's data loader, on the device
-// (yh_letterbox) and on the host (yh_letterbox_host, same per-pixel function):
+// (yh_letterbox_frames, yh_letterbox) and on the host (yh_letterbox_frames_host,
+// yh_letterbox_host: same per-pixel functions):
 //
 //   utils/dataset.py:95-103  load_image: r = input_size / max(h, w); if r != 1
 //                            cv2.resize(image, (int(w r), int(h r)), INTER_LINEAR)
@@ -25,20 +26,36 @@
 //   Which vector width the cv2 build used is an assumption (parity unpinned vs cv2).
 //   Exactly 2x downscales on both axes take INTER_AREA's fast path
 //   ((S00 + S01 + S10 + S11 + 2) >> 2), as cv2.resize does.
+//
+// Beyond the reference (include/yolo_hip.h states the semantics): the canvas may be a
+// rectangle (r = min(canvas_h / h, canvas_w / w), the same division for a square one), and
+// a frame may be NV12. An NV12 source pixel is converted to B, G, R by lb_tap (integer,
+// shift 20, nearest chroma; OpenCV's published COLOR_YUV2BGR_NV12 coefficients, parity
+// unpinned against cv2 like the resize) wherever the resize reads a source pixel, so the
+// canvas is the BGR letterbox of the converted frame without that frame ever existing.
 #include <cmath>
+#include <string>
 #include <thread>
 #include <vector>
 
 #include "common.h"
+#include "host_util.h"
 #include "yolo_hip.h"
 
 namespace yh {
 
+enum LbMode { LB_COPY = 0, LB_AREA2 = 1, LB_LINEAR = 2 };
+
 struct LbImage {
-    const unsigned char* src;   // HWC BGR uint8, row stride `stride` bytes
-    int h, w, stride;
+    const unsigned char* p0;    // BGR: HWC uint8; NV12: the Y plane
+    const unsigned char* p1;    // NV12: interleaved U, V rows (h / 2 rows of w bytes)
+    double sx, sy;              // LB_LINEAR: source step per resized pixel (lb_finish)
+    int h, w, stride0, stride1; // source size, row strides of the planes in bytes
     int nh, nw;                 // resized size
     int top, left;              // border
+    int tail;                   // lb_vtail(3 nw)
+    int format, matrix;         // YH_PIX_*, YH_YUV_*
+    int mode;                   // LbMode
 };
 
 struct LbAxis {
@@ -73,164 +90,318 @@ __host__ __device__ inline int lb_vtail(int width) {
     return x;
 }
 
-// Pixel (y, x) of the letterboxed canvas, 3 channels in RGB order.
-__host__ __device__ inline void lb_pixel(const LbImage& im, int y, int x, unsigned char rgb[3]) {
+__host__ __device__ inline int lb_sat(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// B, G, R of source pixel (y, x): the bytes of a BGR frame, one conversion of an NV12 frame
+// (limited range, shift 20, the chroma pair of (y >> 1, x >> 1); include/yolo_hip.h)
+__host__ __device__ inline void lb_tap(const LbImage& im, int y, int x, int bgr[3]) {
+    if (im.format == YH_PIX_NV12) {
+        const int Y = im.p0[(size_t)y * im.stride0 + x];
+        const unsigned char* c = im.p1 + (size_t)(y >> 1) * im.stride1 + ((x >> 1) << 1);
+        const int u = c[0] - 128, v = c[1] - 128;
+        const bool m709 = im.matrix == YH_YUV_BT709;
+        const int cub = m709 ? 2214593 : 2116026, cug = m709 ? -223347 : -409993;
+        const int cvg = m709 ? -558891 : -852492, cvr = m709 ? 1880097 : 1673527;
+        const int yy = (Y > 16 ? Y - 16 : 0) * 1220542 + (1 << 19);
+        bgr[0] = lb_sat((yy + cub * u) >> 20);
+        bgr[1] = lb_sat((yy + cvg * v + cug * u) >> 20);
+        bgr[2] = lb_sat((yy + cvr * v) >> 20);
+        return;
+    }
+    const unsigned char* p = im.p0 + (size_t)y * im.stride0 + (size_t)x * 3;
+    bgr[0] = p[0]; bgr[1] = p[1]; bgr[2] = p[2];
+}
+
+// what the pixels of one canvas row share: the resized row and its vertical taps
+struct LbRow {
+    int dy;        // row of the resized image, -1 for a border row
+    LbAxis ay;     // LB_LINEAR only
+};
+
+__host__ __device__ inline LbRow lb_row(const LbImage& im, int y) {
+    LbRow r;
+    r.dy = y - im.top;
+    r.ay = LbAxis{0, 0, 0, 0};
+    if (r.dy < 0 || r.dy >= im.nh) r.dy = -1;
+    else if (im.mode == LB_LINEAR) r.ay = lb_axis(r.dy, im.h, im.sy, false);
+    return r;
+}
+
+// Pixel x of canvas row `row`, 3 channels in RGB order.
+__host__ __device__ inline void lb_pixel_row(const LbImage& im, const LbRow& row, int x, unsigned char rgb[3]) {
     rgb[0] = rgb[1] = rgb[2] = 0;
-    const int dy = y - im.top, dx = x - im.left;
-    if (dy < 0 || dy >= im.nh || dx < 0 || dx >= im.nw) return;
-    const unsigned char* S = im.src;
-    if (im.nh == im.h && im.nw == im.w) {   // r == 1: no resize (load_image skips it)
-        const unsigned char* p = S + (size_t)dy * im.stride + (size_t)dx * 3;
-        rgb[0] = p[2]; rgb[1] = p[1]; rgb[2] = p[0];
+    const int dy = row.dy, dx = x - im.left;
+    if (dy < 0 || dx < 0 || dx >= im.nw) return;
+    if (im.mode == LB_COPY) {   // r == 1: no resize (load_image skips it)
+        int t[3];
+        lb_tap(im, dy, dx, t);
+        rgb[0] = (unsigned char)t[2]; rgb[1] = (unsigned char)t[1]; rgb[2] = (unsigned char)t[0];
         return;
     }
-    if (im.h == 2 * im.nh && im.w == 2 * im.nw) {   // INTER_AREA fast path
-        const unsigned char* p0 = S + (size_t)(2 * dy) * im.stride + (size_t)(2 * dx) * 3;
-        const unsigned char* p1 = p0 + im.stride;
-        for (int c = 0; c < 3; ++c) rgb[2 - c] = (unsigned char)((p0[c] + p0[c + 3] + p1[c] + p1[c + 3] + 2) >> 2);
+    if (im.mode == LB_AREA2) {   // INTER_AREA fast path
+        int t00[3], t01[3], t10[3], t11[3];
+        lb_tap(im, 2 * dy, 2 * dx, t00);
+        lb_tap(im, 2 * dy, 2 * dx + 1, t01);
+        lb_tap(im, 2 * dy + 1, 2 * dx, t10);
+        lb_tap(im, 2 * dy + 1, 2 * dx + 1, t11);
+        for (int c = 0; c < 3; ++c) rgb[2 - c] = (unsigned char)((t00[c] + t01[c] + t10[c] + t11[c] + 2) >> 2);
         return;
     }
-    const double sx = 1.0 / ((double)im.nw / (double)im.w);
-    const double sy = 1.0 / ((double)im.nh / (double)im.h);
-    const LbAxis ax = lb_axis(dx, im.w, sx, true);
-    const LbAxis ay = lb_axis(dy, im.h, sy, false);
-    const unsigned char* r0 = S + (size_t)ay.s0 * im.stride;
-    const unsigned char* r1 = S + (size_t)ay.s1 * im.stride;
-    const int tail = lb_vtail(3 * im.nw);
+    const LbAxis ax = lb_axis(dx, im.w, im.sx, true);
+    const LbAxis& ay = row.ay;
+    int t00[3], t01[3], t10[3], t11[3];
+    lb_tap(im, ay.s0, ax.s0, t00);
+    lb_tap(im, ay.s0, ax.s1, t01);
+    lb_tap(im, ay.s1, ax.s0, t10);
+    lb_tap(im, ay.s1, ax.s1, t11);
     for (int c = 0; c < 3; ++c) {
-        const int h0 = r0[ax.s0 * 3 + c] * ax.a0 + r0[ax.s1 * 3 + c] * ax.a1;
-        const int h1 = r1[ax.s0 * 3 + c] * ax.a0 + r1[ax.s1 * 3 + c] * ax.a1;
-        int v = dx * 3 + c < tail ? (lb_mulhi(h0 >> 4, ay.a0) + lb_mulhi(h1 >> 4, ay.a1) + 2) >> 2
-                                  : (h0 * ay.a0 + h1 * ay.a1 + (1 << 21)) >> 22;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        rgb[2 - c] = (unsigned char)v;
+        const int h0 = t00[c] * ax.a0 + t01[c] * ax.a1;
+        const int h1 = t10[c] * ax.a0 + t11[c] * ax.a1;
+        const int v = dx * 3 + c < im.tail ? (lb_mulhi(h0 >> 4, ay.a0) + lb_mulhi(h1 >> 4, ay.a1) + 2) >> 2
+                                           : (h0 * ay.a0 + h1 * ay.a1 + (1 << 21)) >> 22;
+        rgb[2 - c] = (unsigned char)lb_sat(v);
     }
 }
 
-// resized pixel (dy, dx) of an image, 3 channels in the source's (BGR) order
-__host__ __device__ inline void lb_resized(const LbImage& im, int dy, int dx, unsigned char bgr[3]) {
-    LbImage t = im;
-    t.top = 0; t.left = 0;
-    unsigned char rgb[3];
-    lb_pixel(t, dy, dx, rgb);
-    bgr[0] = rgb[2]; bgr[1] = rgb[1]; bgr[2] = rgb[0];
+// the resize path and its constants from h, w, nh, nw
+inline void lb_finish(LbImage& im) {
+    im.mode = im.nh == im.h && im.nw == im.w ? LB_COPY : (im.h == 2 * im.nh && im.w == 2 * im.nw ? LB_AREA2 : LB_LINEAR);
+    im.sx = 1.0 / ((double)im.nw / (double)im.w);
+    im.sy = 1.0 / ((double)im.nh / (double)im.h);
+    im.tail = lb_vtail(3 * im.nw);
 }
 
-// geometry of one image (dataset.py:95-103, 292-313), in the reference's double arithmetic
-inline int lb_geometry(int h, int w, int size, LbImage& im) {
-    if (h <= 0 || w <= 0 || size <= 0) return YH_EINVAL;
-    const double r = (double)size / (double)(h > w ? h : w);
+// geometry of one image on a canvas_h x canvas_w canvas (dataset.py:95-103, 292-313 for a
+// square one), in the reference's double arithmetic; NULL or the reason it is rejected
+inline const char* lb_geometry(int h, int w, int ch, int cw, LbImage& im) {
+    if (h <= 0 || w <= 0 || ch <= 0 || cw <= 0) return "letterbox: image and canvas sides must be positive";
+    const double rh = (double)ch / (double)h, rw = (double)cw / (double)w;
+    const double r = rh < rw ? rh : rw;
     int nh = h, nw = w;
     if (r != 1.0) { nw = (int)(w * r); nh = (int)(h * r); }
-    if (nh < 1 || nw < 1 || nh > size || nw > size) return YH_EINVAL;
-    const double dw = (size - nw) / 2.0, dh = (size - nh) / 2.0;
+    if (nh < 1 || nw < 1) return "letterbox: a resized side is below 1 pixel";
+    if (nh > ch || nw > cw) return "letterbox: the resized image exceeds the canvas";
+    const double dw = (cw - nw) / 2.0, dh = (ch - nh) / 2.0;
     im.h = h; im.w = w; im.nh = nh; im.nw = nw;
     im.top = (int)std::nearbyint(dh - 0.1);
     im.left = (int)std::nearbyint(dw - 0.1);
-    return YH_OK;
+    lb_finish(im);
+    return nullptr;
 }
 
-constexpr int LB_MAX = 32;   // images per launch (kernarg-resident descriptors)
+// descriptor of one frame on a canvas; throws Fail(YH_EINVAL) with the reason
+inline LbImage lb_describe(const yh_frame& f, int ch, int cw) {
+    LbImage im{};
+    require(f.format == YH_PIX_BGR || f.format == YH_PIX_NV12, "letterbox: unknown pixel format " + std::to_string(f.format));
+    const bool nv12 = f.format == YH_PIX_NV12;
+    if (nv12) {
+        require(f.matrix == YH_YUV_BT601 || f.matrix == YH_YUV_BT709, "letterbox: unknown YUV matrix " + std::to_string(f.matrix));
+        require(f.height > 0 && f.width > 0 && f.height % 2 == 0 && f.width % 2 == 0,
+                "letterbox: an NV12 frame needs even, positive height and width");
+    }
+    require(f.plane0 != nullptr, "letterbox: plane0 is NULL");
+    require(!nv12 || f.plane1 != nullptr, "letterbox: plane1 of an NV12 frame is NULL");
+    const char* why = lb_geometry(f.height, f.width, ch, cw, im);
+    require(why == nullptr, why ? why : "");
+    const int row0 = nv12 ? f.width : 3 * f.width;
+    im.stride0 = f.stride0 ? f.stride0 : row0;
+    im.stride1 = nv12 ? (f.stride1 ? f.stride1 : f.width) : 0;
+    require(im.stride0 >= row0 && (!nv12 || im.stride1 >= f.width), "letterbox: a stride is smaller than the row");
+    im.p0 = static_cast<const unsigned char*>(f.plane0);
+    im.p1 = nv12 ? static_cast<const unsigned char*>(f.plane1) : nullptr;
+    im.format = f.format;
+    im.matrix = nv12 ? f.matrix : 0;
+    return im;
+}
+
+constexpr int LB_MAX = 32;   // frames per launch (kernarg-resident descriptors)
 struct LbBatch {
     LbImage im[LB_MAX];
-    unsigned char* dst;      // (n, 3, size, size) uint8
-    int size, n;
+    unsigned char* dst;      // (n, 3, ch, cw) uint8
+    int ch, cw, n;
+    int dwords;              // every 4-pixel group of dst is an aligned dword (cw % 4 == 0, dst % 4 == 0)
 };
 
-__global__ __launch_bounds__(256) void letterbox_u8(const LbBatch b) {
+// One thread: 4 consecutive canvas pixels of one row, all three planes; consecutive lanes write
+// consecutive dwords of a row. The row's vertical taps are computed once (lb_row).
+__global__ __launch_bounds__(256) void letterbox_frames_u8(const LbBatch b) {
     const int i = blockIdx.y;
-    const int px = blockIdx.x * 256 + threadIdx.x;
-    const int plane = b.size * b.size;
-    if (px >= plane) return;
-    unsigned char rgb[3];
-    lb_pixel(b.im[i], px / b.size, px - (px / b.size) * b.size, rgb);
-    unsigned char* o = b.dst + (size_t)i * 3 * plane + px;
-    o[0] = rgb[0];
-    o[plane] = rgb[1];
-    o[2 * (size_t)plane] = rgb[2];
+    const int gw = (b.cw + 3) >> 2;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= gw * b.ch) return;
+    const int y = q / gw, x0 = (q - y * gw) * 4;
+    const LbImage& im = b.im[i];
+    const LbRow row = lb_row(im, y);
+    unsigned out[3] = {0u, 0u, 0u};
+    if (row.dy >= 0 && x0 + 3 >= im.left && x0 < im.left + im.nw) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned char rgb[3];
+            lb_pixel_row(im, row, x0 + k, rgb);
+            out[0] |= (unsigned)rgb[0] << (8 * k);
+            out[1] |= (unsigned)rgb[1] << (8 * k);
+            out[2] |= (unsigned)rgb[2] << (8 * k);
+        }
+    }
+    const size_t plane = (size_t)b.ch * b.cw;
+    unsigned char* o = b.dst + (size_t)i * 3 * plane + (size_t)y * b.cw + x0;
+    if (b.dwords) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<unsigned*>(o + c * plane) = out[c];
+    } else {   // a canvas width or base that is no multiple of 4 (yh_letterbox accepts any size)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            for (int k = 0; k < 4 && x0 + k < b.cw; ++k) o[c * plane + k] = (unsigned char)(out[c] >> (8 * k));
+    }
+}
+
+// validates every frame, then one launch per LB_MAX frames; frames[k] may come from `at(k)`
+template <typename At>
+void lb_launch(At&& at, int batch, int ch, int cw, void* dst, void* stream) {
+    require(batch >= 0 && ch > 0 && cw > 0, "letterbox: negative batch or empty canvas");
+    require(batch == 0 || dst != nullptr, "letterbox: dst is NULL");
+    for (int k = 0; k < batch; ++k) lb_describe(at(k), ch, cw);
+    const size_t plane = (size_t)ch * cw;
+    for (int b0 = 0; b0 < batch; b0 += LB_MAX) {
+        LbBatch lb{};
+        lb.n = batch - b0 < LB_MAX ? batch - b0 : LB_MAX;
+        lb.ch = ch; lb.cw = cw;
+        lb.dst = static_cast<unsigned char*>(dst) + (size_t)b0 * 3 * plane;
+        lb.dwords = cw % 4 == 0 && reinterpret_cast<uintptr_t>(lb.dst) % 4 == 0;
+        for (int k = 0; k < lb.n; ++k) lb.im[k] = lb_describe(at(b0 + k), ch, cw);
+        const long long groups = (long long)((cw + 3) / 4) * ch;
+        require(groups < (1ll << 31), "letterbox: canvas too large");
+        const dim3 g((unsigned)((groups + 255) / 256), (unsigned)lb.n);
+        hipLaunchKernelGGL(letterbox_frames_u8, g, dim3(256), 0, (hipStream_t)stream, lb);
+        HIPCHECK(hipGetLastError());
+    }
+}
+
+void lb_host(const yh_frame& f, int ch, int cw, void* dst, int threads) {
+    require(ch > 0 && cw > 0, "letterbox: empty canvas");
+    require(dst != nullptr, "letterbox: dst is NULL");
+    const LbImage im = lb_describe(f, ch, cw);
+    unsigned char* o = static_cast<unsigned char*>(dst);
+    const size_t plane = (size_t)ch * cw;
+    auto rows = [&](int y0, int y1) {
+        for (int y = y0; y < y1; ++y) {
+            const LbRow row = lb_row(im, y);
+            for (int x = 0; x < cw; ++x) {
+                unsigned char rgb[3];
+                lb_pixel_row(im, row, x, rgb);
+                const size_t q = (size_t)y * cw + x;
+                o[q] = rgb[0]; o[plane + q] = rgb[1]; o[2 * plane + q] = rgb[2];
+            }
+        }
+    };
+    int nt = threads > 0 ? threads : 1;
+    nt = nt < ch ? nt : ch;
+    if (nt <= 1) {
+        rows(0, ch);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (int t = 0; t < nt; ++t) pool.emplace_back(rows, (int)((long long)ch * t / nt), (int)((long long)ch * (t + 1) / nt));
+    for (auto& th : pool) th.join();
+}
+
+inline yh_frame lb_bgr_frame(const void* src, int height, int width, int stride) {
+    yh_frame f{};
+    f.plane0 = src;
+    f.height = height; f.width = width;
+    f.stride0 = stride;
+    f.format = YH_PIX_BGR;
+    return f;
 }
 
 }  // namespace yh
 
 using namespace yh;
 
+extern "C" int yh_letterbox_geometry2(int height, int width, int canvas_h, int canvas_w, int* new_h, int* new_w,
+                                      int* top, int* left) {
+    return guarded([&] {
+        LbImage im{};
+        const char* why = lb_geometry(height, width, canvas_h, canvas_w, im);
+        require(why == nullptr, why ? why : "");
+        if (new_h) *new_h = im.nh;
+        if (new_w) *new_w = im.nw;
+        if (top) *top = im.top;
+        if (left) *left = im.left;
+    });
+}
+
 extern "C" int yh_letterbox_geometry(int height, int width, int size, int* new_h, int* new_w, int* top,
                                      int* left) {
-    LbImage im{};
-    const int rc = lb_geometry(height, width, size, im);
-    if (rc) return rc;
-    if (new_h) *new_h = im.nh;
-    if (new_w) *new_w = im.nw;
-    if (top) *top = im.top;
-    if (left) *left = im.left;
-    return YH_OK;
+    return yh_letterbox_geometry2(height, width, size, size, new_h, new_w, top, left);
+}
+
+extern "C" int yh_letterbox_frames(const yh_frame* frames, int batch, int canvas_h, int canvas_w, void* dst,
+                                   void* stream) {
+    return guarded([&] {
+        require(batch <= 0 || frames != nullptr, "letterbox_frames: frames is NULL");
+        require(canvas_w % 4 == 0, "letterbox_frames: canvas_w must be a multiple of 4");
+        lb_launch([&](int k) -> const yh_frame& { return frames[k]; }, batch, canvas_h, canvas_w, dst, stream);
+    });
+}
+
+extern "C" int yh_letterbox_frames_host(const yh_frame* frame, int canvas_h, int canvas_w, void* dst, int threads) {
+    return guarded([&] {
+        require(frame != nullptr, "letterbox_frames_host: frame is NULL");
+        lb_host(*frame, canvas_h, canvas_w, dst, threads);
+    });
+}
+
+extern "C" int yh_nv12_to_bgr_host(const yh_frame* frame, void* dst_bgr) {
+    return guarded([&] {
+        require(frame != nullptr && dst_bgr != nullptr, "nv12_to_bgr_host: NULL argument");
+        require(frame->format == YH_PIX_NV12, "nv12_to_bgr_host: the frame is not NV12");
+        // the frame's own size as the canvas: validates planes, strides and the matrix
+        const LbImage im = lb_describe(*frame, frame->height, frame->width);
+        unsigned char* o = static_cast<unsigned char*>(dst_bgr);
+        for (int y = 0; y < im.h; ++y)
+            for (int x = 0; x < im.w; ++x) {
+                int t[3];
+                lb_tap(im, y, x, t);
+                unsigned char* p = o + ((size_t)y * im.w + x) * 3;
+                p[0] = (unsigned char)t[0]; p[1] = (unsigned char)t[1]; p[2] = (unsigned char)t[2];
+            }
+    });
 }
 
 extern "C" int yh_letterbox(const void* const* srcs, const int* heights, const int* widths, const int* strides,
                             int batch, int size, void* dst, void* stream) {
-    if (batch < 0 || size <= 0 || (batch > 0 && (!srcs || !heights || !widths || !dst))) return YH_EINVAL;
-    for (int b0 = 0; b0 < batch; b0 += LB_MAX) {
-        LbBatch lb{};
-        lb.n = batch - b0 < LB_MAX ? batch - b0 : LB_MAX;
-        lb.size = size;
-        lb.dst = static_cast<unsigned char*>(dst) + (size_t)b0 * 3 * size * size;
-        for (int k = 0; k < lb.n; ++k) {
-            LbImage& im = lb.im[k];
-            const int rc = lb_geometry(heights[b0 + k], widths[b0 + k], size, im);
-            if (rc) return rc;
-            im.src = static_cast<const unsigned char*>(srcs[b0 + k]);
-            im.stride = strides ? strides[b0 + k] : 3 * widths[b0 + k];
-            if (!im.src || im.stride < 3 * im.w) return YH_EINVAL;
-        }
-        const dim3 g((unsigned)((size * size + 255) / 256), (unsigned)lb.n);
-        hipLaunchKernelGGL(letterbox_u8, g, dim3(256), 0, (hipStream_t)stream, lb);
-        if (hipGetLastError() != hipSuccess) return YH_EHIP;
-    }
-    return YH_OK;
+    return guarded([&] {
+        require(batch <= 0 || (srcs && heights && widths), "letterbox: NULL argument");
+        lb_launch([&](int k) { return lb_bgr_frame(srcs[k], heights[k], widths[k], strides ? strides[k] : 0); },
+                  batch, size, size, dst, stream);
+    });
 }
 
 extern "C" int yh_letterbox_host(const void* src, int height, int width, int stride, int size, void* dst,
                                  int threads) {
-    LbImage im{};
-    const int rc = lb_geometry(height, width, size, im);
-    if (rc) return rc;
-    if (!src || !dst) return YH_EINVAL;
-    im.src = static_cast<const unsigned char*>(src);
-    im.stride = stride > 0 ? stride : 3 * width;
-    if (im.stride < 3 * width) return YH_EINVAL;
-    unsigned char* o = static_cast<unsigned char*>(dst);
-    const size_t plane = (size_t)size * size;
-    auto rows = [&](int y0, int y1) {
-        for (int y = y0; y < y1; ++y)
-            for (int x = 0; x < size; ++x) {
-                unsigned char rgb[3];
-                lb_pixel(im, y, x, rgb);
-                const size_t q = (size_t)y * size + x;
-                o[q] = rgb[0]; o[plane + q] = rgb[1]; o[2 * plane + q] = rgb[2];
-            }
-    };
-    int nt = threads > 0 ? threads : 1;
-    nt = nt < size ? nt : size;
-    if (nt <= 1) {
-        rows(0, size);
-        return YH_OK;
-    }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t) pool.emplace_back(rows, size * t / nt, size * (t + 1) / nt);
-    for (auto& th : pool) th.join();
-    return YH_OK;
+    return guarded([&] { lb_host(lb_bgr_frame(src, height, width, stride > 0 ? stride : 0), size, size, dst, threads); });
 }
 
 extern "C" int yh_resize_linear_host(const void* src, int height, int width, int stride, int new_h, int new_w,
                                      void* dst) {
     if (!src || !dst || height <= 0 || width <= 0 || new_h <= 0 || new_w <= 0) return YH_EINVAL;
     LbImage im{};
-    im.src = static_cast<const unsigned char*>(src);
+    im.p0 = static_cast<const unsigned char*>(src);
     im.h = height; im.w = width; im.nh = new_h; im.nw = new_w;
-    im.stride = stride > 0 ? stride : 3 * width;
-    if (im.stride < 3 * width) return YH_EINVAL;
+    im.stride0 = stride > 0 ? stride : 3 * width;
+    if (im.stride0 < 3 * width) return YH_EINVAL;
+    im.format = YH_PIX_BGR;
+    lb_finish(im);
     unsigned char* o = static_cast<unsigned char*>(dst);
-    for (int y = 0; y < new_h; ++y)
-        for (int x = 0; x < new_w; ++x) lb_resized(im, y, x, o + ((size_t)y * new_w + x) * 3);
+    for (int y = 0; y < new_h; ++y) {
+        const LbRow row = lb_row(im, y);
+        for (int x = 0; x < new_w; ++x) {
+            unsigned char rgb[3];
+            lb_pixel_row(im, row, x, rgb);
+            unsigned char* p = o + ((size_t)y * new_w + x) * 3;
+            p[0] = rgb[2]; p[1] = rgb[1]; p[2] = rgb[0];
+        }
+    }
     return YH_OK;
 }

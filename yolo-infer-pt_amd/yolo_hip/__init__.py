@@ -3,7 +3,9 @@
 `Engine` wraps one yh_handle (include/yolo_hip.h); `nms` is the on-device
 non_max_suppression; `Evaluator` (yolo_hip.evaluate) is the batched mAP
 evaluation over those detections; `Detector` (yolo_hip.detect) returns detections in
-source-image pixels, optionally from tiled inference (`tiles`, `tile_transform`, `merge`);
+source-image pixels, optionally from tiled inference (`tiles`, `tile_transform`, `merge`),
+from BGR or `NV12` video frames on a square or rectangular canvas (`letterbox_frames`,
+`rect_canvas`; yolo_hip.preprocess);
 `Tracker` (yolo_hip.track) gives the detections of video streams identities across frames
 (`track`, `track_state`, `Tracks`). The drop-in module API lives in `nets.nn` / `utils.util`.
 """
@@ -24,6 +26,9 @@ def __getattr__(name):
     if name in ("tiles", "tile_transform"):
         from . import detect
         return getattr(detect, name)
+    if name in ("NV12", "letterbox_frames", "rect_canvas"):
+        from . import preprocess
+        return getattr(preprocess, name)
     if name in ("Tracker", "Tracks", "track", "track_state"):
         # the function shares its name with its module, and importing the module binds the name
         # here: the module is callable as the function (yolo_hip/track.py, at its end)

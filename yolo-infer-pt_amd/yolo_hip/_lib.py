@@ -17,6 +17,8 @@ if os.environ.get("YH_LIB"):
 
 YH_F32, YH_F16, YH_BF16 = 0, 1, 2
 ABI_VERSION = 7
+YH_PIX_BGR, YH_PIX_NV12 = 0, 1
+YH_YUV_BT601, YH_YUV_BT709 = 0, 1
 MERGE_MAX_CAND = 8192   # YH_MERGE_MAX_CAND: candidates (max_tiles * max_det) per image of yh_merge
 
 
@@ -26,6 +28,19 @@ class YhVariant(ctypes.Structure):
         ("depth", c_int * 6),
         ("csp", c_int * 2),
         ("num_classes", c_int),
+    ]
+
+
+class YhFrame(ctypes.Structure):
+    _fields_ = [
+        ("plane0", c_void_p),
+        ("plane1", c_void_p),
+        ("height", c_int),
+        ("width", c_int),
+        ("stride0", c_int),
+        ("stride1", c_int),
+        ("format", c_int),
+        ("matrix", c_int),
     ]
 
 
@@ -77,6 +92,10 @@ _PROTOS = {
     "yh_letterbox_geometry": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_letterbox": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "yh_letterbox_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),
+    "yh_letterbox_geometry2": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "yh_letterbox_frames": (c_int, [POINTER(YhFrame), c_int, c_int, c_int, c_void_p, c_void_p]),
+    "yh_letterbox_frames_host": (c_int, [POINTER(YhFrame), c_int, c_int, c_void_p, c_int]),
+    "yh_nv12_to_bgr_host": (c_int, [POINTER(YhFrame), c_void_p]),
     "yh_resize_linear_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "yh_debug_op_desc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
     "yh_debug_run_ops": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
@@ -118,5 +137,5 @@ def check(rc, what=""):
         raise RuntimeError(f"yolo_hip{': ' + what if what else ''}: {msg} (status {rc})")
 
 
-__all__ = ["lib", "check", "YhVariant", "YH_F32", "YH_F16", "YH_BF16", "LIB_PATH",
+__all__ = ["lib", "check", "YhVariant", "YhFrame", "YH_F32", "YH_F16", "YH_BF16", "LIB_PATH",
            "byref", "c_void_p", "c_int", "c_char_p", "c_double", "c_size_t"]

@@ -59,7 +59,8 @@ def tiles(height, width, tile, overlap=0.2, full_image=False):
 
 
 def tile_transform(crop, size):
-    """(sx, sy, px, py, ox, oy) as np.float32 for one crop (x0, y0, w, h) letterboxed to size x size:
+    """(sx, sy, px, py, ox, oy) as np.float32 for one crop (x0, y0, w, h) letterboxed to size x size
+    (size an int) or to an H x W canvas (size = (H, W)):
     a canvas coordinate x maps to (x - px) * sx + ox in the source image (y alike). The scale is
     the fp32 quotient w / new_w of preprocess.geometry, exactly 1.0 when the crop is not resized."""
     from .preprocess import geometry
@@ -165,6 +166,12 @@ class Detector:
     to min(max_det, MERGE_MAX_CAND // most tiles of one image in the call). max_det rows per image
     come back.
 
+    canvas=(H, W) (both multiples of 32, e.g. preprocess.rect_canvas(1080, 1920) = (384, 640))
+    replaces the square canvas by a rectangle: the pipeline is built at that shape and every tile
+    is letterboxed to it (preprocess.letterbox_frames). canvas=None is (size, size). predict()
+    also takes preprocess.NV12 frames (image height and width are the planes'); they cannot be
+    tiled (crops at odd offsets are out of scope): with `tile` set they raise ValueError.
+
     predict() never reads a device value on the host: sizes, tile lists and transforms come from
     the images' shapes. Stream safety, as yolo_hip.evaluate.Evaluator documents its own: the
     tile batches are forwarded on the pipeline's streams; predict() makes the caller's stream
@@ -175,7 +182,7 @@ class Detector:
     """
 
     def __init__(self, engines, size=640, batch=32, tile=None, overlap=0.2, full_image=False, conf=0.001, iou=0.65,
-                 merge_iou=None, max_det=300, tile_max_det=None):
+                 merge_iou=None, max_det=300, tile_max_det=None, canvas=None):
         from .pipeline import DetectPipeline
         self.size, self.batch = int(size), int(batch)
         self.tile = None if tile is None else int(tile)
@@ -186,7 +193,15 @@ class Detector:
         self.tile_max_det = None if tile_max_det is None else int(tile_max_det)
         if self.batch < 1 or self.max_det < 1:
             raise ValueError("yolo_hip.Detector: batch and max_det must be positive")
-        self.pipe = DetectPipeline(engines, self.batch, self.size, self.size)
+        if canvas is None:
+            self.canvas = None
+            ch = cw = self.size
+        else:
+            ch, cw = (int(v) for v in canvas)
+            if ch < 32 or cw < 32 or ch % 32 or cw % 32:
+                raise ValueError("yolo_hip.Detector: canvas sides must be positive multiples of 32")
+            self.canvas = (ch, cw)
+        self.pipe = DetectPipeline(engines, self.batch, ch, cw)
         self.device = self.pipe.eng.device
 
     def plan(self, shapes):
@@ -204,29 +219,37 @@ class Detector:
         return crops, tmd, max_tiles
 
     def predict(self, images):
+        from .preprocess import NV12, letterbox, letterbox_frames
         dev = self.device
-        srcs = []
+        srcs, shapes = [], []
         for im in images:
+            if isinstance(im, NV12):
+                if self.tile is not None:
+                    raise ValueError("yolo_hip.Detector: NV12 frames cannot be tiled (tile must be None)")
+                srcs.append(im.to(dev, non_blocking=True))
+                shapes.append((im.height, im.width))
+                continue
             t = torch.as_tensor(im)
             if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
-                raise ValueError("yolo_hip.Detector: images must be (h, w, 3) uint8 BGR")
+                raise ValueError("yolo_hip.Detector: images must be (h, w, 3) uint8 BGR or preprocess.NV12")
             if t.stride(2) != 1 or t.stride(1) != 3:
                 t = t.contiguous()
             srcs.append(t.to(dev, non_blocking=True))
+            shapes.append((t.shape[0], t.shape[1]))
         n = len(srcs)
-        crops, tmd, max_tiles = self.plan([(t.shape[0], t.shape[1]) for t in srcs])
+        crops, tmd, max_tiles = self.plan(shapes)
         if n == 0:
             return Detections(torch.zeros((0, self.max_det, 6), dtype=torch.float32, device=dev),
                               torch.zeros((0,), dtype=torch.int32, device=dev))
-        from .preprocess import letterbox
+        canvas = ch, cw = self.canvas or (self.size, self.size)
         # host-side geometry of every tile, uploaded as one pinned block (below):
         # [xf (padded tile axis) x 6 | wh n x 2 | offsets n + 1 (i32)]
         views, xf, offsets = [], [], [0]
         for t, cs in zip(srcs, crops):
             for c in cs:
                 x0, y0, w, h = c
-                views.append(t[y0:y0 + h, x0:x0 + w])
-                xf.append(tile_transform(c, self.size))
+                views.append(t if isinstance(t, NV12) else t[y0:y0 + h, x0:x0 + w])   # an NV12 frame is one whole tile
+                xf.append(tile_transform(c, canvas))
             offsets.append(len(views))
         T = len(views)
         B = self.batch
@@ -234,8 +257,7 @@ class Detector:
         TP = nb * B                              # the tile axis, padded to whole batches
         stage = torch.zeros(6 * TP + 2 * n + n + 1, dtype=torch.float32, pin_memory=True)
         stage[:6 * T].view(T, 6).copy_(torch.from_numpy(np.asarray(xf, dtype=np.float32).reshape(T, 6)))
-        stage[6 * TP:6 * TP + 2 * n].view(n, 2).copy_(torch.tensor([[t.shape[1], t.shape[0]] for t in srcs],
-                                                                    dtype=torch.float32))
+        stage[6 * TP:6 * TP + 2 * n].view(n, 2).copy_(torch.tensor([[w, h] for h, w in shapes], dtype=torch.float32))
         stage[6 * TP + 2 * n:].view(torch.int32).copy_(torch.tensor(offsets, dtype=torch.int32))
         on = stage.to(dev, non_blocking=True)
         tile_xf = on[:6 * TP].view(TP, 6)
@@ -254,8 +276,11 @@ class Detector:
             done = []
             for b in range(nb):
                 part = views[b * B:(b + 1) * B]
-                x = torch.empty((B, 3, self.size, self.size), dtype=torch.uint8, device=dev)
-                letterbox(part, self.size, device=dev, out=x[:len(part)])
+                x = torch.empty((B, 3, ch, cw), dtype=torch.uint8, device=dev)
+                if self.canvas is None and not any(isinstance(v, NV12) for v in part):
+                    letterbox(part, self.size, device=dev, out=x[:len(part)])
+                else:
+                    letterbox_frames(part, canvas, device=dev, out=x[:len(part)])
                 if len(part) < B:
                     x[len(part):].zero_()
                 done.append(pipe.submit(x, out=(tdets[b * B:(b + 1) * B], tcounts[b * B:(b + 1) * B]))[3])
