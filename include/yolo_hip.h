@@ -29,6 +29,10 @@
  *   yh_letterbox_frames no reference counterpart: the same letterbox for video - BGR or NV12 frames
  *                       onto a square or rectangular canvas (yh_letterbox is this for BGR, square)
  *   yh_letterbox_frames_host, yh_nv12_to_bgr_host   the same, and the conversion alone, on the host
+ *   yh_crop_rois        no reference counterpart (the reference has no second stage): one fixed-size
+ *                       RGB crop per detection, cut from the BGR or NV12 source frame with the
+ *                       letterbox's resize, for a batch in one launch
+ *   yh_crop_rois_host   the same in host memory
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -381,6 +385,56 @@ int yh_letterbox_geometry2(int height, int width, int canvas_h, int canvas_w, in
 int yh_letterbox_frames(const yh_frame* frames, int batch, int canvas_h, int canvas_w, void* dst, void* stream);
 int yh_letterbox_frames_host(const yh_frame* frame, int canvas_h, int canvas_w, void* dst, int threads);
 int yh_nv12_to_bgr_host(const yh_frame* frame, void* dst_bgr /* height x width x 3, tight */);
+
+/* Fixed-size crops of detections from their source frames, for a second-stage model: one launch
+ * per 32 frames, nothing read back. (No reference counterpart: the rules below are the
+ * specification; tests/_crop_cases.py restates them in numpy.)
+ *
+ *   frames:  host array of `batch` descriptors as for yh_letterbox_frames (BGR or NV12, mixed, any
+ *            sizes, strided rows); the planes are device memory for yh_crop_rois and host memory
+ *            for yh_crop_rois_host
+ *   boxes:   (batch, max_rois, box_stride) f32, box_stride >= 4; columns 0..3 are x1, y1, x2, y2
+ *            in the pixels of frame b (box_stride 6: the rows of yh_nms, yh_merge and yh_track)
+ *   counts:  (batch) int32, clamped to [0, max_rois]; rows at or beyond it are never read
+ *   crops:   (capacity, 3, out_h, out_w) uint8, RGB, CHW (4-byte aligned on the device)
+ *   rois:    (capacity, 6) int32: frame, row, x0, y0, w, h
+ *   total:   (1) int32
+ * Every byte of crops, rois and total is written.
+ *
+ * 1. Compaction. With n_b the clamped counts, row r of frame b has slot s = n_0 + ... + n_(b-1) + r.
+ *    Rows with s >= capacity are dropped; total = min(sum n_b, capacity); slots at or beyond total
+ *    are zero in crops and in rois.
+ * 2. Rectangle, in fp32 with one rounding per operation:
+ *      bw = x2 - x1; bh = y2 - y1; px = bw * pad; py = bh * pad;
+ *      X1 = x1 - px; Y1 = y1 - py; X2 = x2 + px; Y2 = y2 + py.
+ *    If any of the four is not finite the ROI is empty. Otherwise, clamped in float before the
+ *    conversion, x0 = (int)min(max(floorf(X1), 0), W), ix1 = (int)min(max(ceilf(X2), 0), W),
+ *    w = ix1 - x0, and y0, h alike with H. The ROI is empty if w < 1 or h < 1. An empty ROI keeps
+ *    its slot: its rois row is (b, r, 0, 0, 0, 0) and its crop is zero.
+ * 3. Pixels. Let V be the BGR view [y0 : y0 + h, x0 : x0 + w] of the frame (of the frame's
+ *    yh_nv12_to_bgr_host image for NV12; a tap is converted where it is read, with the chroma pair
+ *    of the absolute pixel, so odd origins are legal and no BGR frame is materialised).
+ *      keep_aspect = 1: the crop is the letterbox of V on an out_h x out_w canvas
+ *                       (yh_letterbox_frames_host); where yh_letterbox_geometry2 rejects
+ *                       (h, w, out_h, out_w) - a resized side below 1 - the ROI is empty as in 2.
+ *      keep_aspect = 0: V resized to out_h x out_w with the same three paths (copy for equal
+ *                       sizes, the exact-2x area path, else linear with the vector/scalar tail of
+ *                       a 3 * out_w byte row): yh_resize_linear_host of V, flipped to RGB, CHW.
+ * 4. YH_EINVAL (message in yh_last_error()), nothing launched: a negative batch, max_rois or
+ *    capacity; out_h < 1; out_w < 4 or out_w % 4 != 0; box_stride < 4; pad negative or not finite;
+ *    keep_aspect outside {0, 1}; a NULL required pointer; a frame that yh_nv12_to_bgr_host's
+ *    validation rejects (each frame is checked against its own size as canvas). batch == 0 or
+ *    capacity == 0 is valid: total = 0.
+ *
+ * yh_crop_rois is asynchronous on `stream`, allocates nothing and never synchronises; the device
+ * and the host compute the same bytes. yh_crop_rois_host splits the slots over `threads`
+ * (<= 0: every hardware thread) and is synchronous. */
+int yh_crop_rois(const yh_frame* frames, int batch, const float* boxes, int box_stride, const int* counts,
+                 int max_rois, int out_h, int out_w, int keep_aspect, float pad, int capacity, void* crops,
+                 int* rois, int* total, void* stream);
+int yh_crop_rois_host(const yh_frame* frames, int batch, const float* boxes, int box_stride, const int* counts,
+                      int max_rois, int out_h, int out_w, int keep_aspect, float pad, int capacity, void* crops,
+                      int* rois, int* total, int threads);
 
 /* cv2.resize(src, (new_w, new_h), INTER_LINEAR) of one uint8 HWC 3-channel host image
  * (the resize step alone; dst is new_h x new_w x 3, channel order kept). */

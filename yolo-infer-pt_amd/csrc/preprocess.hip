@@ -33,6 +33,8 @@
 // shift 20, nearest chroma; OpenCV's published COLOR_YUV2BGR_NV12 coefficients, parity
 // unpinned against cv2 like the resize) wherever the resize reads a source pixel, so the
 // canvas is the BGR letterbox of the converted frame without that frame ever existing.
+// yh_crop_rois / yh_crop_rois_host (further down) run the same resize with a box of a frame as
+// the source: one fixed-size crop per detection.
 #include <cmath>
 #include <string>
 #include <thread>
@@ -56,6 +58,7 @@ struct LbImage {
     int tail;                   // lb_vtail(3 nw)
     int format, matrix;         // YH_PIX_*, YH_YUV_*
     int mode;                   // LbMode
+    int ox, oy;                 // origin of the h x w source inside the planes (a crop; 0 for a whole frame)
 };
 
 struct LbAxis {
@@ -93,8 +96,11 @@ __host__ __device__ inline int lb_vtail(int width) {
 __host__ __device__ inline int lb_sat(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // B, G, R of source pixel (y, x): the bytes of a BGR frame, one conversion of an NV12 frame
-// (limited range, shift 20, the chroma pair of (y >> 1, x >> 1); include/yolo_hip.h)
+// (limited range, shift 20, the chroma pair of (y >> 1, x >> 1); include/yolo_hip.h). The origin
+// is added here, so the chroma pair of a crop is that of the absolute pixel (odd origins are legal).
 __host__ __device__ inline void lb_tap(const LbImage& im, int y, int x, int bgr[3]) {
+    y += im.oy;
+    x += im.ox;
     if (im.format == YH_PIX_NV12) {
         const int Y = im.p0[(size_t)y * im.stride0 + x];
         const unsigned char* c = im.p1 + (size_t)(y >> 1) * im.stride1 + ((x >> 1) << 1);
@@ -164,7 +170,7 @@ __host__ __device__ inline void lb_pixel_row(const LbImage& im, const LbRow& row
 }
 
 // the resize path and its constants from h, w, nh, nw
-inline void lb_finish(LbImage& im) {
+__host__ __device__ inline void lb_finish(LbImage& im) {
     im.mode = im.nh == im.h && im.nw == im.w ? LB_COPY : (im.h == 2 * im.nh && im.w == 2 * im.nw ? LB_AREA2 : LB_LINEAR);
     im.sx = 1.0 / ((double)im.nw / (double)im.w);
     im.sy = 1.0 / ((double)im.nh / (double)im.h);
@@ -173,7 +179,7 @@ inline void lb_finish(LbImage& im) {
 
 // geometry of one image on a canvas_h x canvas_w canvas (dataset.py:95-103, 292-313 for a
 // square one), in the reference's double arithmetic; NULL or the reason it is rejected
-inline const char* lb_geometry(int h, int w, int ch, int cw, LbImage& im) {
+__host__ __device__ inline const char* lb_geometry(int h, int w, int ch, int cw, LbImage& im) {
     if (h <= 0 || w <= 0 || ch <= 0 || cw <= 0) return "letterbox: image and canvas sides must be positive";
     const double rh = (double)ch / (double)h, rw = (double)cw / (double)w;
     const double r = rh < rw ? rh : rw;
@@ -183,8 +189,8 @@ inline const char* lb_geometry(int h, int w, int ch, int cw, LbImage& im) {
     if (nh > ch || nw > cw) return "letterbox: the resized image exceeds the canvas";
     const double dw = (cw - nw) / 2.0, dh = (ch - nh) / 2.0;
     im.h = h; im.w = w; im.nh = nh; im.nw = nw;
-    im.top = (int)std::nearbyint(dh - 0.1);
-    im.left = (int)std::nearbyint(dw - 0.1);
+    im.top = (int)nearbyint(dh - 0.1);
+    im.left = (int)nearbyint(dw - 0.1);
     lb_finish(im);
     return nullptr;
 }
@@ -314,6 +320,276 @@ inline yh_frame lb_bgr_frame(const void* src, int height, int width, int stride)
     return f;
 }
 
+// ---------------------------------------------------------------- yh_crop_rois
+// Fixed-size crops of boxes from BGR / NV12 frames (no reference counterpart; include/yolo_hip.h
+// states the semantics, tests/_crop_cases.py restates them). A crop is the letterbox above with
+// the rectangle as its source: crop_image turns a frame's descriptor and a box into an LbImage
+// whose origin lb_tap adds, on the device and on the host alike.
+
+struct CropRect {
+    int x0, y0, w, h;
+};
+
+// the exponent is not all ones (a bit test: no floating-point assumption can fold it away)
+__host__ __device__ inline bool crop_finite(float v) {
+    return (__builtin_bit_cast(unsigned, v) & 0x7f800000u) != 0x7f800000u;
+}
+
+// (int)min(max(v, 0), hi), clamped in float: v is finite, so the conversion is defined
+__host__ __device__ inline int crop_clamp(float v, int hi) {
+    const float h = (float)hi;
+    v = v < 0.f ? 0.f : v;
+    v = v > h ? h : v;
+    return (int)v;
+}
+
+// The padded box, rounded outwards and clipped to the H x W frame; false for an empty ROI
+// (rc is zero then). fp32, one rounding per operation.
+__host__ __device__ inline bool crop_rect(const float* box, float pad, int H, int W, CropRect& rc) {
+#pragma clang fp contract(off)
+    rc = CropRect{0, 0, 0, 0};
+    const float x1 = box[0], y1 = box[1], x2 = box[2], y2 = box[3];
+    const float bw = x2 - x1, bh = y2 - y1;
+    const float px = bw * pad, py = bh * pad;
+    const float X1 = x1 - px, Y1 = y1 - py, X2 = x2 + px, Y2 = y2 + py;
+    if (!(crop_finite(X1) && crop_finite(Y1) && crop_finite(X2) && crop_finite(Y2))) return false;
+    const int ix0 = crop_clamp(floorf(X1), W), ix1 = crop_clamp(ceilf(X2), W);
+    const int iy0 = crop_clamp(floorf(Y1), H), iy1 = crop_clamp(ceilf(Y2), H);
+    const int w = ix1 - ix0, h = iy1 - iy0;
+    if (w < 1 || h < 1) return false;
+    rc = CropRect{ix0, iy0, w, h};
+    return true;
+}
+
+// LbImage of one ROI on an oh x ow crop from `fr`, its frame described on the frame's own size;
+// false for an empty ROI (rc is zero then)
+__host__ __device__ inline bool crop_image(const LbImage& fr, const float* box, float pad, int oh, int ow,
+                                           int keep_aspect, LbImage& im, CropRect& rc) {
+    im = fr;
+    if (!crop_rect(box, pad, fr.h, fr.w, rc)) return false;
+    if (keep_aspect) {
+        if (lb_geometry(rc.h, rc.w, oh, ow, im) != nullptr) {   // a resized side below 1 pixel
+            rc = CropRect{0, 0, 0, 0};
+            return false;
+        }
+    } else {
+        im.h = rc.h; im.w = rc.w; im.nh = oh; im.nw = ow;
+        im.top = im.left = 0;
+        lb_finish(im);
+    }
+    im.ox = rc.x0; im.oy = rc.y0;
+    return true;
+}
+
+__host__ __device__ inline int crop_count(int n, int max_rois) { return n < 0 ? 0 : (n > max_rois ? max_rois : n); }
+
+struct CropBatch {
+    LbImage fr[LB_MAX];      // frames b0 .. b0 + LB_MAX - 1, each on its own size
+    const float* boxes;      // (batch, max_rois, box_stride)
+    const int* counts;       // (batch)
+    unsigned char* crops;    // (capacity, 3, oh, ow) uint8, 4-byte aligned, ow % 4 == 0
+    int* rois;               // (capacity, 6)
+    int* total;              // (1)
+    int batch, b0, max_rois, box_stride, oh, ow, keep_aspect, capacity, chunks;
+    float pad;
+};
+
+enum CropState { CROP_SKIP = 0, CROP_ZERO = 1, CROP_LIVE = 2 };
+// 4-pixel groups per workgroup, one per thread. 1024 (a loop of four per thread) was measured too:
+// the walk and the geometry are then paid a quarter as often, which helps few small crops, but the
+// loop costs 24 VGPRs (84: 5 waves per SIMD instead of 8) and many large crops get slower
+// (DESIGN.md section 14).
+constexpr int CROP_CHUNK = 256;
+
+// One workgroup: CROP_CHUNK 4-pixel groups (a chunk) of one slot. Wave 0 finds the slot's
+// (frame, row) by a prefix walk over all clamped counts and makes the ROI's LbImage once; then one
+// thread is 4 consecutive pixels of a crop row, all three planes, as in letterbox_frames_u8. A slot
+// whose frame another launch holds is left to that launch; the launch of frame 0 zero-fills the
+// slots beyond total and writes total.
+__global__ __launch_bounds__(256) void crop_rois_u8(const CropBatch b) {
+    __shared__ LbImage s_im;
+    __shared__ int s_state;
+    const int slot = blockIdx.x / b.chunks, chunk = blockIdx.x - slot * b.chunks;
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        const bool first = b.b0 == 0;
+        const bool need_total = first && blockIdx.x == 0;
+        int base = 0, f = -1, r = 0;
+        for (int k0 = 0; k0 < b.batch && (f < 0 || need_total); k0 += 64) {
+            const int k = k0 + lane;
+            const int n = k < b.batch ? crop_count(b.counts[k], b.max_rois) : 0;
+            int inc = n;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int t = __shfl_up(inc, d);
+                if (lane >= d) inc += t;
+            }
+            const int excl = base + inc - n;
+            const unsigned long long hit = __ballot(slot >= excl && slot < excl + n);
+            if (hit != 0 && f < 0) {
+                const int src = __ffsll((long long)hit) - 1;
+                f = k0 + src;
+                r = slot - __shfl(excl, src);
+            }
+            base += __shfl(inc, 63);
+        }
+        // f, r and base are the same in every lane
+        int state = f < 0 ? (first ? CROP_ZERO : CROP_SKIP) : CROP_SKIP;
+        LbImage im;
+        CropRect rc{0, 0, 0, 0};
+        if (f >= b.b0 && f < b.b0 + LB_MAX) {
+            const int fl = __builtin_amdgcn_readfirstlane(f - b.b0);
+            const float* box = b.boxes + ((size_t)f * b.max_rois + r) * b.box_stride;
+            state = crop_image(b.fr[fl], box, b.pad, b.oh, b.ow, b.keep_aspect, im, rc) ? CROP_LIVE : CROP_ZERO;
+        }
+        if (lane == 0) {
+            s_state = state;
+            if (state == CROP_LIVE) s_im = im;
+            if (chunk == 0 && state != CROP_SKIP) {
+                int* o = b.rois + (size_t)slot * 6;
+                o[0] = f < 0 ? 0 : f; o[1] = f < 0 ? 0 : r;
+                o[2] = rc.x0; o[3] = rc.y0; o[4] = rc.w; o[5] = rc.h;
+            }
+            if (need_total) *b.total = base < b.capacity ? base : b.capacity;
+        }
+    }
+    __syncthreads();
+    const int state = s_state;
+    if (state == CROP_SKIP) return;
+    const int gw = b.ow >> 2;
+    const int q = chunk * CROP_CHUNK + threadIdx.x;
+    if (q >= gw * b.oh) return;
+    const int y = q / gw, x0 = (q - y * gw) * 4;
+    unsigned out[3] = {0u, 0u, 0u};
+    if (state == CROP_LIVE) {
+        const LbImage& im = s_im;
+        const LbRow row = lb_row(im, y);
+        if (row.dy >= 0 && x0 + 3 >= im.left && x0 < im.left + im.nw) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                unsigned char rgb[3];
+                lb_pixel_row(im, row, x0 + k, rgb);
+                out[0] |= (unsigned)rgb[0] << (8 * k);
+                out[1] |= (unsigned)rgb[1] << (8 * k);
+                out[2] |= (unsigned)rgb[2] << (8 * k);
+            }
+        }
+    }
+    const size_t plane = (size_t)b.oh * b.ow;
+    unsigned char* o = b.crops + (size_t)slot * 3 * plane + (size_t)y * b.ow + x0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<unsigned*>(o + c * plane) = out[c];
+}
+
+struct CropArgs {
+    const yh_frame* frames;
+    int batch;
+    const float* boxes;
+    int box_stride;
+    const int* counts;
+    int max_rois, oh, ow, keep_aspect;
+    float pad;
+    int capacity;
+    void* crops;
+    int* rois;
+    int* total;
+};
+
+// every YH_EINVAL of yh_crop_rois / yh_crop_rois_host; returns the frames on their own sizes
+std::vector<LbImage> crop_check(const CropArgs& a) {
+    require(a.batch >= 0 && a.max_rois >= 0 && a.capacity >= 0, "crop_rois: negative batch, max_rois or capacity");
+    require(a.oh >= 1, "crop_rois: out_h must be at least 1");
+    require(a.ow >= 4 && a.ow % 4 == 0, "crop_rois: out_w must be a positive multiple of 4");
+    require(a.box_stride >= 4, "crop_rois: box_stride must be at least 4");
+    require(crop_finite(a.pad) && a.pad >= 0.f, "crop_rois: pad must be finite and not negative");
+    require(a.keep_aspect == 0 || a.keep_aspect == 1, "crop_rois: keep_aspect must be 0 or 1");
+    require(a.total != nullptr, "crop_rois: total is NULL");
+    require(a.batch == 0 || (a.frames != nullptr && a.counts != nullptr), "crop_rois: frames or counts is NULL");
+    require(a.batch == 0 || a.max_rois == 0 || a.boxes != nullptr, "crop_rois: boxes is NULL");
+    require(a.capacity == 0 || (a.crops != nullptr && a.rois != nullptr), "crop_rois: crops or rois is NULL");
+    require((long long)a.batch * a.max_rois < (1ll << 31), "crop_rois: batch * max_rois too large");
+    std::vector<LbImage> fr((size_t)a.batch);
+    for (int k = 0; k < a.batch; ++k) fr[k] = lb_describe(a.frames[k], a.frames[k].height, a.frames[k].width);
+    return fr;
+}
+
+void crop_launch(const CropArgs& a, void* stream) {
+    const std::vector<LbImage> fr = crop_check(a);
+    require(reinterpret_cast<uintptr_t>(a.crops) % 4 == 0, "crop_rois: crops must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (a.capacity == 0) {
+        HIPCHECK(hipMemsetAsync(a.total, 0, sizeof(int), st));
+        return;
+    }
+    const long long groups = (long long)(a.ow / 4) * a.oh;
+    const long long chunks = (groups + CROP_CHUNK - 1) / CROP_CHUNK;
+    require(groups < (1ll << 30) && chunks * a.capacity < (1ll << 31), "crop_rois: capacity x crop size too large");
+    CropBatch cb{};
+    cb.boxes = a.boxes; cb.counts = a.counts;
+    cb.crops = static_cast<unsigned char*>(a.crops); cb.rois = a.rois; cb.total = a.total;
+    cb.batch = a.batch; cb.max_rois = a.max_rois; cb.box_stride = a.box_stride;
+    cb.oh = a.oh; cb.ow = a.ow; cb.keep_aspect = a.keep_aspect; cb.capacity = a.capacity;
+    cb.chunks = (int)chunks; cb.pad = a.pad;
+    for (int b0 = 0; b0 == 0 || b0 < a.batch; b0 += LB_MAX) {   // batch 0: one launch zero-fills
+        cb.b0 = b0;
+        for (int k = 0; k < LB_MAX; ++k) cb.fr[k] = b0 + k < a.batch ? fr[b0 + k] : LbImage{};
+        hipLaunchKernelGGL(crop_rois_u8, dim3((unsigned)(chunks * a.capacity)), dim3(256), 0, st, cb);
+        HIPCHECK(hipGetLastError());
+    }
+}
+
+void crop_host(const CropArgs& a, int threads) {
+    const std::vector<LbImage> fr = crop_check(a);
+    std::vector<long long> start((size_t)a.batch + 1, 0);
+    for (int k = 0; k < a.batch; ++k) start[k + 1] = start[k] + crop_count(a.counts[k], a.max_rois);
+    const int total = (int)(start[a.batch] < a.capacity ? start[a.batch] : a.capacity);
+    *a.total = total;
+    const size_t plane = (size_t)a.oh * a.ow;
+    unsigned char* crops = static_cast<unsigned char*>(a.crops);
+    auto slots = [&](int s0, int s1) {
+        int f = 0;
+        for (int s = s0; s < s1; ++s) {
+            unsigned char* o = crops + (size_t)s * 3 * plane;
+            int* ro = a.rois + (size_t)s * 6;
+            LbImage im;
+            CropRect rc{0, 0, 0, 0};
+            bool live = false;
+            ro[0] = ro[1] = 0;
+            if (s < total) {
+                while (start[f + 1] <= s) ++f;
+                const int r = (int)(s - start[f]);
+                ro[0] = f; ro[1] = r;
+                live = crop_image(fr[f], a.boxes + ((size_t)f * a.max_rois + r) * a.box_stride, a.pad, a.oh, a.ow,
+                                  a.keep_aspect, im, rc);
+            }
+            ro[2] = rc.x0; ro[3] = rc.y0; ro[4] = rc.w; ro[5] = rc.h;
+            if (!live) {
+                std::memset(o, 0, 3 * plane);
+                continue;
+            }
+            for (int y = 0; y < a.oh; ++y) {
+                const LbRow row = lb_row(im, y);
+                for (int x = 0; x < a.ow; ++x) {
+                    unsigned char rgb[3];
+                    lb_pixel_row(im, row, x, rgb);
+                    const size_t q = (size_t)y * a.ow + x;
+                    o[q] = rgb[0]; o[plane + q] = rgb[1]; o[2 * plane + q] = rgb[2];
+                }
+            }
+        }
+    };
+    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    nt = nt < a.capacity ? nt : a.capacity;
+    if (nt <= 1) {
+        slots(0, a.capacity);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (int t = 0; t < nt; ++t)
+        pool.emplace_back(slots, (int)((long long)a.capacity * t / nt), (int)((long long)a.capacity * (t + 1) / nt));
+    for (auto& th : pool) th.join();
+}
+
 }  // namespace yh
 
 using namespace yh;
@@ -366,6 +642,24 @@ extern "C" int yh_nv12_to_bgr_host(const yh_frame* frame, void* dst_bgr) {
                 unsigned char* p = o + ((size_t)y * im.w + x) * 3;
                 p[0] = (unsigned char)t[0]; p[1] = (unsigned char)t[1]; p[2] = (unsigned char)t[2];
             }
+    });
+}
+
+extern "C" int yh_crop_rois(const yh_frame* frames, int batch, const float* boxes, int box_stride, const int* counts,
+                            int max_rois, int out_h, int out_w, int keep_aspect, float pad, int capacity, void* crops,
+                            int* rois, int* total, void* stream) {
+    return guarded([&] {
+        crop_launch(CropArgs{frames, batch, boxes, box_stride, counts, max_rois, out_h, out_w, keep_aspect, pad,
+                             capacity, crops, rois, total}, stream);
+    });
+}
+
+extern "C" int yh_crop_rois_host(const yh_frame* frames, int batch, const float* boxes, int box_stride,
+                                 const int* counts, int max_rois, int out_h, int out_w, int keep_aspect, float pad,
+                                 int capacity, void* crops, int* rois, int* total, int threads) {
+    return guarded([&] {
+        crop_host(CropArgs{frames, batch, boxes, box_stride, counts, max_rois, out_h, out_w, keep_aspect, pad,
+                           capacity, crops, rois, total}, threads);
     });
 }
 

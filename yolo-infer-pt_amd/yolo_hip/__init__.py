@@ -5,7 +5,8 @@ non_max_suppression; `Evaluator` (yolo_hip.evaluate) is the batched mAP
 evaluation over those detections; `Detector` (yolo_hip.detect) returns detections in
 source-image pixels, optionally from tiled inference (`tiles`, `tile_transform`, `merge`),
 from BGR or `NV12` video frames on a square or rectangular canvas (`letterbox_frames`,
-`rect_canvas`; yolo_hip.preprocess);
+`rect_canvas`; yolo_hip.preprocess), and `crop_rois` cuts one fixed-size crop per detection from
+those frames for a second-stage model (`Crops`);
 `Tracker` (yolo_hip.track) gives the detections of video streams identities across frames
 (`track`, `track_state`, `Tracks`). The drop-in module API lives in `nets.nn` / `utils.util`.
 """
@@ -26,7 +27,7 @@ def __getattr__(name):
     if name in ("tiles", "tile_transform"):
         from . import detect
         return getattr(detect, name)
-    if name in ("NV12", "letterbox_frames", "rect_canvas"):
+    if name in ("NV12", "letterbox_frames", "rect_canvas", "crop_rois", "Crops"):
         from . import preprocess
         return getattr(preprocess, name)
     if name in ("Tracker", "Tracks", "track", "track_state"):

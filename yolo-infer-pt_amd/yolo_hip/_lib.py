@@ -96,6 +96,10 @@ _PROTOS = {
     "yh_letterbox_frames": (c_int, [POINTER(YhFrame), c_int, c_int, c_int, c_void_p, c_void_p]),
     "yh_letterbox_frames_host": (c_int, [POINTER(YhFrame), c_int, c_int, c_void_p, c_int]),
     "yh_nv12_to_bgr_host": (c_int, [POINTER(YhFrame), c_void_p]),
+    "yh_crop_rois": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                             c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "yh_crop_rois_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_float, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     "yh_resize_linear_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "yh_debug_op_desc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
     "yh_debug_run_ops": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),

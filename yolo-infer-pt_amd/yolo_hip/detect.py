@@ -140,11 +140,14 @@ def merge(dets, counts, tile_xf, tile_offsets, image_wh, max_tiles, iou=0.65, ma
 
 class Detections:
     """Result of Detector.predict: dets (n, max_det, 6) f32 = x1, y1, x2, y2, score, class in source
-    pixels and counts (n,) i32, both on the device; rows beyond an image's count are 0."""
+    pixels and counts (n,) i32, both on the device; rows beyond an image's count are 0. frames:
+    the device-resident sources of predict(..., keep_frames=True) (BGR tensors and NV12 objects,
+    what preprocess.crop_rois takes), else None."""
 
-    def __init__(self, dets, counts):
+    def __init__(self, dets, counts, frames=None):
         self.dets = dets
         self.counts = counts
+        self.frames = frames
 
     def __len__(self):
         return self.dets.shape[0]
@@ -218,7 +221,10 @@ class Detector:
                              f"MERGE_MAX_CAND = {MERGE_MAX_CAND}; use larger tiles or less overlap")
         return crops, tmd, max_tiles
 
-    def predict(self, images):
+    def predict(self, images, keep_frames=False):
+        """images -> Detections. keep_frames=True also returns the device-resident sources as
+        `.frames`, so preprocess.crop_rois(det.frames, det.dets, det.counts, ...) needs no second
+        upload."""
         from .preprocess import NV12, letterbox, letterbox_frames
         dev = self.device
         srcs, shapes = [], []
@@ -240,7 +246,7 @@ class Detector:
         crops, tmd, max_tiles = self.plan(shapes)
         if n == 0:
             return Detections(torch.zeros((0, self.max_det, 6), dtype=torch.float32, device=dev),
-                              torch.zeros((0,), dtype=torch.int32, device=dev))
+                              torch.zeros((0,), dtype=torch.int32, device=dev), [] if keep_frames else None)
         canvas = ch, cw = self.canvas or (self.size, self.size)
         # host-side geometry of every tile, uploaded as one pinned block (below):
         # [xf (padded tile axis) x 6 | wh n x 2 | offsets n + 1 (i32)]
@@ -288,4 +294,4 @@ class Detector:
                 pipe.wait(e)
             out = merge(tdets, tcounts, tile_xf, tile_offsets, image_wh, max_tiles, iou=self.merge_iou,
                         max_out=self.max_det)
-        return Detections(*out)
+        return Detections(*out, srcs if keep_frames else None)

@@ -16,8 +16,12 @@ oracle/preprocess.py and to torch's bilinear resize within one level.
 decoder's Y plane and interleaved half-resolution UV plane, converted tap by tap inside the
 resize, include/yolo_hip.h) and the canvas may be a rectangle (`rect_canvas`), so a 16:9 frame
 does not pay for the zero rows of a square canvas.
+
+`crop_rois` (yh_crop_rois / _host) is the step after the detector: one fixed-size RGB crop per box,
+cut from the full-resolution BGR or NV12 frame with the same resize, for a second-stage model.
 """
 from ctypes import byref, c_int, c_void_p
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -242,3 +246,115 @@ def letterbox_frames(frames, canvas, device=None, out=None):
     for t in srcs:   # keep the sources alive for the queued kernel
         t.record_stream(stream)
     return out
+
+
+class Crops(NamedTuple):
+    """Result of `crop_rois`: data (capacity, 3, h, w) uint8 RGB CHW, rois (capacity, 6) i32 rows of
+    frame, row, x0, y0, w, h and total (1,) i32, all on the device of the boxes. Slots at or beyond
+    total are zero, and so is the crop of an empty ROI (w = h = 0)."""
+    data: torch.Tensor
+    rois: torch.Tensor
+    total: torch.Tensor
+
+    def gather(self, t):
+        """t (B, max_rois, ...) -> (capacity, ...): t[frame, row] of every slot, so that scores,
+        classes or track ids follow their crops. No synchronisation; slots at or beyond total (rois
+        rows of zeros) pick t[0, 0]."""
+        if t.shape[0] == 0 or t.shape[1] == 0:
+            return t.new_zeros((self.rois.shape[0],) + tuple(t.shape[2:]))
+        idx = self.rois.long()
+        return t[idx[:, 0], idx[:, 1]]
+
+    def tolist(self):
+        """[(crop (3, h, w), (frame, row, x0, y0, w, h)), ...] of the first total slots (reads total
+        on the host: synchronises the current stream)."""
+        n = int(self.total.item())
+        return [(self.data[i], tuple(r)) for i, r in enumerate(self.rois[:n].tolist())]
+
+
+def _check_crop(name, t, shape, dtype, device):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"yolo_hip.crop_rois: {name} must be a tensor")
+    if t.dtype != dtype:
+        raise TypeError(f"yolo_hip.crop_rois: {name} must be {dtype}, got {t.dtype}")
+    if t.device != device:
+        raise ValueError(f"yolo_hip.crop_rois: {name} is on {t.device}, expected {device}")
+    if len(shape) != t.dim() or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+        want = tuple("*" if w is None else w for w in shape)
+        raise ValueError(f"yolo_hip.crop_rois: {name} has shape {tuple(t.shape)}, expected {want}")
+    if not t.is_contiguous():
+        raise ValueError(f"yolo_hip.crop_rois: {name} must be contiguous")
+
+
+def crop_rois(frames, boxes, counts, size, keep_aspect=False, pad=0.0, capacity=None, device=None, out=None,
+              threads=0):
+    """One fixed-size RGB crop per box, cut from the boxes' source frames: all frames of a call in
+    one launch per 32 frames, nothing read back (yh_crop_rois; include/yolo_hip.h is the spec).
+
+    frames: B frames as for `letterbox_frames` (BGR tensors / arrays and `NV12`, mixed, any sizes);
+    boxes (B, max_rois, S >= 4) f32 with x1, y1, x2, y2 in frame pixels first - `Detections.dets` and
+    `Tracks.dets` as they lie; counts (B,) i32 (rows at or beyond it are never read). size: int or
+    (h, w), w a multiple of 4. keep_aspect=False stretches the box to the crop; True letterboxes it
+    on a zero border. pad widens the box by that fraction of its size on every side. capacity
+    (default B * max_rois) is the number of slots; rows beyond it are dropped.
+    -> Crops(data, rois, total); out=(data, rois, total) reuses buffers. Every byte is written.
+
+    cuda boxes run the HIP kernel asynchronously on the current stream of their device (host frames
+    are copied there first); CPU boxes with host frames run the host twin (yh_crop_rois_host,
+    `threads` <= 0: every hardware thread), which computes the same bytes."""
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 3:
+        raise ValueError("yolo_hip.crop_rois: boxes must be a (B, max_rois, S) tensor")
+    dev = boxes.device
+    if device is not None and torch.device(device) != dev:
+        raise ValueError(f"yolo_hip.crop_rois: boxes are on {dev}, expected {torch.device(device)}")
+    B, M, S = boxes.shape
+    if len(frames) != B:
+        raise ValueError(f"yolo_hip.crop_rois: {len(frames)} frames for boxes of {B} frames")
+    _check_crop("boxes", boxes, (B, M, S), torch.float32, dev)
+    _check_crop("counts", counts, (B,), torch.int32, dev)
+    oh, ow = _hw(size)
+    capacity = B * M if capacity is None else int(capacity)
+    srcs, descs = [], (YhFrame * max(1, B))()
+    for k, f in enumerate(frames):
+        if isinstance(f, NV12):
+            if dev.type == "cuda":
+                f = f.to(dev, non_blocking=True)
+            elif f.device != dev:
+                raise ValueError("yolo_hip.crop_rois: CPU boxes need host frames")
+            srcs.extend(f.tensors())
+            descs[k] = f._desc()
+        else:
+            t = _bgr(f, "crop_rois")
+            if dev.type == "cuda":
+                t = t.to(dev, non_blocking=True)
+            elif t.device != dev:
+                raise ValueError("yolo_hip.crop_rois: CPU boxes need host frames")
+            srcs.append(t)
+            descs[k] = _bgr_desc(t)
+    if out is None:
+        data = torch.empty((max(capacity, 0), 3, max(oh, 0), max(ow, 0)), dtype=torch.uint8, device=dev)
+        rois = torch.empty((max(capacity, 0), 6), dtype=torch.int32, device=dev)
+        total = torch.empty((1,), dtype=torch.int32, device=dev)
+    else:
+        data, rois, total = out
+        _check_crop("out data", data, (capacity, 3, oh, ow), torch.uint8, dev)
+        _check_crop("out rois", rois, (capacity, 6), torch.int32, dev)
+        _check_crop("out total", total, (1,), torch.int32, dev)
+
+    def ptr(t):
+        return c_void_p(t.data_ptr())
+
+    args = (descs, B, ptr(boxes), S, ptr(counts), M, oh, ow, int(keep_aspect), float(pad), capacity, ptr(data),
+            ptr(rois), ptr(total))
+    if dev.type == "cuda":
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            check(lib().yh_crop_rois(*args, c_void_p(stream.cuda_stream)), "crop_rois")
+        for t in srcs:   # keep the sources alive for the queued kernel
+            t.record_stream(stream)
+    elif dev.type == "cpu":
+        check(lib().yh_crop_rois_host(*args, int(threads)), "crop_rois_host")
+    else:
+        raise ValueError(f"yolo_hip.crop_rois: unsupported device {dev}")
+    del srcs
+    return Crops(data, rois, total)
