@@ -33,6 +33,10 @@
  *                       RGB crop per detection, cut from the BGR or NV12 source frame with the
  *                       letterbox's resize, for a batch in one launch
  *   yh_crop_rois_host   the same in host memory
+ *   yh_create_cls       no reference counterpart (the reference has no classifier): the graph of
+ *                       nets/nn.py YOLOCls - Ultralytics' YOLO11-cls: DarkNet without the SPPF, C2PSA,
+ *                       then Classify (1x1 conv to 1280 + BN + SiLU, global average pool, linear, softmax)
+ *   yh_classify         YOLOCls.forward / YOLOCls.features in eval mode on a batch of crops
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -140,6 +144,52 @@ int yh_forward(yh_handle* h, const void* x, int batch, int height, int width,
  * device (u * fp32(1/255), rounded to the dtype). */
 int yh_forward_u8(yh_handle* h, const void* x, int batch, int height, int width,
                   void* y, void* stream);
+
+/* Second stage: a classifier over fixed-size crops (yh_crop_rois's output layout).
+ *
+ * yh_create_cls builds the graph of nets/nn.py YOLOCls for a variant: the detector's backbone up
+ * to net.p5.1, C2PSA as net.p5.2, then the head. Its convs are named as in the module's
+ * state_dict; the last two are "head.conv" (1x1, BatchNorm, SiLU, YH_CLS_EMBED couts) and
+ * "head.linear" (the Linear layer described as a 1x1 conv with bias: weight (nc, 1280, 1, 1)).
+ * Everything that takes a handle works on both kinds, except: yh_classify on a detection handle,
+ * and yh_forward / yh_forward_u8 / yh_num_anchors on a classifier handle, return YH_ESTATE with
+ * a message and launch nothing. On a classifier handle yh_debug_run_ops' y is the (batch, nc)
+ * fp32 probs (no logits / embed copies, no count), and per-image fp32 vectors appear among the
+ * operands of yh_debug_op_desc as 1 x 1 maps with "f32": 1 (roles "e": the embedding, "z": the
+ * logits, "a": the head conv's output), which yh_debug_operand copies as fp32.
+ *
+ * yh_classify: x as for yh_forward (x_u8 = 0: handle dtype) or yh_forward_u8 (x_u8 = 1: uint8 RGB,
+ * / 255 fused into the stem); height and width multiples of 32 (a shape some kernel of the graph
+ * has no plan for is refused with YH_EINVAL before anything is launched).
+ *   probs  (batch, nc) f32, required; logits (batch, nc) f32 and embed (batch, YH_CLS_EMBED) f32
+ *   may be NULL. count: device int32* or NULL.
+ * Asynchronous on `stream`; allocates nothing once the workspace of the shape exists; replays one
+ * captured single-chain graph per (batch, height, width, input kind) - the outputs and count are
+ * reached through an indirection, so any pointers serve.
+ *
+ * Classifier arithmetic (every dtype; f = the last feature map, HW its pixels per image):
+ *  1. a = head.conv(f), bit for bit the per-layer dense 1x1 conv's output: conv_mx's single
+ *     reduction order on 16-bit handles, folded BN, bias and SiLU in fp32, one rounding to the
+ *     handle dtype. On the fp32 handle the K sum is exact (fp64 accumulation) and this layer's bias
+ *     and SiLU are evaluated in fp64 too, so a is the fp64 conv rounded once to fp32.
+ *  2. e[b, c] = s * (float)(1.0 / HW) where s is one fp32 chain from zero over image b's pixels
+ *     in ascending row-major order: s = (..((a[b,0,c] + a[b,1,c]) + a[b,2,c]) ..) + a[b,HW-1,c].
+ *     The fused head (16-bit handles, YH_CLSHEAD=1 at yh_create_cls; the default is conv + pool,
+ *     which measured faster) runs the same chain in its epilogue, so both paths give the same e
+ *     bit for bit. The order does
+ *     not depend on the batch size, on the image's place in the batch or on the conv plan.
+ *  3. z = W e + b with W in the handle dtype (fp32 on the fp32 handle), e and the accumulation in
+ *     fp32 (per class: 64 partial fmaf chains over interleaved 8-channel chunks, added in a fixed
+ *     butterfly, the bias last); probs = exp(z - max z) / sum exp(z - max z) in fp32. Each output
+ *     element is written exactly once.
+ *  4. n = clamp(*count, 0, batch) (batch when count is NULL). Rows at or beyond n are all-zero in
+ *     probs, logits and embed. The forward still runs on every row: the shape stays fixed, nothing
+ *     synchronises and the graph replays. This is how yh_crop_rois' `total` is consumed without a
+ *     read-back. */
+#define YH_CLS_EMBED 1280
+int yh_create_cls(const yh_variant* variant, int device, int dtype, yh_handle** out);
+int yh_classify(yh_handle* h, const void* x, int x_u8, int batch, int height, int width,
+                const int* count, float* probs, float* logits, float* embed, void* stream);
 
 /* Bytes of device workspace yh_nms needs for a (batch, 4 + num_classes, anchors) input. */
 size_t yh_nms_workspace_bytes(int batch, int num_classes, int anchors);
@@ -454,7 +504,8 @@ int yh_op_count(const yh_handle* h);
  * path), class (0 dense 3x3 conv, 1 dense 1x1 conv, 2 stem conv, 3 depthwise,
  * 4 SPPF pools, 5 PSA attention, 6 head decode, 7 fused head cls branch,
  * 8 fused box tail with DFL, 9 fused C3k2 block, 10 fused C3k block, 11 fused box branch of all
- * levels), algorithmic bytes (each
+ * levels, 12 pointwise chain, 13 classifier head: pool, fused conv + pool, linear + softmax),
+ * algorithmic bytes (each
  * operand read once, each output written once, handle dtype) and FLOPs per
  * call, accumulated profiled milliseconds and call count. */
 int yh_op_info(const yh_handle* h, int index, int batch, int height, int width,

@@ -10,7 +10,9 @@ namespace yh {
 enum DType { F32 = 0, F16 = 1, BF16 = 2 };
 inline int dtype_size(int dt) { return dt == F32 ? 4 : 2; }
 
-enum Act { ACT_ID = 0, ACT_SILU = 1 };
+// ACT_SILU_F64: SiLU of (K sum + bias) evaluated in fp64 and rounded once to fp32; only the fp32
+// handle's classifier head conv (conv_gemm's EXACT instances), whose output is held to one ulp
+enum Act { ACT_ID = 0, ACT_SILU = 1, ACT_SILU_F64 = 2 };
 
 // floor(n / d) for a run-time divisor without a division: (n * m) >> s with
 // m = floor(2^s / d) + 1. Exact for 0 <= n < 2^s / d while n * m < 2^32 (hc_exact is the host
@@ -328,6 +330,63 @@ struct PwChainArgs {
     const void* zero;                  // >= 16 zero bytes
 };
 int launch_pw_chain(int dtype, const PwChainArgs& a, int lds, hipStream_t s);
+
+// Classifier head (cls.hip; nets/nn.py Classify): 1x1 conv to CLS_EMBED channels + SiLU, the
+// per-image mean over pixels, the linear layer and the softmax. Summation order of the mean
+// (include/yolo_hip.h, "classifier arithmetic"): one fp32 chain per (image, channel) from zero over
+// the image's pixels in ascending row-major order, then one multiplication by (float)(1.0 / HW).
+constexpr int CLS_EMBED = 1280;
+constexpr int CLS_THREADS = 256;                          // cls_head: 4 waves
+constexpr int CLS_SCR_BYTES = 4 * 32 * 33 * 4;            // cls_head: per wave a 32 x 32 fp32 tile, rows padded
+constexpr int CLS_FC_TB = 8, CLS_FC_TN = 64;              // cls_fc: images x classes per workgroup
+// cls_pool: a (B, HW, C) in the handle dtype -> e (B, C) fp32
+struct ClsPoolArgs {
+    const void* a; int lda;
+    int B, HW, C;
+    float inv;           // (float)(1.0 / HW)
+    float* e;
+};
+// cls_head: x (B, HW, K) -> e (B, N) without the (B, HW, N) activations in between. A workgroup owns
+// G consecutive images (G * HW <= 128 pixels, a function of HW and K only) and all N channels.
+struct ClsHeadArgs {
+    const void* x; int ldx;
+    int B, HW, K, N, G;
+    const void* w; int wld;   // 16-bit weights in A-fragment order (engine upload "pwfrag")
+    const float* bias;
+    int act;
+    float inv;
+    float* e;
+};
+// pixels one cls_head workgroup can hold (0: K has no kernel), images per workgroup, LDS bytes
+inline int cls_head_pmax(int K) {
+    if (K < 128 || K % 128) return 0;
+    for (int p : {128, 64, 32})
+        if (p * (K + 8) * 2 + CLS_SCR_BYTES <= 160 * 1024) return p;
+    return 0;
+}
+inline int cls_head_group(int K, int HW) {
+    const int pm = cls_head_pmax(K);
+    return HW > 0 && HW <= pm ? pm / HW : 0;
+}
+inline int cls_head_lds(int K, int HW) {
+    const int g = cls_head_group(K, HW);
+    return g ? (g * HW + 31) / 32 * 32 * (K + 8) * 2 + CLS_SCR_BYTES : 0;
+}
+// cls_fc: z = W e + b (fp32 accumulation, W in the handle dtype), then per row the softmax, the
+// count mask and the copies to the caller's probs / logits / embed (io[2..4], count io[5])
+struct ClsFcArgs {
+    const float* e;
+    const void* w; int wld;   // [>= nc rows][wld] handle dtype
+    const float* bias;
+    int B, nc, K;
+    float* z; int ldz;
+    const void* const* io;
+};
+int launch_cls_pool(int dtype, const ClsPoolArgs& a, hipStream_t s);
+int launch_cls_head(int dtype, const ClsHeadArgs& a, hipStream_t s);
+int launch_cls_fc(int dtype, const ClsFcArgs& a, hipStream_t s);
+int launch_set_io_cls(void** io, const void* x, float* probs, float* logits, float* embed, const int* count,
+                      hipStream_t s);
 
 // launchers (return hipError_t as int)
 bool conv_kernel_ok(int dtype, int kern, const ConvArgs& a);

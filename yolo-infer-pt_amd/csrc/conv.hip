@@ -34,7 +34,8 @@ struct ConvSmem {
     static constexpr int REGION = MAIN > EPI ? MAIN : EPI;  // epilogue reuses the staging area
 };
 
-template <typename T, int BM, int BN>
+// EXACT (fp32 handle, ACT_SILU_F64): bias and SiLU on the fp64 accumulator, one rounding to fp32
+template <typename T, int BM, int BN, bool EXACT = false>
 __global__ __launch_bounds__(NT_) void conv_gemm(const ConvArgs p) {
     static_assert(BM % 64 == 0 && BN % 16 == 0, "tile");
     constexpr int MT = BM / 64;             // 16-pixel MFMA tiles per wave
@@ -185,8 +186,14 @@ __global__ __launch_bounds__(NT_) void conv_gemm(const ConvArgs p) {
             T* dst = Cs + px * LDE;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float v = Mma<T>::finish(acc[i][j][r], bv[r]);
-                if (p.act == ACT_SILU) v = silu<T>(v);
+                float v;
+                if constexpr (EXACT) {
+                    const double d = (double)acc[i][j][r] + (double)bv[r];
+                    v = (float)(d / (1.0 + exp(-d)));
+                } else {
+                    v = Mma<T>::finish(acc[i][j][r], bv[r]);
+                    if (p.act == ACT_SILU) v = silu<T>(v);
+                }
                 dst[co[r]] = fromf<T>(v);
             }
         }
@@ -223,6 +230,22 @@ int launch_conv_t(const ConvArgs& a, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm<T, BM, BN>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
+    }
+    if (a.act == ACT_SILU_F64) {
+        // instantiated for the one layer that asks for it: fp32, 128-cout tiles of 64 or 128 pixels
+        // (Net::conv_args keeps to those; the 256-pixel instance would spill)
+        if constexpr (sizeof(T) == 4 && BN == 128 && BM <= 128) {
+            static bool attr_x = false;
+            if (!attr_x) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm<T, BM, BN, true>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                attr_x = true;
+            }
+            hipLaunchKernelGGL((conv_gemm<T, BM, BN, true>), dim3(a.gm * a.gn), dim3(NT_), lds, s, a);
+            return (int)hipGetLastError();
+        } else {
+            return (int)hipErrorInvalidValue;
+        }
     }
     hipLaunchKernelGGL((conv_gemm<T, BM, BN>), dim3(a.gm * a.gn), dim3(NT_), lds, s, a);
     return (int)hipGetLastError();

@@ -17,7 +17,7 @@ int yh_abi_version(void) { return YH_ABI_VERSION; }
 
 const char* yh_last_error(void) { return yh::g_err.c_str(); }
 
-int yh_create(const yh_variant* v, int device, int dtype, yh_handle** out) {
+static int create(const yh_variant* v, int device, int dtype, yh_handle** out, int task) {
     return guarded([&] {
         yh::require(v && out, "null argument");
         yh::require(dtype == YH_F32 || dtype == YH_F16 || dtype == YH_BF16, "dtype must be YH_F32, YH_F16 or YH_BF16");
@@ -32,17 +32,22 @@ int yh_create(const yh_variant* v, int device, int dtype, yh_handle** out) {
         std::unique_ptr<yh_handle> h(new yh_handle());
         yh::Net& n = h->net;
         n.var = *v;
+        n.task = task;
         n.opt = yh::Options::from_env();
         n.device = device;
         n.dtype = dtype;
         n.es = yh::dtype_size(dtype);
         n.build();
-        HIPCHECK(hipMalloc(&n.io_dev, 2 * sizeof(void*)));
+        HIPCHECK(hipMalloc(&n.io_dev, 6 * sizeof(void*)));
+        HIPCHECK(hipMemset(n.io_dev, 0, 6 * sizeof(void*)));
         HIPCHECK(hipMalloc(&n.zero_dev, 256));
         HIPCHECK(hipMemset(n.zero_dev, 0, 256));
         *out = h.release();
     });
 }
+
+int yh_create(const yh_variant* v, int device, int dtype, yh_handle** out) { return create(v, device, dtype, out, 0); }
+int yh_create_cls(const yh_variant* v, int device, int dtype, yh_handle** out) { return create(v, device, dtype, out, 1); }
 
 void yh_destroy(yh_handle* h) {
     if (!h) return;
@@ -80,6 +85,7 @@ int yh_load_conv(yh_handle* h, int index, const float* weight, const float* bias
 int yh_num_anchors(const yh_handle* h, int height, int width, int* anchors) {
     return guarded([&] {
         yh::require(h && anchors, "null argument");
+        yh::require(h->net.task == 0, "yh_num_anchors: a classifier handle has no anchors", YH_ESTATE);
         yh::require(height > 0 && width > 0 && height % 32 == 0 && width % 32 == 0, "height/width must be multiples of 32");
         *anchors = yh::Net::anchor_off(3, height, width);
     });
@@ -105,6 +111,7 @@ static int forward(yh_handle* h, const void* x, int batch, int height, int width
     return guarded([&] {
         yh::require(h && x && y, "null argument");
         yh::require(batch > 0, "batch must be positive");
+        yh::require(h->net.task == 0, "yh_forward on a classifier handle (made by yh_create_cls): call yh_classify", YH_ESTATE);
         HIPCHECK(hipSetDevice(h->net.device));
         h->net.forward(x, batch, height, width, y, (hipStream_t)stream, x_u8);
     });
@@ -114,6 +121,17 @@ int yh_forward(yh_handle* h, const void* x, int batch, int height, int width, vo
 }
 int yh_forward_u8(yh_handle* h, const void* x, int batch, int height, int width, void* y, void* stream) {
     return forward(h, x, batch, height, width, y, stream, 1);
+}
+
+int yh_classify(yh_handle* h, const void* x, int x_u8, int batch, int height, int width, const int* count, float* probs,
+                float* logits, float* embed, void* stream) {
+    return guarded([&] {
+        yh::require(h && x && probs, "null argument");
+        yh::require(batch > 0, "batch must be positive");
+        yh::require(h->net.task == 1, "yh_classify on a detection handle (made by yh_create): call yh_forward", YH_ESTATE);
+        HIPCHECK(hipSetDevice(h->net.device));
+        h->net.classify(x, x_u8 != 0, batch, height, width, count, probs, logits, embed, (hipStream_t)stream);
+    });
 }
 
 // Launch units: unit i of a shape's plan is its i-th active op (one op per unit, never a level).

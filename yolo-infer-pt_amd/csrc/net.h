@@ -20,11 +20,12 @@ namespace yh {
 // ---------------------------------------------------------------- graph model
 enum ConvKind { CK_DENSE = 0, CK_FIRST = 1, CK_DW = 2, CK_PE = 3 };
 enum OpKind { OP_FIRST, OP_CONV, OP_DW, OP_SPPF, OP_ATTN, OP_DECODE, OP_HEADCLS, OP_BOXDFL, OP_CSP, OP_STEM2, OP_C3K,
-              OP_BOXCHAIN, OP_PWCHAIN };
+              OP_BOXCHAIN, OP_PWCHAIN, OP_CLSPOOL, OP_CLSHEAD, OP_CLSFC };
 const char* op_kind_name(OpKind k);
 enum OpClass { CL_CONV3 = 0, CL_CONV1 = 1, CL_FIRST = 2, CL_DW = 3, CL_SPPF = 4, CL_ATTN = 5, CL_DECODE = 6,
-               CL_HEADCLS = 7, CL_BOXDFL = 8, CL_CSP = 9, CL_C3K = 10, CL_BOXCHAIN = 11, CL_PWCHAIN = 12, CL_N = 13 };
+               CL_HEADCLS = 7, CL_BOXDFL = 8, CL_CSP = 9, CL_C3K = 10, CL_BOXCHAIN = 11, CL_PWCHAIN = 12, CL_CLS = 13, CL_N = 14 };
 
+// level < 0: one fp32 vector of C values per image (the classifier's embedding and logits)
 struct Tensor { int level; int C; };        // physical channels = pixel stride
 struct View { int t = -1; int coff = 0; int C = 0; };
 
@@ -89,6 +90,9 @@ struct Op {
     std::vector<View> pwl;          // prologue loads (global views)
     std::vector<int> pwl_lds;       // their LDS byte offsets
     int pwP = 0, pwLds = 0;
+    // OP_CLSPOOL: in[0] = the head conv's output, out = the embedding vector. OP_CLSHEAD: conv =
+    // head.conv, in[0] = its input, out = the embedding (alts: the conv op and the pool).
+    // OP_CLSFC: conv = head.linear, in[0] = the embedding, out = the logits vector
     std::string label;
 };
 
@@ -113,9 +117,12 @@ struct GraphKey {
 // the whole block would fit one launch (tested the same way), YH_CONV=<k> forces
 // candidate plan k of every 16-bit dense conv, YH_TUNE_LOG=1 prints the tuner's timings,
 // YH_C3K=0 keeps the C3k blocks as per-layer launches (compared bit for bit by the tests),
-// YH_HCLS_WIDE=0 keeps a 256-channel level's cls branch (v11_n 20x20) as per-layer launches.
+// YH_HCLS_WIDE=0 keeps a 256-channel level's cls branch (v11_n 20x20) as per-layer launches,
+// YH_CLSHEAD=1 runs a classifier's head.conv + cls_pool as one launch (cls_head; bit-identical, compared
+// by the tests; off by default because the two launches measured faster).
 struct Options {
     bool fuse = true, csp_tail = false, tune_log = false, c3k = true, hcls_wide = true, box_chain = false, pw_chain = true;
+    bool cls_head = false;
     int conv_force = -1;
     static Options from_env() {
         Options o;
@@ -125,6 +132,7 @@ struct Options {
         if (const char* e = getenv("YH_CSP_TAIL")) o.csp_tail = atoi(e) != 0;
         if (const char* e = getenv("YH_C3K")) o.c3k = atoi(e) != 0;
         if (const char* e = getenv("YH_HCLS_WIDE")) o.hcls_wide = atoi(e) != 0;
+        if (const char* e = getenv("YH_CLSHEAD")) o.cls_head = atoi(e) != 0;
         if (const char* e = getenv("YH_CONV")) o.conv_force = atoi(e);
         o.tune_log = getenv("YH_TUNE_LOG") != nullptr;
         return o;
@@ -133,13 +141,14 @@ struct Options {
 
 struct Net {
     yh_variant var;
+    int task = 0;   // 0: detection (yh_create), 1: classification (yh_create_cls)
     Options opt;
     int device, dtype, es;
     std::vector<Tensor> tensors;
     std::vector<ConvDesc> convs;
     std::vector<Op> ops;
     Workspace ws;
-    void** io_dev = nullptr;      // {x, y}
+    void** io_dev = nullptr;      // {x, y, probs, logits, embed, count} (the last four: classifier)
     void* zero_dev = nullptr;     // 256 zero bytes: source of padded conv taps
     bool use_graph = true;
     std::map<GraphKey, hipGraphExec_t> graphs;
@@ -173,6 +182,8 @@ struct Net {
 
     // ---------------------------------------------------------- net_build.cpp
     void build();
+    int build_backbone(int& b3, int& b4);
+    void build_cls();
     int tensor(int level, int C);
     View full(int t, int C = -1) const { return View{t, 0, C < 0 ? tensors[t].C : C}; }
     View slice(int t, int coff, int C) const;
@@ -216,7 +227,9 @@ struct Net {
     const char* mx_weights(int ci, const MxPlan& p, const MxShape& sh);
 
     // ---------------------------------------------------------- net_forward.cpp
+    size_t tensor_bytes(const Tensor& t, int B, int H, int W) const;
     size_t ws_bytes_for(int B, int H, int W, std::vector<size_t>* offs) const;
+    void check_shape(int B, int H, int W) const;
     void reserve(int B, int H, int W);
     char* ptr(const View& v) const { return (char*)ws.base + ws.off[v.t] + (size_t)v.coff * es; }
     int ldc(const View& v) const { return tensors[v.t].C; }
@@ -225,6 +238,9 @@ struct Net {
     void ensure_plan(int B, int H, int W);
     void run_ops(int B, int H, int W, hipStream_t s);
     void forward(const void* x, int B, int H, int W, void* y, hipStream_t s, int x_u8 = 0);
+    void classify(const void* x, int x_u8, int B, int H, int W, const int* count, float* probs, float* logits,
+                  float* embed, hipStream_t s);
+    void launch_plan(int B, int H, int W, hipStream_t s);
 
     // ---------------------------------------------------------- net_launch.cpp
     static int anchor_off(int l, int H, int W);
@@ -244,6 +260,9 @@ struct Net {
     PwChainArgs pw_chain_args(const Op& op, int B, int H, int W);
     CspArgs csp_args(size_t oi, int B, int H, int W, int& grid);
     C3kArgs c3k_args(const Op& op, int B, int H, int W);
+    ClsPoolArgs cls_pool_args(const Op& op, int B, int H, int W) const;
+    ClsHeadArgs cls_head_args(const Op& op, int B, int H, int W) const;
+    ClsFcArgs cls_fc_args(const Op& op, int B) const;
     int launch_mx_op(const Op& op, const MxPlan& pl, int B, int H, int W, hipStream_t s);
     void launch_op(size_t oi, int B, int H, int W, hipStream_t s);
     void ensure_tuned(int B, int H, int W, hipStream_t s);

@@ -188,12 +188,12 @@ void Net::psa(const std::string& p, View x, int ch, int n, View out, int level) 
     conv1(p + ".conv2", full(t), 2 * half, ch, ACT_SILU, out);
 }
 
-void Net::build() {
+// DarkNet (nn.py:151-189) up to net.p5.1, which both tasks share; returns that block's output
+// tensor, and the p3 / p4 outputs the detector's FPN reads.
+int Net::build_backbone(int& b3, int& b4) {
     const int* w = var.width;
     const int* d = var.depth;
     const bool c0 = var.csp[0] != 0, c1 = var.csp[1] != 0;
-    const int nc = var.num_classes;
-    // ---- DarkNet (nn.py:151-189)
     const int t2 = tensor(2, w[2]);
     if (fuse_stem(w[0], w[1], w[2])) {
         // stem + net.p2.0 in one launch: the stem output never reaches HBM
@@ -219,16 +219,74 @@ void Net::build() {
     csp("net.p2.1", {Seg{full(t2, w[2]), 0}}, {w[2]}, w[3], d[0], c0, 4, full(t2b, w[3]), 2);
     const int t3 = tensor(3, w[3]);
     conv3("net.p3.0", full(t2b, w[3]), w[3], w[3], 2, ACT_SILU, full(t3, w[3]));
-    const int b3 = tensor(3, w[4]);
+    b3 = tensor(3, w[4]);
     csp("net.p3.1", {Seg{full(t3, w[3]), 0}}, {w[3]}, w[4], d[1], c0, 4, full(b3, w[4]), 3);
     const int t4 = tensor(4, w[4]);
     conv3("net.p4.0", full(b3, w[4]), w[4], w[4], 2, ACT_SILU, full(t4, w[4]));
-    const int b4 = tensor(4, w[4]);
+    b4 = tensor(4, w[4]);
     csp("net.p4.1", {Seg{full(t4, w[4]), 0}}, {w[4]}, w[4], d[2], c1, 2, full(b4, w[4]), 4);
     const int t5 = tensor(5, w[5]);
     conv3("net.p5.0", full(b4, w[4]), w[4], w[5], 2, ACT_SILU, full(t5, w[5]));
     const int t5b = tensor(5, w[5]);
     csp("net.p5.1", {Seg{full(t5, w[5]), 0}}, {w[5]}, w[5], d[3], c1, 2, full(t5b, w[5]), 5);
+    return t5b;
+}
+
+// The classifier (nn.py YOLOCls): the backbone without the SPPF, C2PSA as net.p5.2, then the
+// Classify head: head.conv (1x1 to CLS_EMBED, SiLU), the mean over pixels, head.linear (described
+// as a 1x1 conv with bias, so weights load by name like every other layer) and the softmax.
+void Net::build_cls() {
+    const int* w = var.width;
+    const int nc = var.num_classes;
+    int b3, b4;
+    const int t5b = build_backbone(b3, b4);
+    const int t5c = tensor(5, w[5]);
+    psa("net.p5.2", full(t5b, w[5]), w[5], var.depth[4], full(t5c, w[5]), 5);
+    // per-layer path: the dense 1x1 conv writes a, cls_pool reduces it
+    const int ta = tensor(5, CLS_EMBED), te = tensor(-1, CLS_EMBED), tz = tensor(-1, nc);
+    const int conv_op = (int)ops.size();
+    // fp32 handle: this layer's output is held to one fp32 ulp of the fp64 conv (the parity tests),
+    // which SiLU in fp32 after the rounded K sum misses; its epilogue runs in fp64 (conv.hip)
+    conv1("head.conv", full(t5c, w[5]), w[5], CLS_EMBED, dtype == F32 ? ACT_SILU_F64 : ACT_SILU, full(ta, CLS_EMBED));
+    const int pool_op = (int)ops.size();
+    Op pool;
+    pool.kind = OP_CLSPOOL;
+    pool.label = "head.pool";
+    pool.in = {Seg{full(ta, CLS_EMBED), 0}};
+    pool.out = full(te);
+    ops.push_back(pool);
+    // 16-bit handles with YH_CLSHEAD=1: conv + pool as one launch (cls.hip cls_head) at shapes where
+    // an image's map fits a workgroup (Net::fused_fits); the default keeps the two launches, which
+    // measured faster
+    if (dtype != F32 && opt.fuse && opt.cls_head && cls_head_pmax(w[5]) > 0 && tensors[t5c].C == w[5]) {
+        Op hd;
+        hd.kind = OP_CLSHEAD;
+        hd.label = "head.conv+pool";
+        hd.conv = ops[conv_op].conv;
+        hd.in = {Seg{full(t5c, w[5]), 0}};
+        hd.out = full(te);
+        hd.alts = {conv_op, pool_op};
+        ops.push_back(hd);
+    }
+    Op fc;
+    fc.kind = OP_CLSFC;
+    fc.label = "head.linear";
+    fc.conv = new_dense_conv("head.linear", CLS_EMBED, nc, 1, 1, ACT_ID);
+    fc.in = {Seg{full(te), 0}};
+    fc.out = full(tz);
+    ops.push_back(fc);
+    finalize_convs();
+    fuse_pw_chains();
+}
+
+void Net::build() {
+    if (task == 1) { build_cls(); return; }
+    const int* w = var.width;
+    const int* d = var.depth;
+    const bool c0 = var.csp[0] != 0, c1 = var.csp[1] != 0;
+    const int nc = var.num_classes;
+    int b3, b4;
+    const int t5b = build_backbone(b3, b4);
     const int t5c = tensor(5, w[5]);
     sppf("net.p5.2", full(t5b, w[5]), w[5], w[5], full(t5c, w[5]), 5);
     // R = [h5(p4) | p5] (h6 input); backbone p5 is written into its slice 1

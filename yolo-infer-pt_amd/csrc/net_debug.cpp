@@ -9,8 +9,9 @@ namespace yh {
 static const struct { const char* name; OpClass cls; } KINDS[] = {
     {"stem", CL_FIRST}, {"conv", CL_CONV1}, {"dwconv", CL_DW}, {"sppf", CL_SPPF}, {"attention", CL_ATTN},
     {"decode", CL_DECODE}, {"head_cls", CL_HEADCLS}, {"box_dfl", CL_BOXDFL}, {"c3k2", CL_CSP}, {"stem_fused", CL_FIRST},
-    {"c3k", CL_C3K}, {"box_chain", CL_BOXCHAIN}, {"pw_chain", CL_PWCHAIN}};
-static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == OP_PWCHAIN + 1, "one entry per OpKind");
+    {"c3k", CL_C3K}, {"box_chain", CL_BOXCHAIN}, {"pw_chain", CL_PWCHAIN}, {"cls_pool", CL_CLS}, {"cls_head", CL_CLS},
+    {"cls_fc", CL_CLS}};
+static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == OP_CLSFC + 1, "one entry per OpKind");
 const char* op_kind_name(OpKind k) { return KINDS[k].name; }
 OpClass Net::op_class(const Op& op) const {
     return op.kind == OP_CONV && convs[op.conv].k == 3 ? CL_CONV3 : KINDS[op.kind].cls;
@@ -134,6 +135,25 @@ void Net::op_cost(const Op& op, int B, int H, int W, double& bytes, double& flop
             }
             break;
         }
+        case OP_CLSPOOL:
+            // the activations read once, the fp32 embedding written once
+            bytes = px(5) * op.out.C * es + (double)B * op.out.C * 4;
+            flops = px(5) * op.out.C;
+            break;
+        case OP_CLSHEAD: {
+            // the feature map read once, the fp32 embedding written once, the weights once
+            const ConvDesc& d = convs[op.conv];
+            bytes = px(5) * d.cin * es + (double)B * d.cout * 4 + (double)d.cout * d.cin * es + d.cout * 4.0;
+            flops = 2.0 * px(5) * d.cout * d.cin + px(5) * d.cout;
+            break;
+        }
+        case OP_CLSFC: {
+            // the embedding read once; logits, probs and the embedding copy written once; weights once
+            const ConvDesc& d = convs[op.conv];
+            bytes = (double)B * d.cin * 4 * 2 + 2.0 * B * d.cout * 4 + (double)d.cout * d.cin * es + d.cout * 4.0;
+            flops = 2.0 * B * d.cout * d.cin + 4.0 * B * d.cout;
+            break;
+        }
         case OP_BOXDFL: {
             // the box.l.1 outputs read once, 4 box rows written, weights once per level
             for (int l = 0; l < 3; ++l) {
@@ -187,6 +207,18 @@ std::vector<Net::Operand> Net::operands(const Op& op) const {
         case OP_DECODE:
             for (int l = 0; l < 3; ++l) add("L" + std::to_string(l), op.lvl[l], 0, 64 + var.num_classes);
             break;
+        case OP_CLSPOOL:   // a (the head conv's output), e (fp32)
+            add("a", op.in[0].v, 0, op.in[0].v.C);
+            add("e", op.out, 0, op.out.C);
+            break;
+        case OP_CLSHEAD:
+            add("in0", op.in[0].v, 0, op.in[0].v.C);
+            add("e", op.out, 0, op.out.C);
+            break;
+        case OP_CLSFC:     // e and the logits z (both fp32)
+            add("e", op.in[0].v, 0, op.in[0].v.C);
+            add("z", op.out, 0, var.num_classes);
+            break;
         case OP_PWCHAIN:
             // per stage s<k>.in<i> / s<k>.res (inputs, read before the chain runs), then the
             // outputs no later stage overwrites (s<k>.out)
@@ -221,7 +253,7 @@ bool Net::pw_final(const Op& op, int k) const {
 std::vector<int> Net::op_convs(const Op& op) const {
     std::vector<int> r;
     switch (op.kind) {
-        case OP_CONV: case OP_FIRST: case OP_DW: case OP_ATTN: return {op.conv};
+        case OP_CONV: case OP_FIRST: case OP_DW: case OP_ATTN: case OP_CLSHEAD: case OP_CLSFC: return {op.conv};
         case OP_STEM2: return {op.conv, op.cs[0]};
         case OP_CSP: return {op.cs[0], op.cs[1], op.cs[2], op.cs[3]};
         case OP_C3K: return std::vector<int>(op.ck, op.ck + 7);
@@ -237,7 +269,7 @@ std::vector<int> Net::op_convs(const Op& op) const {
         case OP_PWCHAIN:
             for (int k : op.alts) r.push_back(ops[k].conv);
             break;
-        case OP_SPPF: case OP_DECODE: break;
+        case OP_SPPF: case OP_DECODE: case OP_CLSPOOL: break;
     }
     return r;
 }
@@ -263,10 +295,13 @@ std::string Net::op_desc(int oi, int B, int H, int W) const {
     s += "], \"operands\": [";
     const std::vector<Operand> od = operands(op);
     for (size_t i = 0; i < od.size(); ++i) {
+        // a per-image fp32 vector (level < 0) reads as a 1 x 1 map with "f32": 1
         const int lv = tensors[od[i].v.t].level;
-        s += std::string(i ? ", " : "") + "{\"role\": \"" + od[i].role + "\", \"H\": " + std::to_string(H >> lv) +
-             ", \"W\": " + std::to_string(W >> lv) + ", \"C\": " + std::to_string(od[i].v.C) + ", \"logical\": " +
-             std::to_string(od[i].logical) + ", \"up\": " + std::to_string(od[i].up) + "}";
+        const int oh = lv < 0 ? 1 : H >> lv, ow = lv < 0 ? 1 : W >> lv;
+        s += std::string(i ? ", " : "") + "{\"role\": \"" + od[i].role + "\", \"H\": " + std::to_string(oh) +
+             ", \"W\": " + std::to_string(ow) + ", \"C\": " + std::to_string(od[i].v.C) + ", \"logical\": " +
+             std::to_string(od[i].logical) + ", \"up\": " + std::to_string(od[i].up) + ", \"f32\": " +
+             std::to_string(lv < 0 ? 1 : 0) + "}";
     }
     s += "]";
     if (op.kind == OP_PWCHAIN) {
@@ -300,13 +335,15 @@ std::string Net::op_desc(int oi, int B, int H, int W) const {
 }
 // the active ops in [first, last) of the forward at (B, H, W), launched eagerly on s
 void Net::debug_run(const void* x, int x_u8, int B, int H, int W, void* y, int first, int last, hipStream_t s) {
+    // a classifier handle's y is its (B, num_classes) fp32 probs; no logits / embed copies, no count
     in_u8 = x_u8;
     for (auto& d : convs) require(d.loaded, "weights of " + d.name + " not loaded", YH_ESTATE);
     require(ws.base && ws.B == B && ws.H == H && ws.W == W, "yh_debug_run_ops: run yh_forward at this shape first",
             YH_ESTATE);
     require(first >= 0 && first <= last && last <= (int)ops.size(), "op range out of bounds");
     HIPCHECK(hipSetDevice(device));
-    require(launch_set_io(io_dev, x, y, s) == 0, "set_io launch failed", YH_EHIP);
+    const int rc = task == 1 ? launch_set_io_cls(io_dev, x, (float*)y, nullptr, nullptr, nullptr, s) : launch_set_io(io_dev, x, y, s);
+    require(rc == 0, "set_io launch failed", YH_EHIP);
     ensure_plan(B, H, W);
     ensure_tuned(B, H, W, s);
     for (int i = first; i < last; ++i)
@@ -320,7 +357,8 @@ void Net::debug_operand(int oi, int slot, void* dst, size_t dst_bytes, hipStream
     require(ws.base != nullptr, "no workspace yet", YH_ESTATE);
     const View& v = od[slot].v;
     const int lv = tensors[v.t].level;
-    const size_t rows = (size_t)ws.B * (ws.H >> lv) * (ws.W >> lv);
+    const size_t rows = lv < 0 ? (size_t)ws.B : (size_t)ws.B * (ws.H >> lv) * (ws.W >> lv);
+    const int es = lv < 0 ? 4 : this->es;   // per-image vectors are fp32 on every handle
     // the caller sizes dst from a desc made at some (batch, H, W): a desc of another shape
     // (or a later reserve() at a larger one) must not turn into an out-of-bounds write
     require(dst_bytes == rows * (size_t)v.C * es, "yh_debug_operand: dst size " + std::to_string(dst_bytes) +

@@ -4,15 +4,19 @@
 
 namespace yh {
 
-// Tensors are laid out coarsest level first.
+size_t Net::tensor_bytes(const Tensor& t, int B, int H, int W) const {
+    if (t.level < 0) return (size_t)B * t.C * 4;   // one fp32 vector per image
+    return (size_t)B * (H >> t.level) * (W >> t.level) * t.C * es;
+}
+// Tensors are laid out coarsest level first (a classifier's per-image vectors after the maps).
 size_t Net::ws_bytes_for(int B, int H, int W, std::vector<size_t>* offs) const {
     size_t total = 0;
     if (offs) offs->assign(tensors.size(), 0);
-    for (int lvl = 5; lvl >= 0; --lvl)
+    for (int lvl = 5; lvl >= -1; --lvl)
         for (size_t i = 0; i < tensors.size(); ++i) {
             const Tensor& t = tensors[i];
             if (t.level != lvl) continue;
-            const size_t b = (size_t)B * (H >> t.level) * (W >> t.level) * t.C * es;
+            const size_t b = tensor_bytes(t, B, H, W);
             if (offs) (*offs)[i] = total;
             total += (b + 255) & ~(size_t)255;
         }
@@ -25,6 +29,7 @@ void Net::reserve(int B, int H, int W) {
     for (const Op& op : ops)
         require(op.kind != OP_STEM2 || stem2_size_ok(H, W),
                 "input image too large for the fused stem (3 * height * width must be below 2^32); set YH_FUSE=0");
+    if (task == 1) check_shape(B, H, W);
     if (ws.base && ws.B == B && ws.H == H && ws.W == W) return;
     std::vector<size_t> offs;
     const size_t need = ws_bytes_for(B, H, W, &offs);
@@ -42,6 +47,22 @@ void Net::reserve(int B, int H, int W) {
     ws.B = B;
     ws.H = H;
     ws.W = W;
+}
+
+// A classifier handle meets maps down to 1 x 1 (32 x 32 crops): every op without a per-layer
+// alternative must have a plan at the shape, or the shape is refused here, before any launch.
+void Net::check_shape(int B, int H, int W) const {
+    for (const Op& op : ops) {
+        if (op.kind == OP_CSP) {
+            const int lv = tensors[op.out.t].level;
+            int th, tw;
+            require(csp_tile(op.cs[0] >= 0 ? convs[op.cs[0]].cin / 16 : 0, convs[op.cs[1]].cin / 16, convs[op.cs[3]].cout / 32,
+                             B, H >> lv, W >> lv, 256, th, tw),
+                    op.label + ": no tile for a " + std::to_string(H >> lv) + " x " + std::to_string(W >> lv) + " map");
+        }
+        // cls_pool's grid has one row of workgroups per image
+        if (op.kind == OP_CLSPOOL) require(B <= 65535, "classifier batch above 65535");
+    }
 }
 
 void Net::drop_graphs() {
@@ -97,6 +118,10 @@ bool Net::fused_fits(const Op& op, int B, int H, int W) const {
             const int lv = tensors[op.out.t].level;
             return c3k_lds(H >> lv, W >> lv, convs[op.ck[0]].cout) > 0;
         }
+        case OP_CLSHEAD:
+            // where a workgroup holds at least one whole image's map (cls_head_group; a function
+            // of the map and the channels only, never of the batch)
+            return cls_head_group(convs[op.conv].K, (H >> 5) * (W >> 5)) > 0;
         default: return true;
     }
 }
@@ -133,6 +158,23 @@ void Net::forward(const void* x, int B, int H, int W, void* y, hipStream_t s, in
     reserve(B, H, W);
     HIPCHECK(hipSetDevice(device));
     require(launch_set_io(io_dev, x, y, s) == 0, "set_io launch failed", YH_EHIP);
+    launch_plan(B, H, W, s);
+}
+
+// The classifier's forward (yh_classify): the same plan / tuner / graph machinery; the outputs and
+// the count are reached through io_dev, so a replayed graph serves any set of pointers.
+void Net::classify(const void* x, int x_u8, int B, int H, int W, const int* count, float* probs, float* logits,
+                   float* embed, hipStream_t s) {
+    in_u8 = x_u8;
+    for (auto& d : convs) require(d.loaded, "weights of " + d.name + " not loaded", YH_ESTATE);
+    reserve(B, H, W);
+    HIPCHECK(hipSetDevice(device));
+    require(launch_set_io_cls(io_dev, x, probs, logits, embed, count, s) == 0, "set_io launch failed", YH_EHIP);
+    launch_plan(B, H, W, s);
+}
+
+// the plan of (B, H, W) on stream s: profiled, eager or as one replayed graph
+void Net::launch_plan(int B, int H, int W, hipStream_t s) {
     ensure_plan(B, H, W);
     ensure_tuned(B, H, W, s);
     if (profile) {   // HIP events around every launch, on the caller's stream

@@ -47,6 +47,7 @@ void Net::conv_args(const Op& op, int B, int H, int W, ConvArgs& a, int& BM, int
     a.Cout = d.cout_p;
     a.act = d.act;
     pick_tile(a.M, a.Cout, BM, BN);
+    if (a.act == ACT_SILU_F64 && BM > 128) BM = 128;   // conv_gemm's fp64-epilogue instances (conv.hip)
     a.gm = (a.M + BM - 1) / BM;
     a.gn = (a.Cout + BN - 1) / BN;
     a.zero = zero_dev;
@@ -582,6 +583,45 @@ C3kArgs Net::c3k_args(const Op& op, int B, int H, int W) {
     return a;
 }
 
+// ---------------------------------------------------------- classifier head
+ClsPoolArgs Net::cls_pool_args(const Op& op, int B, int H, int W) const {
+    ClsPoolArgs a{};
+    const View& v = op.in[0].v;
+    a.a = ptr(v); a.lda = ldc(v);
+    a.B = B; a.HW = (H >> 5) * (W >> 5); a.C = op.out.C;
+    a.inv = (float)(1.0 / a.HW);
+    a.e = (float*)ptr(op.out);
+    return a;
+}
+ClsHeadArgs Net::cls_head_args(const Op& op, int B, int H, int W) const {
+    const ConvDesc& d = convs[op.conv];
+    ClsHeadArgs a{};
+    const View& v = op.in[0].v;
+    a.x = ptr(v); a.ldx = ldc(v);
+    a.B = B; a.HW = (H >> 5) * (W >> 5); a.K = d.K; a.N = d.cout;
+    a.G = cls_head_group(a.K, a.HW);
+    require(a.G > 0 && v.C == d.K && d.Kp == d.K, op.label + ": no cls_head plan at this shape");
+    auto itw = d.mx_w.find("pwfrag");
+    require(itw != d.mx_w.end(), "cls_head: no fragment-ordered weights for " + d.name);
+    a.w = itw->second; a.wld = d.Kp;
+    a.bias = d.b_dev;
+    a.act = d.act;
+    a.inv = (float)(1.0 / a.HW);
+    a.e = (float*)ptr(op.out);
+    return a;
+}
+ClsFcArgs Net::cls_fc_args(const Op& op, int B) const {
+    const ConvDesc& d = convs[op.conv];
+    ClsFcArgs a{};
+    a.e = (const float*)ptr(op.in[0].v);
+    a.w = d.w_dev; a.wld = d.Kp;
+    a.bias = d.b_dev;
+    a.B = B; a.nc = d.cout; a.K = d.cin;
+    a.z = (float*)ptr(op.out); a.ldz = ldc(op.out);
+    a.io = (const void* const*)io_dev;
+    return a;
+}
+
 void Net::launch_op(size_t oi, int B, int H, int W, hipStream_t s) {
     const Op& op = ops[oi];
     int rc = 0;
@@ -615,6 +655,9 @@ void Net::launch_op(size_t oi, int B, int H, int W, hipStream_t s) {
             break;
         }
         case OP_C3K: rc = launch_c3k(dtype, c3k_args(op, B, H, W), s); break;
+        case OP_CLSPOOL: rc = launch_cls_pool(dtype, cls_pool_args(op, B, H, W), s); break;
+        case OP_CLSHEAD: rc = launch_cls_head(dtype, cls_head_args(op, B, H, W), s); break;
+        case OP_CLSFC: rc = launch_cls_fc(dtype, cls_fc_args(op, B), s); break;
     }
     if (rc != 0) throw Fail(YH_EHIP, "launch of " + op.label + " failed: " + hipGetErrorString((hipError_t)rc));
 }

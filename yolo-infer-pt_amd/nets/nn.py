@@ -18,6 +18,9 @@ Reference map (file:line into /root/reference):
   fuse_conv 8-25, Conv 28-39, Residual 42-49, CSPModule 52-63, CSP 66-80,
   SPP 83-94, Attention 97-123, PSABlock 126-136, PSA 139-148, DarkNet 151-189,
   DarkFPN 192-209, DFL 212-225, Head 228-279, YOLO 282-305, yolo_v11_* 308-347.
+
+Not in the reference: `DarkNet(..., spp=False)`, `Classify`, `YOLOCls` and `yolo_v11_cls_*`, the
+YOLO11-cls classifier that runs as a second stage on crops (yolo_hip.Classifier, yh_classify).
 """
 import math
 
@@ -27,7 +30,8 @@ from utils.util import make_anchors
 
 __all__ = ["fuse_conv", "Conv", "Residual", "CSPModule", "CSP", "SPP", "Attention", "PSABlock", "PSA",
            "DarkNet", "DarkFPN", "DFL", "Head", "YOLO", "yolo_v11_n", "yolo_v11_t", "yolo_v11_s",
-           "yolo_v11_m", "yolo_v11_l", "yolo_v11_x"]
+           "yolo_v11_m", "yolo_v11_l", "yolo_v11_x", "Classify", "YOLOCls", "yolo_v11_cls_n", "yolo_v11_cls_t",
+           "yolo_v11_cls_s", "yolo_v11_cls_m", "yolo_v11_cls_l", "yolo_v11_cls_x"]
 
 _SILU = torch.nn.SiLU
 _ID = torch.nn.Identity
@@ -187,17 +191,23 @@ def _down(cin, cout):
 
 
 class DarkNet(torch.nn.Module):
-    """Backbone: stem + four stride-2 stages; returns (p3, p4, p5)."""
+    """Backbone: stem + four stride-2 stages; returns (p3, p4, p5).
 
-    def __init__(self, width, depth, csp):
+    spp=False (the classifier's backbone, Ultralytics' yolo11-cls.yaml) leaves the SPPF out:
+    p5 = (down, C3k2, C2PSA)."""
+
+    def __init__(self, width, depth, csp, spp=True):
         super().__init__()
         w, d = width, depth
         self.p1 = torch.nn.Sequential(_down(w[0], w[1]))
         self.p2 = torch.nn.Sequential(_down(w[1], w[2]), CSP(w[2], w[3], d[0], csp[0], r=4))
         self.p3 = torch.nn.Sequential(_down(w[3], w[3]), CSP(w[3], w[4], d[1], csp[0], r=4))
         self.p4 = torch.nn.Sequential(_down(w[4], w[4]), CSP(w[4], w[4], d[2], csp[1], r=2))
-        self.p5 = torch.nn.Sequential(_down(w[4], w[5]), CSP(w[5], w[5], d[3], csp[1], r=2),
-                                      SPP(w[5], w[5]), PSA(w[5], d[4]))
+        if spp:
+            self.p5 = torch.nn.Sequential(_down(w[4], w[5]), CSP(w[5], w[5], d[3], csp[1], r=2),
+                                          SPP(w[5], w[5]), PSA(w[5], d[4]))
+        else:
+            self.p5 = torch.nn.Sequential(_down(w[4], w[5]), CSP(w[5], w[5], d[3], csp[1], r=2), PSA(w[5], d[4]))
 
     def forward(self, x):
         p3 = self.p3(self.p2(self.p1(x)))
@@ -324,6 +334,56 @@ class YOLO(torch.nn.Module):
             self._yh_arch = _infer_arch(self)
 
 
+class Classify(torch.nn.Module):
+    """Ultralytics' Classify head: 1x1 conv to `hidden` channels (BN, SiLU), global average pool,
+    linear; softmax probabilities in eval mode, logits in training."""
+
+    def __init__(self, cin, nc, hidden=1280):
+        super().__init__()
+        self.nc = nc
+        self.conv = Conv(cin, hidden, _SILU(), k=1)
+        self.linear = torch.nn.Linear(hidden, nc)
+
+    def features(self, x):
+        e = self.conv(x).mean((2, 3))
+        z = self.linear(e)
+        return z.softmax(1), z, e
+
+    def forward(self, x):
+        p, z, _ = self.features(x)
+        return z if self.training else p
+
+
+class YOLOCls(torch.nn.Module):
+    """YOLO11-cls: the detector's backbone without the SPPF, then Classify on the last feature map.
+    Inputs are RGB in [0, 1] (x / 255, no mean / std), height and width multiples of 32."""
+
+    def __init__(self, width, depth, csp, num_classes):
+        super().__init__()
+        self.net = DarkNet(width, depth, csp, spp=False)
+        self.head = Classify(width[5], num_classes)
+        self._yh_arch = (tuple(width), tuple(depth), tuple(bool(c) for c in csp), int(num_classes))
+
+    def features(self, x):
+        """(probs, logits, embed): (B, nc), (B, nc), (B, 1280); float32 on the HIP path."""
+        if x.is_cuda and not self.training:
+            return _hip_classify(self, x)
+        return self.head.features(self.net(x)[2])
+
+    def forward(self, x):
+        if x.is_cuda and not self.training:
+            return _hip_classify(self, x, probs_only=True)[0].to(x.dtype)
+        return self.head(self.net(x)[2])
+
+    def fuse(self):
+        return YOLO.fuse(self)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        if "_yh_arch" not in self.__dict__:
+            self._yh_arch = _infer_arch(self)
+
+
 def _infer_arch(model):
     net = model.net
     w1 = net.p1[0].conv.out_channels
@@ -368,8 +428,59 @@ def _hip_forward(model, x):
     return eng.forward(x)
 
 
+def _hip_engine(model, x, task):
+    from yolo_hip.engine import Engine
+
+    engines = model.__dict__.setdefault("_yh_engines", {})
+    key = (x.device.index if x.device.index is not None else torch.cuda.current_device(), x.dtype)
+    sig = _weights_signature(model)
+    eng = engines.get(key)
+    if eng is None:
+        width, depth, csp, nc = model._yh_arch
+        eng = Engine(width, depth, csp, nc, torch.device("cuda", key[0]), x.dtype, task=task)
+        engines[key] = eng
+    if eng.signature != sig:
+        eng.load_module(model)
+        eng.signature = sig
+    return eng
+
+
+def _hip_classify(model, x, probs_only=False):
+    """Eval forward of a YOLOCls on the HIP path (include/yolo_hip.h yh_classify)."""
+    eng = _hip_engine(model, x, "classify")
+    return eng.classify(x, logits=not probs_only, embed=not probs_only)
+
+
 def _build(width, depth, csp, num_classes):
     return YOLO(list(width), list(depth), list(csp), num_classes)
+
+
+def _build_cls(width, depth, csp, num_classes):
+    return YOLOCls(list(width), list(depth), list(csp), num_classes)
+
+
+def yolo_v11_cls_n(num_classes: int = 1000):
+    return _build_cls((3, 16, 32, 64, 128, 256), (1,) * 6, (False, True), num_classes)
+
+
+def yolo_v11_cls_t(num_classes: int = 1000):
+    return _build_cls((3, 24, 48, 96, 192, 384), (1,) * 6, (False, True), num_classes)
+
+
+def yolo_v11_cls_s(num_classes: int = 1000):
+    return _build_cls((3, 32, 64, 128, 256, 512), (1,) * 6, (False, True), num_classes)
+
+
+def yolo_v11_cls_m(num_classes: int = 1000):
+    return _build_cls((3, 64, 128, 256, 512, 512), (1,) * 6, (True, True), num_classes)
+
+
+def yolo_v11_cls_l(num_classes: int = 1000):
+    return _build_cls((3, 64, 128, 256, 512, 512), (2,) * 6, (True, True), num_classes)
+
+
+def yolo_v11_cls_x(num_classes: int = 1000):
+    return _build_cls((3, 96, 192, 384, 768, 768), (2,) * 6, (True, True), num_classes)
 
 
 def yolo_v11_n(num_classes: int = 80):

@@ -49,6 +49,9 @@ _PROTOS = {
     "yh_abi_version": (c_int, []),
     "yh_last_error": (c_char_p, []),
     "yh_create": (c_int, [POINTER(YhVariant), c_int, c_int, POINTER(c_void_p)]),
+    "yh_create_cls": (c_int, [POINTER(YhVariant), c_int, c_int, POINTER(c_void_p)]),
+    "yh_classify": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p]),
     "yh_destroy": (None, [c_void_p]),
     "yh_conv_count": (c_int, [c_void_p]),
     "yh_conv_info": (c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_int), POINTER(c_int),

@@ -17,7 +17,8 @@ from ._lib import YhVariant, check, lib
 _DTYPES = {torch.float32: _lib.YH_F32, torch.float16: _lib.YH_F16, torch.bfloat16: _lib.YH_BF16}
 
 OP_CLASSES = ("conv3x3", "conv1x1", "stem", "dwconv", "sppf", "attention", "decode", "head_cls", "box_dfl", "c3k2",
-              "c3k", "box_chain", "pw_chain")
+              "c3k", "box_chain", "pw_chain", "cls")
+CLS_EMBED = 1280   # YH_CLS_EMBED
 
 
 def dtype_code(dtype):
@@ -31,9 +32,15 @@ def _stream_ptr(device):
 
 
 class Engine:
-    """HIP inference engine for one YOLOv11 variant on one device in one dtype."""
+    """HIP inference engine for one YOLOv11 variant on one device in one dtype.
 
-    def __init__(self, width, depth, csp, num_classes, device, dtype):
+    task="detect" (default) is the detector (nets.nn.YOLO: forward), task="classify" the
+    classifier over crops (nets.nn.YOLOCls: classify)."""
+
+    def __init__(self, width, depth, csp, num_classes, device, dtype, task="detect"):
+        if task not in ("detect", "classify"):
+            raise ValueError(f"yolo_hip.Engine: task must be 'detect' or 'classify', got {task!r}")
+        self.task = task
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError("yolo_hip.Engine needs a cuda (HIP) device")
@@ -48,7 +55,8 @@ class Engine:
         v.csp[0], v.csp[1] = int(bool(csp[0])), int(bool(csp[1]))
         v.num_classes = self.num_classes
         h = c_void_p()
-        check(lib().yh_create(byref(v), self.index, dtype_code(dtype), byref(h)), "create")
+        create = lib().yh_create_cls if task == "classify" else lib().yh_create
+        check(create(byref(v), self.index, dtype_code(dtype), byref(h)), "create")
         self._h = h
         self.convs = []
         n = lib().yh_conv_count(h)
@@ -77,6 +85,8 @@ class Engine:
             if not isinstance(conv, torch.nn.Conv2d):  # plain nn.Conv2d (head outputs)
                 conv, norm = mod, None
             w = conv.weight.detach()
+            if w.dim() == 2:   # torch.nn.Linear (the classifier's head.linear): a 1x1 conv with bias
+                w = w[:, :, None, None]
             if tuple(w.shape) != (cout, cpg, k, k):
                 raise ValueError(f"yolo_hip: {name}.weight has shape {tuple(w.shape)}, "
                                  f"expected {(cout, cpg, k, k)}")
@@ -95,6 +105,8 @@ class Engine:
                                sd[f"{name}.norm.running_mean"], sd[f"{name}.norm.running_var"], 1e-3)
             else:
                 w, b, norm = sd[f"{name}.weight"], sd.get(f"{name}.bias"), None
+            if w.dim() == 2:
+                w = w[:, :, None, None]
             if tuple(w.shape) != (cout, cpg, k, k):
                 raise ValueError(f"yolo_hip: {name} weight shape {tuple(w.shape)} != {(cout, cpg, k, k)}")
             self._load(idx, w, b, norm)
@@ -144,6 +156,44 @@ class Engine:
         check(fwd(self._h, c_void_p(x.data_ptr()), B, H, W, c_void_p(out.data_ptr()), _stream_ptr(x.device)),
               "forward")
         return out
+
+    def classify(self, x, count=None, logits=False, embed=False, out=None):
+        """x: (B, 3, H, W) cuda tensor, engine dtype or uint8 (RGB; / 255 runs inside the stem) ->
+        (probs (B, nc), logits (B, nc) or None, embed (B, 1280) or None), all float32.
+
+        count: optional int32 cuda tensor of one element: rows at or beyond clamp(count, 0, B) are
+        zero in every output (the rows are still computed; nothing is read on the host).
+        out: optional (probs, logits, embed) tensors to write into (None for an output not asked for).
+        Asynchronous on the current stream."""
+        if self.task != "classify":
+            raise RuntimeError("yolo_hip: classify() needs an Engine made with task='classify'")
+        if not x.is_cuda or x.device.index != self.index:
+            raise ValueError(f"yolo_hip: input must live on cuda:{self.index}")
+        if x.dtype != self.dtype and x.dtype != torch.uint8:
+            raise TypeError(f"yolo_hip: input dtype {x.dtype} is neither the engine dtype {self.dtype} nor uint8")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"yolo_hip: expected (B, 3, H, W), got {tuple(x.shape)}")
+        x = x.contiguous()
+        B, _, H, W = x.shape
+        if count is not None and (not count.is_cuda or count.device.index != self.index or count.dtype != torch.int32
+                                  or count.numel() != 1):
+            raise ValueError("yolo_hip: count must be one int32 on the engine's device")
+        po, lo, eo = out if out is not None else (None, None, None)
+        shapes = ((B, self.num_classes), (B, self.num_classes), (B, CLS_EMBED))
+        res = []
+        for want, t, shp in zip((True, logits, embed), (po, lo, eo), shapes):
+            if not want:
+                res.append(None)
+                continue
+            if t is None:
+                t = torch.empty(shp, dtype=torch.float32, device=x.device)
+            elif (tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous()):
+                raise ValueError(f"yolo_hip: out tensors must be contiguous float32 {shp} on the device")
+            res.append(t)
+        ptr = lambda t: c_void_p(t.data_ptr()) if t is not None else None
+        check(lib().yh_classify(self._h, c_void_p(x.data_ptr()), int(x.dtype == torch.uint8), B, H, W, ptr(count),
+                                ptr(res[0]), ptr(res[1]), ptr(res[2]), _stream_ptr(x.device)), "classify")
+        return tuple(res)
 
     def reserve(self, batch, height, width):
         check(lib().yh_reserve(self._h, int(batch), int(height), int(width)), "reserve")
@@ -213,9 +263,11 @@ class Engine:
               "debug_run")
 
     def debug_operand(self, index, slot, batch, desc):
-        """Operand `slot` of op `index` as a dense (batch, H, W, C) tensor of the engine dtype."""
+        """Operand `slot` of op `index` as a dense (batch, H, W, C) tensor of the engine dtype
+        (float32 for a classifier's per-image vectors, "f32": 1 in the desc)."""
         o = desc["operands"][slot]
-        out = torch.empty((batch, o["H"], o["W"], o["C"]), dtype=self.dtype, device=self.device)
+        dt = torch.float32 if o.get("f32") else self.dtype
+        out = torch.empty((batch, o["H"], o["W"], o["C"]), dtype=dt, device=self.device)
         check(lib().yh_debug_operand(self._h, int(index), int(slot), c_void_p(out.data_ptr()),
                                      out.numel() * out.element_size(), _stream_ptr(self.device)), "debug_operand")
         return out
