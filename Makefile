@@ -16,7 +16,7 @@ NET := engine net_build net_weights net_forward net_launch net_debug
 # handle-free host code compiled as HIP
 HOSTHIP := post_abi nms_host
 # kernels; the NOFMA ones promise bit-exact arithmetic against host code: no FMA contraction
-KERNELS := conv misc conv_mx conv_rw head c3k2 c3k boxc pwchain cls
+KERNELS := conv misc conv_mx conv_rw head c3k2 c3k pwchain cls
 KERNELS_NOFMA := preprocess nms match merge track
 # HIP-free translation units: plain C++, no device pass, no FMA contraction
 HOSTCXX := match_host merge_host track_host

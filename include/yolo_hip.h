@@ -503,8 +503,8 @@ int yh_op_count(const yh_handle* h);
 /* Describe op `index` for an input of (batch, height, width): label (module
  * path), class (0 dense 3x3 conv, 1 dense 1x1 conv, 2 stem conv, 3 depthwise,
  * 4 SPPF pools, 5 PSA attention, 6 head decode, 7 fused head cls branch,
- * 8 fused box tail with DFL, 9 fused C3k2 block, 10 fused C3k block, 11 fused box branch of all
- * levels, 12 pointwise chain, 13 classifier head: pool, fused conv + pool, linear + softmax),
+ * 8 fused box tail with DFL, 9 fused C3k2 block, 10 fused C3k block, 11 unused (no op reports it;
+ * the later numbers keep their values), 12 pointwise chain, 13 classifier head: pool, fused conv + pool, linear + softmax),
  * algorithmic bytes (each
  * operand read once, each output written once, handle dtype) and FLOPs per
  * call, accumulated profiled milliseconds and call count. */

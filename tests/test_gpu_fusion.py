@@ -271,30 +271,6 @@ def test_c3k_row_bands_equal_per_layer_launches(gpu, bands):
     assert torch.equal(yf, yp), (yf.float() - yp.float()).abs().max().item()
 
 
-@pytest.mark.parametrize("variant,dtype,batch,h,w", [("n", torch.bfloat16, 4, 640, 640), ("n", torch.float16, 3, 96, 160),
-                                                     ("n", torch.bfloat16, 2, 608, 480), ("n", torch.bfloat16, 1, 1280, 1280),
-                                                     ("s", torch.float16, 2, 384, 640), ("m", torch.bfloat16, 1, 320, 320)])
-def test_box_chain_equals_per_layer_launches(gpu, variant, dtype, batch, h, w):
-    """boxc.hip (opt-in, YH_BOXCHAIN=1): the box branch of all three levels (box.l.0 3x3 -> box.l.1 3x3
-    -> box.l.2 1x1 + DFL + anchors + dist2bbox) in one launch, the 64-channel intermediates in LDS, is
-    bit-identical to the seven per-layer launches (YH_BOXCHAIN=0): whole and partial tiles, level inputs of 64 / 128 / 256
-    (n) and 128 / 256 / 512 (s) channels, K-split (mx_kchunks: 640, 40x40 / 20x20 levels) and
-    unsplit box.l.0 shapes (1280: 80x80 / 40x40), an anchor count that is not a multiple of 8."""
-    model = make_model(variant)
-    x = synth.synth_scenes(batch, h, w, seed=43).to(gpu, dtype)
-    fused = _engine(model, dtype, gpu, True, YH_BOXCHAIN="1")   # opt-in (slower than the per-layer launches)
-    plain = _engine(model, dtype, gpu, True, YH_BOXCHAIN="0")
-    yf = fused.forward(x).clone()
-    yp = plain.forward(x).clone()
-    lf = [u["label"] for u in fused.units(batch, h, w)]
-    lp = [u["label"] for u in plain.units(batch, h, w)]
-    assert "head.box" in lf and "head.box_dfl" not in lf and not any(l.startswith("head.box.") for l in lf), lf
-    assert "head.box" not in lp and "head.box_dfl" in lp
-    assert len(lp) - len(lf) == 6
-    assert torch.isfinite(yf.float()).all()
-    assert torch.equal(yf, yp), (yf.float() - yp.float()).abs().max().item()
-
-
 @pytest.mark.parametrize("variant,dtype,batch,h,w,nchain", [("n", torch.bfloat16, 2, 640, 640, 3),
                                                            ("n", torch.float16, 3, 96, 160, 3),
                                                            ("n", torch.bfloat16, 32, 640, 640, 3),
@@ -361,15 +337,14 @@ def _load_convs(eng, sd, names):
             eng._load(idx, sd[f"{name}.weight"], sd.get(f"{name}.bias"), None)
 
 
-@pytest.mark.parametrize("boxchain", [False, True])
-def test_reloaded_weights_reach_the_fused_kernels(gpu, boxchain):
+def test_reloaded_weights_reach_the_fused_kernels(gpu):
     """A fused op packs its member convs' weights into one cached device image on its first launch
-    (the fused stem, whole and tail C3k2, C3k, and with YH_BOXCHAIN=1 the box chain), head_cls / box_dfl /
+    (the fused stem, whole and tail C3k2, C3k), head_cls / box_dfl /
     the pointwise chains read per-conv device copies, and the captured graph holds all those
     pointers. Loading weights again, all of them or a single member conv that does not own the
     cache, must reach the next forward: bit-identical to an engine that only ever saw those weights."""
     batch, h, w = 2, 96, 160
-    env = {"YH_BOXCHAIN": "1"} if boxchain else {}
+    env = {}
     x = synth.synth_scenes(batch, h, w, seed=53).to(gpu, torch.float16)
     eng, template = _bare_engine(gpu, env)
     sd_a = synth.synth_state_dict(template, seed=0)
@@ -383,7 +358,7 @@ def test_reloaded_weights_reach_the_fused_kernels(gpu, boxchain):
     kinds, labels = {u["cls"] for u in units}, [u["label"] for u in units]
     assert {"c3k2", "c3k", "head_cls", "pw_chain"} <= kinds, kinds
     assert "net.p1.0+p2.0" in labels and "net.p2.1" in labels and "fpn.h2.tail" in labels, labels
-    assert ("box_chain" in kinds and "box_dfl" not in kinds) if boxchain else "box_dfl" in kinds, kinds
+    assert "box_dfl" in kinds, kinds
     # 2. B into the same engine
     _load_convs(eng, sd_b, every)
     y_b = eng.forward(x).clone()
@@ -396,12 +371,10 @@ def test_reloaded_weights_reach_the_fused_kernels(gpu, boxchain):
 
     # 3. partial reload: per fused kind one member conv that does not own the cached image
     #    (stem: the image lives with net.p2.0; whole C3k2: with conv1; tail C3k2 and C3k: with the
-    #    first conv of the op; box chain: with box.l.0), and one conv each of head_cls, box_dfl and
+    #    first conv of the op), and one conv each of head_cls, box_dfl and
     #    a pointwise chain
     some = {"net.p1.0", "net.p2.1.res_m.0.conv2", "fpn.h2.conv2", "net.p4.1.res_m.0.res_m.1.conv1", "head.cls.0.3",
             "head.box.1.2", "net.p5.2.conv1"}
-    if boxchain:
-        some.add("head.box.0.1")
     assert some <= every, some - every
     part, _ = _bare_engine(gpu, env)
     _load_convs(part, sd_a, every)

@@ -13,7 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [("n", "bf16", 4, 640), ("s", "fp16", 2, 320), ("n", "fp16", 2, 224), ("m", "bf16", 2, 480),
          ("n", "fp32", 2, 224), ("x", "bf16", 1, 256)]
-SETTINGS = [{}, {"YH_FUSE": "0"}, {"YH_C3K": "0"}, {"YH_PWCHAIN": "0"}, {"YH_CSP_TAIL": "1"}, {"YH_BOXCHAIN": "1"}]
+SETTINGS = [{}, {"YH_FUSE": "0"}, {"YH_C3K": "0"}, {"YH_PWCHAIN": "0"}, {"YH_CSP_TAIL": "1"}]
 DTYPES = {"bf16": "bfloat16", "fp16": "float16", "fp32": "float32"}
 
 

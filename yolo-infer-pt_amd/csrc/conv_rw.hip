@@ -29,7 +29,6 @@
 #include "dtypes.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 
 #ifndef RW_PF
@@ -58,9 +57,9 @@ RwGeo rw_geo(int S, int cin, int ncg, int npg, int mb, int tw, bool res, int nkc
     g.slot = (g.nbi + g.nbr) * g.nw * 1024;
     // K-split layers: every chunk's fp32 partial tile in LDS (the reduction and the epilogue
     // are shared by the chunk waves); otherwise one 32-pixel x 32-cout staging tile per wave for
-    // the coalesced epilogue. + the slice's bias, + the counter mode's slot counters (2 x 8 words)
+    // the coalesced epilogue. + the slice's bias
     g.red = nkc > 1 ? nkc * ncg * npg * mb * 4096 : 0;
-    g.epi = (nkc > 1 ? 0 : ncg * npg * 2048) + ncg * 128 + 64;
+    g.epi = (nkc > 1 ? 0 : ncg * npg * 2048) + ncg * 128;
     return g;
 }
 
@@ -99,22 +98,6 @@ __device__ __forceinline__ void rw_vmwait() {
 __device__ __forceinline__ void rw_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-}
-
-// counter mode: wait (bounded) until the LDS word at p reaches target. Returns false if the
-// bound ran out: the caller then poisons its tile with NaN, so a stalled hand-off shows up as
-// wrong outputs every test catches, not as a silent race (and not as a hang or a trap)
-__device__ __forceinline__ bool rw_spin(const unsigned* p, unsigned target) {
-    for (int k = 0; k < (1 << 22); ++k) {
-        const unsigned v = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const volatile unsigned*>(p));
-        if (v >= target) return true;
-        __builtin_amdgcn_s_sleep(1);
-    }
-    return false;
-}
-__device__ __forceinline__ void rw_signal(unsigned* p, int lane) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's LDS reads of the slot are done
-    if (lane == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 // LDS column of patch column pcol (and back): stride 2 stores a row's even columns first
@@ -163,13 +146,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rw_rsrc(const void* base) {
 
 }  // namespace
 
-// CM (counter mode, NKC = 1): no workgroup barrier per tile. Tile it + NS - 2 is issued at
-// iteration it into the slot tile it - 2 used, once every wave has signalled it done with that
-// tile (LDS counter); a wave starts tile it once every wave has signalled its pieces of tile it
-// landed. Waves may drift up to a tile apart: the second half of the waves starts half a tile
-// late, so on each SIMD one wave's epilogue (VALU: SiLU, the staging, the stores) runs beside
-// the other's MFMAs instead of after them. Same arithmetic, same bits.
-template <typename T, int S, int CIN, int NCG, int NPG, int MB, int TW, int NS, bool RES, int NKC, bool CM>
+template <typename T, int S, int CIN, int NCG, int NPG, int MB, int TW, int NS, bool RES, int NKC>
 __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG > 1 || CIN <= 32) ? 2 : 1) void conv_rw(
     const MxArgs p) {
     constexpr int NW = NCG * NKC * NPG;
@@ -195,11 +172,6 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
     constexpr int CNT0 = (NS - 1) * SPT + (NS - 2) * (NBI + NBR);
     static_assert(NKC == 1 || NKC == 2 || NKC == 4, "K chunks");
     static_assert(CNT0 <= 63, "vmcnt range");
-    // counter mode: tiles issued D = NS - 2 ahead; at the wait for tile it's DMA, the wave has
-    // issued since then the DMAs of D - 1 tiles and the stores of D epilogues
-    constexpr int DPC = NS - 2;
-    constexpr int CNTP = DPC * 2 * MB + (DPC - 1) * (NBI + NBR);
-    static_assert(!CM || (NKC == 1 && NS >= 3 && CNTP <= 63), "counter mode geometry");
 
     const unsigned long long t_entry = RW_TRACE ? __builtin_amdgcn_s_memrealtime() : 0ull;
     extern __shared__ __attribute__((aligned(1024))) uint4 sm4[];
@@ -352,9 +324,6 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
     // where its vmcnt(0) would drain the patch ring every iteration)
 #pragma unroll
     for (int s = 0; s < NKS; ++s) asm volatile("" :: "v"(wf[s].x), "v"(wf[s].y), "v"(wf[s].z), "v"(wf[s].w));
-    // counter mode: landed[NS] then done[NS], zeroed before the barrier below
-    unsigned* cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(sm4) + NS * SLOT + RED + EST + NCG * 128);
-    if (CM && (int)threadIdx.x < 2 * NS) cnt[threadIdx.x] = 0u;
     rw_vmwait<0>();
     rw_barrier();
     const unsigned long long t_setup = RW_TRACE ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -480,47 +449,22 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
     // it's MFMAs (the partials wait in LDS; the residual would sit in a slot the ring has already
     // re-filled). Iteration 0 issues the same number of stores to the dropped offset, so the
     // vmcnt arithmetic (CNT0) holds from the first iteration on.
-    constexpr bool DEFER = NKC > 1 && !RES && !CM;
+    constexpr bool DEFER = NKC > 1 && !RES;
     auto dummy_stores = [&]() {
         constexpr int NR = 32 / NKC / 8;
 #pragma unroll
         for (int k = 0; k < MB * NR; ++k) __builtin_amdgcn_raw_buffer_store_b64(rw_u32x2{0u, 0u}, ro, RW_OOB, 0, 0);
     };
     unsigned long long t_wait = 0ull;   // diagnostic builds, dbg 64: time spent in the loop-top waits
-    if constexpr (CM) {
-        // the prologue issued tiles 0 .. NS - 2; tiles 0 .. DPC - 1 are the ones this loop expects
-        // (issue distance DPC): the remaining one (NS - 2) is also in flight, counted like the rest
-        if (wv >= NW / 2) {   // the second half of the waves starts half a tile late
-#pragma unroll 1
-            for (int k = 0; k < p.pc_delay; ++k) __builtin_amdgcn_s_sleep(32);
-        }
-    }
-    bool stalled = false;   // counter mode: a hand-off wait ran out (rw_spin)
     for (int it = 0; it < n_it; ++it) {
-        if constexpr (CM) {
-            const int sl_it = it % NS;
-            if (it >= NS - 1) {
-                // tiles past the prologue's: this wave's pieces landed, then everyone's (the count
-                // of slot sl_it's tiles from NS - 1 on, this one included)
-                const int first = sl_it == NS - 1 ? NS - 1 : sl_it + NS;
-                rw_vmwait<CNTP>();
-                rw_signal(cnt + sl_it, lane);
-                stalled |= !rw_spin(cnt + sl_it, (unsigned)(NW * ((it - first) / NS + 1)));
-            }
-            if (it >= 1) {
-                // tile it + NS - 2 into the slot tile it - 2 used, once every wave is done with it
-                // (tile NS - 1, issued at it = 1, takes the ring's unused last slot)
-                if (it >= 2) stalled |= !rw_spin(cnt + NS + (it - 2) % NS, (unsigned)(NW * ((it - 2) / NS + 1)));
-                issue(it + NS - 2, (it + NS - 2) % NS);
-            }
-        } else if (it > 0) {
+        if (it > 0) {
             const unsigned long long tw0 = (RW_TRACE && RW_DBG(64)) ? __builtin_amdgcn_s_memrealtime() : 0ull;
             rw_vmwait<CNT0>();
             rw_barrier();   // tile it complete in its slot; slot (it - 1) % NS read by every wave
             if (RW_TRACE && RW_DBG(64)) t_wait += __builtin_amdgcn_s_memrealtime() - tw0;
             if (RW_TRACE && it == 1) t_first = __builtin_amdgcn_s_memrealtime();
         }
-        if constexpr (!CM) issue(it + NS - 1, (it + NS - 1) % NS);
+        issue(it + NS - 1, (it + NS - 1) % NS);
         if constexpr (DEFER) {
             if (it > 0) epilogue_split(it - 1);
             else dummy_stores();
@@ -558,14 +502,6 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
             }
         }
 
-        if constexpr (CM) {
-            if (stalled) {
-#pragma unroll
-                for (int j = 0; j < MB; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[j][e] = __builtin_nanf("");
-            }
-        }
         if (RW_DBG(16)) continue;   // ablation: no K-chunk reduction, no epilogue
         // ---- K chunks: every chunk wave's partial tile to LDS (lane (r32, h) holds couts
         //      16 h .. 16 h + 15 of pixel r32: 4 swizzled 16-B chunks), then the shared epilogue
@@ -586,7 +522,6 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
         } else {
             epilogue(it);
         }
-        if constexpr (CM) rw_signal(cnt + NS + it % NS, lane);
     }
     if constexpr (DEFER) {
         rw_barrier();   // the last tile's partials
@@ -697,10 +632,10 @@ void mx_candidates_w(const MxShape& sh, std::vector<MxConfig>& out) {
     if (!(sh.cin == 16 || sh.cin == 32 || sh.cin == 64 || nkc > 1)) return;
     // small layers (fewer tiles than 2 per CU) also get the grid halved and quartered
     const bool small = (double)sh.B * sh.Ho * sh.Wo < 2.0 * 256 * 64;
-    auto add = [&](int ncg, int npg, int mb, int tw, int ns, int pc = 0) {
+    auto add = [&](int ncg, int npg, int mb, int tw, int ns) {
         MxConfig c{};
         c.kind = 2; c.ks = 3; c.s = sh.s; c.na = ncg; c.mb = mb; c.wn = ncg; c.wm = npg; c.ncb = sh.cin / 16;
-        c.tw = tw; c.nbuf = ns; c.nkc = nkc; c.pc = pc;
+        c.tw = tw; c.nbuf = ns; c.nkc = nkc;
         for (int gd : {1, 2, 4}) {
             if (gd > 1 && !small) break;
             c.gdiv = gd;
@@ -722,9 +657,6 @@ void mx_candidates_w(const MxShape& sh, std::vector<MxConfig>& out) {
     } else if (sh.s == 1) {
         if (sh.cin == 64 && ncg == 2) {
             add(2, 4, 1, 16, 4); add(2, 4, 1, 8, 4); add(2, 2, 1, 8, 4); add(2, 2, 1, 4, 4); add(2, 2, 1, 8, 3);
-            // counter mode (YH_RW_CM=1 only: bit-identical, measured slower, r05 micro bench box0.0:
-            // 26.8-27.5 us against 25.5 us for the barrier ring)
-            if (getenv("YH_RW_CM")) { add(2, 4, 1, 16, 4, 1); add(2, 4, 1, 16, 5, 1); add(2, 4, 1, 8, 4, 1); }
         } else if (sh.cin == 64 && ncg == 1) {
             add(1, 8, 1, 16, 3); add(1, 4, 1, 8, 4);
         } else if (sh.cin == 32 && ncg == 1) {
@@ -734,7 +666,6 @@ void mx_candidates_w(const MxShape& sh, std::vector<MxConfig>& out) {
         }
     } else if (sh.cin == 64 && ncg == 2) {
         add(2, 2, 1, 8, 3); add(2, 4, 1, 16, 2);
-        if (getenv("YH_RW_CM")) add(2, 2, 1, 8, 3, 1);
         // 128 couts in one workgroup: the patch is read once, not once per 64-cout slice
         if (sh.cout % 128 == 0) { add(4, 2, 1, 8, 3); add(4, 1, 1, 8, 4); }
     }
@@ -776,12 +707,12 @@ std::vector<uint16_t> mx_pack_w(const MxPlan& pl, const MxShape& sh, const float
 
 namespace {
 
-template <typename T, int S, int CIN, int NCG, int NPG, int MB, int TW, int NS, bool RES, int NKC, bool CM = false>
+template <typename T, int S, int CIN, int NCG, int NPG, int MB, int TW, int NS, bool RES, int NKC>
 int launch_rw_t(const MxPlan& pl, const MxArgs& a, hipStream_t s) {
     const RwGeo g = rw_geo(S, CIN, NCG, NPG, MB, TW, RES, NKC);
     if (g.nbi != pl.nbi || NS * g.slot + g.red + g.epi != pl.lds || RES != (a.res != nullptr)) return (int)hipErrorInvalidValue;
     static bool attr = false;
-    auto k = &conv_rw<T, S, CIN, NCG, NPG, MB, TW, NS, RES, NKC, CM>;
+    auto k = &conv_rw<T, S, CIN, NCG, NPG, MB, TW, NS, RES, NKC>;
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024);
@@ -796,22 +727,10 @@ int launch_rw_cfg(const MxPlan& pl, const MxArgs& a, hipStream_t s) {
     const MxConfig& c = pl.cfg;
 #define YH_RW(S_, CIN_, NCG_, NPG_, MB_, TW_, NS_, NKC_)                                                    \
     if (c.s == S_ && c.ncb * 16 == CIN_ && c.na == NCG_ && c.wm == NPG_ && c.mb == MB_ && c.tw == TW_ &&     \
-        c.nbuf == NS_ && c.nkc == NKC_ && c.pc == 0) {                                                       \
+        c.nbuf == NS_ && c.nkc == NKC_) {                                                                    \
         if (S_ == 1 && a.res) return launch_rw_t<T, S_, CIN_, NCG_, NPG_, MB_, TW_, NS_, (S_ == 1), NKC_>(pl, a, s); \
         return launch_rw_t<T, S_, CIN_, NCG_, NPG_, MB_, TW_, NS_, false, NKC_>(pl, a, s);                     \
     }
-#define YH_RWP(S_, CIN_, NCG_, NPG_, MB_, TW_, NS_)                                                          \
-    if (c.s == S_ && c.ncb * 16 == CIN_ && c.na == NCG_ && c.wm == NPG_ && c.mb == MB_ && c.tw == TW_ &&     \
-        c.nbuf == NS_ && c.nkc == 1 && c.pc == 1) {                                                          \
-        if (S_ == 1 && a.res) return launch_rw_t<T, S_, CIN_, NCG_, NPG_, MB_, TW_, NS_, (S_ == 1), 1, true>(pl, a, s); \
-        return launch_rw_t<T, S_, CIN_, NCG_, NPG_, MB_, TW_, NS_, false, 1, true>(pl, a, s);                   \
-    }
-    // counter mode (pc = 1)
-    YH_RWP(1, 64, 2, 4, 1, 16, 4)
-    YH_RWP(1, 64, 2, 4, 1, 16, 5)
-    YH_RWP(1, 64, 2, 4, 1, 8, 4)
-    YH_RWP(2, 64, 2, 2, 1, 8, 3)
-#undef YH_RWP
     YH_RW(1, 64, 2, 4, 1, 16, 4, 1)
     YH_RW(1, 64, 2, 4, 1, 8, 4, 1)
     YH_RW(1, 64, 2, 2, 1, 8, 4, 1)
@@ -843,12 +762,7 @@ int launch_rw_cfg(const MxPlan& pl, const MxArgs& a, hipStream_t s) {
 
 }  // namespace
 
-int launch_rw(int dtype, const MxPlan& pl, const MxArgs& a0, hipStream_t s) {
-    MxArgs a = a0;
-    // counter mode: how long the second half of the waves starts late (YH_RW_DELAY, read per
-    // launch: s_sleep(32) rounds of 2048 cycles)
-    const char* e = getenv("YH_RW_DELAY");
-    a.pc_delay = e ? std::max(0, atoi(e)) : 1;
+int launch_rw(int dtype, const MxPlan& pl, const MxArgs& a, hipStream_t s) {
     if (dtype == BF16) return launch_rw_cfg<__bf16>(pl, a, s);
     if (dtype == F16) return launch_rw_cfg<_Float16>(pl, a, s);
     return (int)hipErrorInvalidValue;

@@ -20,10 +20,10 @@ namespace yh {
 // ---------------------------------------------------------------- graph model
 enum ConvKind { CK_DENSE = 0, CK_FIRST = 1, CK_DW = 2, CK_PE = 3 };
 enum OpKind { OP_FIRST, OP_CONV, OP_DW, OP_SPPF, OP_ATTN, OP_DECODE, OP_HEADCLS, OP_BOXDFL, OP_CSP, OP_STEM2, OP_C3K,
-              OP_BOXCHAIN, OP_PWCHAIN, OP_CLSPOOL, OP_CLSHEAD, OP_CLSFC };
+              OP_PWCHAIN, OP_CLSPOOL, OP_CLSHEAD, OP_CLSFC };
 const char* op_kind_name(OpKind k);
 enum OpClass { CL_CONV3 = 0, CL_CONV1 = 1, CL_FIRST = 2, CL_DW = 3, CL_SPPF = 4, CL_ATTN = 5, CL_DECODE = 6,
-               CL_HEADCLS = 7, CL_BOXDFL = 8, CL_CSP = 9, CL_C3K = 10, CL_BOXCHAIN = 11, CL_PWCHAIN = 12, CL_CLS = 13, CL_N = 14 };
+               CL_HEADCLS = 7, CL_BOXDFL = 8, CL_CSP = 9, CL_C3K = 10, /* 11: unused */ CL_PWCHAIN = 12, CL_CLS = 13, CL_N = 14 };
 
 // level < 0: one fp32 vector of C values per image (the classifier's embedding and logits)
 struct Tensor { int level; int C; };        // physical channels = pixel stride
@@ -74,12 +74,9 @@ struct Op {
     // OP_C3K: conv1, conv2, res_m.0.conv1, res_m.0.conv2, res_m.1.conv1, res_m.1.conv2, conv3 of
     // a CSPModule
     int ck[7] = {-1, -1, -1, -1, -1, -1, -1};
-    // OP_BOXCHAIN: per level the box.l.0 / box.l.1 / box.l.2 convs (input hx[l])
-    int bxc[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};
-    // OP_C3K, OP_BOXCHAIN, OP_PWCHAIN: the per-layer ops this op replaces at shapes where it fits
+    // OP_C3K, OP_PWCHAIN: the per-layer ops this op replaces at shapes where it fits
     // (Net::fused_fits); exactly one side is active in a plan. OP_C3K: the block's seven convs.
-    // OP_BOXCHAIN: box.l.0 per level, box.l.1 per level, box_dfl. OP_PWCHAIN: the member 1x1
-    // conv ops (stages, in order)
+    // OP_PWCHAIN: the member 1x1 conv ops (stages, in order)
     std::vector<int> alts;
     // OP_PWCHAIN: per stage its input runs (16-channel blocks in weight order: LDS region of an
     // earlier stage's output, or a prologue-loaded global view), its residual and whether its
@@ -121,13 +118,12 @@ struct GraphKey {
 // YH_CLSHEAD=1 runs a classifier's head.conv + cls_pool as one launch (cls_head; bit-identical, compared
 // by the tests; off by default because the two launches measured faster).
 struct Options {
-    bool fuse = true, csp_tail = false, tune_log = false, c3k = true, hcls_wide = true, box_chain = false, pw_chain = true;
+    bool fuse = true, csp_tail = false, tune_log = false, c3k = true, hcls_wide = true, pw_chain = true;
     bool cls_head = false;
     int conv_force = -1;
     static Options from_env() {
         Options o;
         if (const char* e = getenv("YH_FUSE")) o.fuse = atoi(e) != 0;
-        if (const char* e = getenv("YH_BOXCHAIN")) o.box_chain = atoi(e) != 0;
         if (const char* e = getenv("YH_PWCHAIN")) o.pw_chain = atoi(e) != 0;
         if (const char* e = getenv("YH_CSP_TAIL")) o.csp_tail = atoi(e) != 0;
         if (const char* e = getenv("YH_C3K")) o.c3k = atoi(e) != 0;
@@ -207,7 +203,6 @@ struct Net {
     bool fuse_stem(int c0, int c1, int c2) const;
     bool fuse_csp(const std::vector<Seg>& in, const std::vector<int>& logical, int c, int out_ch, View out) const;
     bool fuse_csp_tail(int c, int out_ch, View out) const;
-    bool fuse_box_chain(int boxc, const int (&xs)[3], const int (&xc)[3]) const;
     bool fuse_decode(int boxc, int nc) const;
     bool fuse_head_cls(int C0, int c3, int nc) const;
 
@@ -223,7 +218,6 @@ struct Net {
     const void* stem2_params(const Op& op, int& bias_off, int& stem_off);
     const void* csp_params(const Op& op);
     const void* c3k_params(const Op& op);
-    const void* box_chain_params(const Op& op, int l);
     const char* mx_weights(int ci, const MxPlan& p, const MxShape& sh);
 
     // ---------------------------------------------------------- net_forward.cpp
@@ -256,7 +250,6 @@ struct Net {
     DecodeArgs decode_args(const Op& op, int B, int H, int W) const;
     HeadClsArgs head_cls_args(const Op& op, int B, int H, int W);
     BoxDflArgs box_dfl_args(const Op& op, int B, int H, int W);
-    BoxChainArgs box_chain_args(const Op& op, int B, int H, int W);
     PwChainArgs pw_chain_args(const Op& op, int B, int H, int W);
     CspArgs csp_args(size_t oi, int B, int H, int W, int& grid);
     C3kArgs c3k_args(const Op& op, int B, int H, int W);

@@ -329,15 +329,12 @@ void Net::build() {
     Op bdop;
     bdop.kind = OP_BOXDFL;
     bdop.label = "head.box_dfl";
-    int bop[3][2];   // per level: the ops of box.l.0 and box.l.1
     // per level, coarsest first (the 80x80 level's launches come last)
     for (int l : {2, 1, 0}) {
         const int lvl = 3 + l;
         const std::string bp = "head.box." + std::to_string(l);
         const int tb1 = tensor(lvl, boxc), tb2 = tensor(lvl, boxc);
-        bop[l][0] = (int)ops.size();
         conv3(bp + ".0", full(xs[l], xc[l]), xc[l], boxc, 1, ACT_SILU, full(tb1, boxc));
-        bop[l][1] = (int)ops.size();
         conv3(bp + ".1", full(tb1, boxc), boxc, boxc, 1, ACT_SILU, full(tb2, boxc));
         if (fdec) {
             bdop.bc[l] = new_dense_conv(bp + ".2", boxc, 64, 1, 1, ACT_ID);
@@ -368,23 +365,6 @@ void Net::build() {
     }
     if (fuse_any) ops.push_back(hcop);
     if (fdec) ops.push_back(bdop);
-    // 16-bit handles: the whole box branch of every level as one launch (boxc.hip) at shapes
-    // where each level has a tile (ensure_plan picks it or the seven launches above)
-    if (fdec && fuse_box_chain(boxc, xs, xc)) {
-        Op bc;
-        bc.kind = OP_BOXCHAIN;
-        bc.label = "head.box";
-        for (int l = 0; l < 3; ++l) {
-            bc.bxc[l][0] = ops[bop[l][0]].conv;
-            bc.bxc[l][1] = ops[bop[l][1]].conv;
-            bc.bxc[l][2] = bdop.bc[l];
-            bc.hx[l] = full(xs[l], xc[l]);
-        }
-        for (int l = 0; l < 3; ++l) bc.alts.push_back(bop[l][0]);
-        for (int l = 0; l < 3; ++l) bc.alts.push_back(bop[l][1]);
-        bc.alts.push_back((int)ops.size() - 1);   // box_dfl
-        ops.push_back(bc);
-    }
     Op dec;
     dec.kind = OP_DECODE;
     for (int l = 0; l < 3; ++l) dec.lvl[l] = full(L[l]);
@@ -569,14 +549,6 @@ bool Net::fuse_csp_tail(int c, int out_ch, View out) const {
     if (c % 16 || out_ch % 32 || out.coff % 8) return false;
     int TH, TW;
     return csp_tile(0, c / 16, out_ch / 32, 1, 1 << 30, 1 << 30, 1, TH, TW);
-}
-// the box branch runs as one launch (boxc.hip) for 64 box channels and level inputs of
-// 64 / 128 / 256 / 512 channels (plain views)
-bool Net::fuse_box_chain(int boxc, const int (&xs)[3], const int (&xc)[3]) const {
-    if (dtype == F32 || !opt.fuse || !opt.box_chain || boxc != 64) return false;
-    for (int l = 0; l < 3; ++l)
-        if (!bx_ok(xc[l]) || tensors[xs[l]].C != xc[l]) return false;
-    return true;
 }
 // the decode folds into box_dfl + head_cls / a class-rows decode (16-bit handles; the
 // box branch's last conv has 4 or 6 16-channel K blocks)

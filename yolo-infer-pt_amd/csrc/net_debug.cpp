@@ -9,7 +9,7 @@ namespace yh {
 static const struct { const char* name; OpClass cls; } KINDS[] = {
     {"stem", CL_FIRST}, {"conv", CL_CONV1}, {"dwconv", CL_DW}, {"sppf", CL_SPPF}, {"attention", CL_ATTN},
     {"decode", CL_DECODE}, {"head_cls", CL_HEADCLS}, {"box_dfl", CL_BOXDFL}, {"c3k2", CL_CSP}, {"stem_fused", CL_FIRST},
-    {"c3k", CL_C3K}, {"box_chain", CL_BOXCHAIN}, {"pw_chain", CL_PWCHAIN}, {"cls_pool", CL_CLS}, {"cls_head", CL_CLS},
+    {"c3k", CL_C3K}, {"pw_chain", CL_PWCHAIN}, {"cls_pool", CL_CLS}, {"cls_head", CL_CLS},
     {"cls_fc", CL_CLS}};
 static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == OP_CLSFC + 1, "one entry per OpKind");
 const char* op_kind_name(OpKind k) { return KINDS[k].name; }
@@ -124,17 +124,6 @@ void Net::op_cost(const Op& op, int B, int H, int W, double& bytes, double& flop
             }
             break;
         }
-        case OP_BOXCHAIN: {
-            // the level inputs read once, 4 box rows written, the three convs' weights once
-            for (int l = 0; l < 3; ++l) {
-                const double n = px(tensors[op.hx[l].t].level);
-                const int C0 = convs[op.bxc[l][0]].cin;
-                const double macs = 64.0 * C0 * 9 + 64.0 * 64 * 9 + 64.0 * 64;
-                bytes += n * C0 * es + n * 4 * es + macs * es + 3 * 64 * 4.0;
-                flops += 2.0 * n * macs + n * 64 * 4.0;
-            }
-            break;
-        }
         case OP_CLSPOOL:
             // the activations read once, the fp32 embedding written once
             bytes = px(5) * op.out.C * es + (double)B * op.out.C * 4;
@@ -201,9 +190,6 @@ std::vector<Net::Operand> Net::operands(const Op& op) const {
         case OP_BOXDFL:
             for (int l = 0; l < 3; ++l) add("x" + std::to_string(l), op.bx[l], 0, op.bx[l].C);
             break;
-        case OP_BOXCHAIN:
-            for (int l = 0; l < 3; ++l) add("x" + std::to_string(l), op.hx[l], 0, op.hx[l].C);
-            break;
         case OP_DECODE:
             for (int l = 0; l < 3; ++l) add("L" + std::to_string(l), op.lvl[l], 0, 64 + var.num_classes);
             break;
@@ -262,10 +248,6 @@ std::vector<int> Net::op_convs(const Op& op) const {
                 for (int k = 0; k < 5; ++k) r.push_back(op.hlv[l] ? op.hc[l][k] : -1);
             break;
         case OP_BOXDFL: return {op.bc[0], op.bc[1], op.bc[2]};
-        case OP_BOXCHAIN:
-            for (int l = 0; l < 3; ++l)
-                for (int k = 0; k < 3; ++k) r.push_back(op.bxc[l][k]);
-            break;
         case OP_PWCHAIN:
             for (int k : op.alts) r.push_back(ops[k].conv);
             break;

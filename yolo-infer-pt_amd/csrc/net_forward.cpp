@@ -92,14 +92,6 @@ Net::~Net() {
 // whether a fused op with per-layer alternatives (Op::alts) runs at this shape
 bool Net::fused_fits(const Op& op, int B, int H, int W) const {
     switch (op.kind) {
-        case OP_BOXCHAIN:
-            // where every level has a tile
-            for (int l = 0; l < 3; ++l) {
-                const int lv = tensors[op.hx[l].t].level;
-                int th, tw;
-                if (!bx_tile(H >> lv, W >> lv, th, tw)) return false;
-            }
-            return true;
         case OP_PWCHAIN: {
             const int lv = tensors[op.out.t].level;
             // a pointwise chain reads every stage's weights once per workgroup: kept where that is at
@@ -133,9 +125,8 @@ void Net::ensure_plan(int B, int H, int W) {
     pl.active.assign(ops.size(), 1);
     // Either a fused op or its alternatives run. The order of the decisions cannot matter: the
     // alternative sets are disjoint and hold no op that has alternatives itself (build(): a C3k
-    // op's are its own block's seven convs, the box chain's the head's box convs and box_dfl, and
-    // fuse_pw_chains takes only plain convs that are in no other op's set, each for one chain), so
-    // every entry of `active` is cleared by at most one op
+    // op's are its own block's seven convs, and fuse_pw_chains takes only plain convs that are in
+    // no other op's set, each for one chain), so every entry of `active` is cleared by at most one op
     for (size_t i = 0; i < ops.size(); ++i) {
         if (ops[i].alts.empty()) continue;
         if (fused_fits(ops[i], B, H, W))

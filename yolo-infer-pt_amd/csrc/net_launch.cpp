@@ -66,8 +66,8 @@ MxShape Net::mx_shape(const ConvArgs& a, int B) const {
 static std::string mx_name(const MxPlan& p) {
     char b[96];
     if (p.cfg.kind == 2)
-        snprintf(b, sizeof(b), "rw_g%d_p%d_mb%d_ns%d_t%dx%d%s%s", p.cfg.na, p.cfg.wm, p.cfg.mb, p.cfg.nbuf, p.TH, p.TW,
-                 p.cfg.gdiv == 2 ? "_d2" : p.cfg.gdiv == 4 ? "_d4" : "", p.cfg.pc ? "_cm" : "");
+        snprintf(b, sizeof(b), "rw_g%d_p%d_mb%d_ns%d_t%dx%d%s", p.cfg.na, p.cfg.wm, p.cfg.mb, p.cfg.nbuf, p.TH, p.TW,
+                 p.cfg.gdiv == 2 ? "_d2" : p.cfg.gdiv == 4 ? "_d4" : "");
     else
         snprintf(b, sizeof(b), "%s_na%d_mb%d_w%dx%d_ncb%d_t%dx%d", p.cfg.kind ? "mxr" : "mx", p.cfg.na, p.cfg.mb,
                  p.cfg.wn, p.cfg.wm, p.cfg.ncb, p.TH, p.TW);
@@ -440,41 +440,6 @@ BoxDflArgs Net::box_dfl_args(const Op& op, int B, int H, int W) {
     return a;
 }
 
-BoxChainArgs Net::box_chain_args(const Op& op, int B, int H, int W) {
-    BoxChainArgs a{};
-    a.B = B;
-    a.nc = var.num_classes;
-    a.A = anchor_off(3, H, W);
-    a.io = (const void* const*)io_dev;
-    a.zero = zero_dev;
-    int wg = 0;
-    // workgroup order: the coarsest level, whose tiles are the longest, first (142 vs 148 us)
-    for (int k = 0; k < 3; ++k) {
-        const int l = 2 - k;
-        BoxChainLevel& v = a.lv[a.nlv++];
-        const int lv = tensors[op.hx[l].t].level;
-        v.x = ptr(op.hx[l]);
-        v.ldx = ldc(op.hx[l]);
-        v.C0 = convs[op.bxc[l][0]].cin;
-        v.H = H >> lv;
-        v.W = W >> lv;
-        require(bx_tile(v.H, v.W, v.TH, v.TW), "head.box: no tile");
-        v.ntw = (v.W + v.TW - 1) / v.TW;
-        v.tiles = v.ntw * ((v.H + v.TH - 1) / v.TH);
-        // box.l.0's canonical K order at this shape (conv_mx.h mx_kchunks)
-        ConvArgs ca{};
-        int BM, BN;
-        conv_args(ops[op.alts[l]], B, H, W, ca, BM, BN);
-        v.nkc = mx_kchunks(mx_shape(ca, B));
-        v.stride = (float)(1 << lv);
-        v.aoff = anchor_off(l, H, W);
-        v.prm = box_chain_params(op, l);
-        v.wg0 = wg;
-        wg += B * v.tiles;
-    }
-    return a;
-}
-
 // Work items of one tile over P1-P4 (c3k2.hip cs_phase: one 32-cout A tile x one 32-pixel
 // B tile each); P1 and P2 run on the tile with its 2- / 1-pixel halo.
 static int csp_items(int TH, int TW, int ni, int nc, int no) {
@@ -645,7 +610,6 @@ void Net::launch_op(size_t oi, int B, int H, int W, hipStream_t s) {
         case OP_HEADCLS: rc = launch_head_cls(dtype, head_cls_args(op, B, H, W), s); break;
         case OP_DECODE: rc = launch_decode(dtype, decode_args(op, B, H, W), s); break;
         case OP_BOXDFL: rc = launch_box_dfl(dtype, box_dfl_args(op, B, H, W), s); break;
-        case OP_BOXCHAIN: rc = launch_box_chain(dtype, box_chain_args(op, B, H, W), s); break;
         case OP_PWCHAIN: rc = launch_pw_chain(dtype, pw_chain_args(op, B, H, W), op.pwLds, s); break;
         case OP_STEM2: rc = launch_stem2(dtype, stem2_args(op, B, H, W), s); break;
         case OP_CSP: {

@@ -247,44 +247,5 @@ const void* Net::c3k_params(const Op& op) {
         return img;
     });
 }
-// packed parameters of one level of the box chain (boxc.hip layout), cached with box.l.0
-const void* Net::box_chain_params(const Op& op, int l) {
-    return fused_params(op.bxc[l][0], "bxc", {op.bxc[l][1], op.bxc[l][2]}, [&] {
-        const ConvDesc &c0 = convs[op.bxc[l][0]], &c1 = convs[op.bxc[l][1]], &c2 = convs[op.bxc[l][2]];
-        const int C0 = c0.cin, ncb = C0 / 16;
-        require(c0.cout == 64 && c1.cin == 64 && c1.cout == 64 && c2.cin == 64 && c2.cout == 64 && c2.k == 1,
-                "box chain: conv shapes");
-        std::vector<uint8_t> img((size_t)bx_prm_bytes(C0), 0);
-        uint16_t* dst = reinterpret_cast<uint16_t*>(img.data());
-        const size_t item = 18 * 1024 / 2;   // ring item (uint16 units)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int R = lane & 31, hh = lane >> 5;
-            for (int a = 0; a < 2; ++a) {
-                // conv_mx's rows (lane half hh: couts 16 hh ..) and c3k's permuted rows (registers
-                // 8 jj .. of tile a = channels 32 a + 16 jj + 8 hh ..: the 1x1's B fragments)
-                const int co0 = 32 * a + frag_row(R, ROWS_MX), co1 = 32 * a + frag_row(R, ROWS_RHO);
-                const int co2 = 32 * ((R >> 2) & 1) + 16 * a + (R & 3) + 4 * (R >> 3);   // box_dfl's rows
-                for (int j = 0; j < 8; ++j) {
-                    for (int cb = 0; cb < ncb; ++cb)
-                        for (int t = 0; t < 9; ++t)
-                            dst[cb * item + ((size_t)(a * 9 + t) * 64 + lane) * 8 + j] =
-                                to16(c0.wf[((size_t)co0 * C0 + 16 * cb + 8 * hh + j) * 9 + t]);
-                    for (int kb = 0; kb < 4; ++kb) {
-                        for (int t = 0; t < 9; ++t)
-                            dst[(ncb + kb) * item + ((size_t)(a * 9 + t) * 64 + lane) * 8 + j] =
-                                to16(c1.wf[((size_t)co1 * 64 + 16 * kb + 8 * hh + j) * 9 + t]);
-                        dst[(ncb + 4) * item + ((size_t)(a * 4 + kb) * 64 + lane) * 8 + j] =
-                            to16(c2.wf[(size_t)co2 * 64 + 16 * kb + 8 * hh + j]);
-                    }
-                }
-            }
-        }
-        uint8_t* bd = img.data() + img.size() - 3 * 64 * 4;
-        put_bias(bd, c0);
-        put_bias(bd + 64 * 4, c1);
-        put_bias(bd + 128 * 4, c2);
-        return img;
-    });
-}
 
 }  // namespace yh
