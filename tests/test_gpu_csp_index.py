@@ -82,12 +82,11 @@ def _fused(variant, dtype, dev, tile=None, tail=False):
 
 
 def _check(dev, dtype, batch, h, w, seed, tile=None, tail=False, variant="n"):
-    """Fused forward (YH_CSP_TILE read at launch) == per-layer forward; returns the fused engine and
-    {label: plan string} of its c3k2 ops."""
+    """Fused forward (YH_CSP_TILE read at handle creation) == per-layer forward; returns the fused
+    engine and {label: plan string} of its c3k2 ops."""
     ref = _reference(variant, dtype, dev, batch, h, w, seed)
     eng = _fused(variant, dtype, dev, tile, tail)
-    with _env(YH_CSP_TILE=tile):
-        y = eng.forward(_input(dtype, dev, batch, h, w, seed)).clone()
+    y = eng.forward(_input(dtype, dev, batch, h, w, seed)).clone()
     plans = {o["label"]: o["kernel"] for o in eng.ops(batch, h, w) if o["cls"] == "c3k2"}
     assert plans, "no fused c3k2 op"
     if tail:
@@ -140,8 +139,7 @@ def test_tile_walk_crosses_images(gpu, batch):
     assert plans["net.p2.1"] == "c3k2_t10x32", plans
     # another input, graph replay off: the same walk launched eagerly
     eng.set_graph(False)
-    with _env(YH_CSP_TILE="10x32"):
-        y2 = eng.forward(_input(dtype, gpu, batch, h, w, 65)).clone()
+    y2 = eng.forward(_input(dtype, gpu, batch, h, w, 65)).clone()
     assert torch.equal(y2, _reference("n", dtype, gpu, batch, h, w, 65)), "second forward differs"
 
 

@@ -3,7 +3,7 @@ tile shape. Marked gpu.
 
 The kernel takes any run-time TH x TW (pixels are linearised into 32-pixel B tiles), the engine
 picks the tile per launch from the map size, the batch and the CU count (Engine::csp_tile) and
-YH_CSP_TILE=<TH>x<TW> overrides it. The cases cover what the choice can produce: more tiles
+YH_CSP_TILE=<TH>x<TW>, read at handle creation like every switch, overrides it. The cases cover what the choice can produce: more tiles
 than workgroups (the persistent loop, the counted top-of-tile wait across tiles, a part-empty
 last round), tile widths that are no multiple of 16 or 32, tiles that do not divide the map in
 either direction, tail mode, the default choice, and a second forward on another input without
@@ -39,20 +39,6 @@ def _engine(model, dtype, dev, fuse, **env):
     return eng
 
 
-def _forward(eng, x, **env):
-    """One forward with YH_* settings that the library reads at launch time (YH_CSP_TILE)."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return eng.forward(x).clone()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
 def _csp_ops(eng, batch, h, w):
     return [o for o in eng.ops(batch, h, w) if o["cls"] == "c3k2"]
 
@@ -63,7 +49,7 @@ def _check(gpu, dtype, batch, h, w, seed, tile=None, tail=False):
     env = {"YH_CSP_TILE": tile} if tile else {}
     fused = _engine(model, dtype, gpu, True, **({"YH_CSP_TAIL": "1"} if tail else {}), **env)
     plain = _engine(model, dtype, gpu, False)
-    yf = _forward(fused, x, **env)
+    yf = fused.forward(x).clone()
     yp = plain.forward(x).clone()
     csp = _csp_ops(fused, batch, h, w)
     assert csp and not _csp_ops(plain, batch, h, w)
@@ -113,3 +99,35 @@ def test_second_forward_without_graph_replay(gpu):
     x2 = synth.synth_scenes(batch, h, w, seed=59).to(gpu, dtype)
     y2 = fused.forward(x2).clone()
     assert torch.equal(y2, plain.forward(x2)), "second forward differs"
+
+
+def test_switch_binds_at_handle_creation(gpu):
+    """A handle keeps the switches its creation saw. Engine A is created with YH_CSP_TILE=8x12 and
+    runs after the variable is gone; engine B is created without it and runs its first forward
+    with the variable set; C never sees it; P is the per-layer reference (YH_FUSE=0). A must run
+    the 8x12 tile, B must run exactly C's kernels, and all three must equal P bit for bit."""
+    dtype, batch, h, w = torch.bfloat16, 3, 96, 160
+    model = make_model("n")
+    x = synth.synth_scenes(batch, h, w, seed=43).to(gpu, dtype)
+    assert "YH_CSP_TILE" not in os.environ
+    # YH_CONV=0: every dense conv on its first candidate plan, so that the kernel lists do not
+    # depend on the autotuner's timings (the plans are bit-identical either way)
+    a = _engine(model, dtype, gpu, True, YH_CONV="0", YH_CSP_TILE="8x12")
+    b = _engine(model, dtype, gpu, True, YH_CONV="0")
+    c = _engine(model, dtype, gpu, True, YH_CONV="0")
+    p = _engine(model, dtype, gpu, False, YH_CONV="0")
+    ya = a.forward(x).clone()
+    os.environ["YH_CSP_TILE"] = "8x12"
+    try:
+        yb = b.forward(x).clone()
+        torch.cuda.synchronize()
+    finally:
+        del os.environ["YH_CSP_TILE"]
+    yc = c.forward(x).clone()
+    yp = p.forward(x).clone()
+    kernels = lambda e: [o["kernel"] for o in e.ops(batch, h, w)]
+    assert any(o["kernel"] == "c3k2_t8x12" for o in _csp_ops(a, batch, h, w)), kernels(a)
+    assert kernels(b) == kernels(c)
+    assert torch.isfinite(yp.float()).all()
+    for y in (ya, yb, yc):
+        assert torch.equal(y, yp), (y.float() - yp.float()).abs().max().item()

@@ -156,30 +156,15 @@ def test_attention_lds_kernel_equals_per_wave_kernel(gpu, variant, dtype, batch,
     """misc.hip psa_attention_lds (K / V staged in LDS once per workgroup, chunks of 256 keys)
     runs psa_attention_mfma's per-16-key-block arithmetic in the same order: bit-identical, also
     over several chunks (x at 1280: 1600 tokens) and with a partial last block (224: 49 tokens).
-    YH_ATTN_LDS is read at launch, so each engine captures its own kernel."""
+    YH_ATTN_LDS, like every switch, is read at handle creation: each engine keeps its own kernel."""
     model = make_model(variant)
     x = synth.synth_scenes(batch, size, size, seed=33).to(gpu, dtype)
     ys = []
-    old_full = os.environ.get("YH_ATTN_FULL")
-    os.environ["YH_ATTN_FULL"] = "0"   # the chunked kernel, not the whole-K/V one, where both apply
-    try:
-        for v in ("0", "1"):
-            old = os.environ.get("YH_ATTN_LDS")
-            os.environ["YH_ATTN_LDS"] = v
-            try:
-                eng = _engine(model, dtype, gpu, True)
-                ys.append(eng.forward(x).clone())
-                torch.cuda.synchronize()
-            finally:
-                if old is None:
-                    del os.environ["YH_ATTN_LDS"]
-                else:
-                    os.environ["YH_ATTN_LDS"] = old
-    finally:
-        if old_full is None:
-            del os.environ["YH_ATTN_FULL"]
-        else:
-            os.environ["YH_ATTN_FULL"] = old_full
+    for v in ("0", "1"):
+        # YH_ATTN_FULL=0: the chunked kernel, not the whole-K/V one, where both apply
+        eng = _engine(model, dtype, gpu, True, YH_ATTN_FULL="0", YH_ATTN_LDS=v)
+        ys.append(eng.forward(x).clone())
+        torch.cuda.synchronize()
     assert torch.isfinite(ys[0].float()).all()
     assert torch.equal(ys[0], ys[1])
 
@@ -197,18 +182,9 @@ def test_attention_full_kernel_equals_chunked_kernel_and_pe_add(gpu, variant, dt
     x = synth.synth_scenes(batch, size, size, seed=34).to(gpu, dtype)
     ys = []
     for env in ({"YH_ATTN_FULL": "0"}, {"YH_ATTN_FULL": "1"}, {"YH_ATTN_FULL": "1", "YH_ATTN_NW": "16", "YH_ATTN_QS": "1"}):
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
-            eng = _engine(model, dtype, gpu, True)
-            ys.append(eng.forward(x).clone())
-            torch.cuda.synchronize()
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    del os.environ[k]
-                else:
-                    os.environ[k] = v
+        eng = _engine(model, dtype, gpu, True, **env)
+        ys.append(eng.forward(x).clone())
+        torch.cuda.synchronize()
     assert torch.isfinite(ys[0].float()).all()
     for y in ys[1:]:
         assert torch.equal(ys[0], y), (ys[0].float() - y.float()).abs().max().item()
@@ -221,24 +197,15 @@ def test_sppf_kernel_equals_three_maxpools(gpu, variant, dtype, batch, size):
     halved until the planes fit the LDS) with the default and 1, 2, 4 and 8 chunks (YH_SPPF_CPW;
     8 fits at 20x20, 40x40 falls back to 2) is bit-identical to three maxpool5 launches
     (YH_SPPF_FUSED=0).
-    Both switches are read at launch."""
+    Both switches are read at handle creation."""
     model = make_model(variant)
     x = synth.synth_scenes(batch, size, size, seed=35).to(gpu, dtype)
     ys = []
     for env in ({"YH_SPPF_FUSED": "0"}, {"YH_SPPF_CPW": "1"}, {}, {"YH_SPPF_CPW": "2"}, {"YH_SPPF_CPW": "4"},
                 {"YH_SPPF_CPW": "8"}):
-        old = {k: os.environ.get(k) for k in ("YH_SPPF_FUSED", "YH_SPPF_CPW")}
-        os.environ.update(env)
-        try:
-            eng = _engine(model, dtype, gpu, True)
-            ys.append(eng.forward(x).clone())
-            torch.cuda.synchronize()
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
+        eng = _engine(model, dtype, gpu, True, **env)
+        ys.append(eng.forward(x).clone())
+        torch.cuda.synchronize()
     assert torch.isfinite(ys[0].float()).all()
     for yv in ys[1:]:
         assert torch.equal(ys[0], yv)
@@ -251,22 +218,14 @@ def test_c3k_row_bands_equal_per_layer_launches(gpu, bands):
     region fits, 20 = one row each at 20x20, uneven splits, a last band with no rows; the 40x40
     h = 32 block takes at least the 10 bands its regions need and the 20x20 h = 64 blocks at least
     the 4 bands of their SPLIT mode, the only mode h = 64 runs in) is bit-identical to the seven
-    per-layer launches. YH_C3K_BANDS is read at launch."""
+    per-layer launches. YH_C3K_BANDS is read at handle creation."""
     model = make_model("n")
     x = synth.synth_scenes(2, 640, 640, seed=38).to(gpu, torch.bfloat16)
     plain = _engine(model, torch.bfloat16, gpu, True, YH_C3K="0")
     yp = plain.forward(x).clone()
-    old = os.environ.get("YH_C3K_BANDS")
-    os.environ["YH_C3K_BANDS"] = bands
-    try:
-        fused = _engine(model, torch.bfloat16, gpu, True)
-        yf = fused.forward(x).clone()
-        torch.cuda.synchronize()
-    finally:
-        if old is None:
-            del os.environ["YH_C3K_BANDS"]
-        else:
-            os.environ["YH_C3K_BANDS"] = old
+    fused = _engine(model, torch.bfloat16, gpu, True, YH_C3K_BANDS=bands)
+    yf = fused.forward(x).clone()
+    torch.cuda.synchronize()
     assert [u["cls"] for u in fused.units(2, 640, 640)].count("c3k") == 3
     assert torch.equal(yf, yp), (yf.float() - yp.float()).abs().max().item()
 

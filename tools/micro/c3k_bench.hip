@@ -2,6 +2,7 @@
 // the per-workgroup phase times from the kernel's stamps (YH_ABLATION build; stamps are
 // s_memrealtime, 100 MHz). Random weights / inputs (timing only, no numerics).
 //   ./c3k_bench [B H W hh] ...   (default: v11_n's 640 x 640 batch-32 blocks)
+// YH_C3K_BANDS / YH_C3K_NB (read once in main) set the first band count / cap the ring buffers.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -26,6 +27,8 @@ static unsigned short bf(float v) {
     return (unsigned short)((u + 0x7fff + ((u >> 16) & 1)) >> 16);
 }
 
+static yh::LaunchCtx ctx{};   // the launcher reads only the tuning
+
 static void run(int B, int H, int W, int hh) {
     const int c = 2 * hh;
     int off[9];
@@ -47,24 +50,24 @@ static void run(int B, int H, int W, int hh) {
     CK(hipMemcpy(dx, x.data(), x.size() * 2, hipMemcpyHostToDevice));
     yh::C3kArgs a{};
     a.x = dx; a.ldx = c; a.y = dy; a.ldy = c; a.B = B; a.H = H; a.W = W; a.prm = dp; a.hh = hh;
-    const int bands = yh::c3k_bands(B, H, W, hh);
+    const int bands = yh::c3k_bands(B, H, W, hh, ctx.tune.c3k_bands);
     const int nwg = B * bands;
     CK(hipMalloc(&dt, (size_t)nwg * 24 * 8));
     CK(hipMemset(dt, 0, (size_t)nwg * 24 * 8));
-    for (int r = 0; r < 3; ++r) CK((hipError_t)yh::launch_c3k(yh::BF16, a, 0));
+    for (int r = 0; r < 3; ++r) CK((hipError_t)yh::launch_c3k(yh::BF16, a, ctx, 0));
     CK(hipDeviceSynchronize());
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
     const int reps = 50;
     CK(hipEventRecord(e0));
-    for (int r = 0; r < reps; ++r) CK((hipError_t)yh::launch_c3k(yh::BF16, a, 0));
+    for (int r = 0; r < reps; ++r) CK((hipError_t)yh::launch_c3k(yh::BF16, a, ctx, 0));
     CK(hipEventRecord(e1));
     CK(hipEventSynchronize(e1));
     float ms = 0;
     CK(hipEventElapsedTime(&ms, e0, e1));
     a.trace = dt;
-    CK((hipError_t)yh::launch_c3k(yh::BF16, a, 0));
+    CK((hipError_t)yh::launch_c3k(yh::BF16, a, ctx, 0));
     CK(hipDeviceSynchronize());
     std::vector<unsigned long long> tr((size_t)nwg * 24);
     CK(hipMemcpy(tr.data(), dt, tr.size() * 8, hipMemcpyDeviceToHost));
@@ -96,6 +99,8 @@ static void run(int B, int H, int W, int hh) {
 }
 
 int main(int argc, char** argv) {
+    if (const char* e = getenv("YH_C3K_BANDS")) ctx.tune.c3k_bands = std::max(1, atoi(e));
+    if (const char* e = getenv("YH_C3K_NB")) ctx.tune.c3k_nb = std::max(1, atoi(e));
     if (argc >= 5) {
         for (int i = 1; i + 3 < argc; i += 4) run(atoi(argv[i]), atoi(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3]));
     } else {

@@ -515,29 +515,25 @@ static int ck_fit_bands(int hh, int H, int W, int r) {
 }
 
 template <typename T, int HH>
-int launch_c3k_t(const C3kArgs& a0, hipStream_t s) {
+int launch_c3k_t(const C3kArgs& a0, const Tuning& tune, hipStream_t s) {
     C3kArgs a = a0;
-    a.bands = c3k_bands(a.B, a.H, a.W, HH);
+    a.bands = c3k_bands(a.B, a.H, a.W, HH, tune.c3k_bands);
     const int rpx = ck_region_px(a.H, a.W, a.bands), bpx = (a.H + a.bands - 1) / a.bands * a.W;
     // h = 64 runs only in SPLIT mode (phases B..F within 8 tiles, the ring keeping >= 4 buffers
     // beside conv2's band: c3k_lds / c3k_bands admit no other h = 64 shape); as many ring buffers
-    // as the LDS holds (YH_C3K_NB: fewer)
+    // as the LDS holds (Tuning::c3k_nb: fewer)
     const bool split = HH == 64 && ck_live_px(a.H, a.W, a.bands) <= 32 * 8 && ck_lds_px(HH, rpx, 4, bpx) <= 160 * 1024;
     if (HH == 64 && !split) return (int)hipErrorInvalidValue;
     const long long bp = split ? bpx : 0;
     a.nbuf = 2;
     while (a.nbuf < CK_MAXNB && ck_lds_px(HH, rpx, a.nbuf + 1, bp) <= 160 * 1024) ++a.nbuf;
-    if (const char* e = getenv("YH_C3K_NB")) a.nbuf = std::max(split ? 4 : 2, std::min(a.nbuf, atoi(e)));
+    if (tune.c3k_nb > 0) a.nbuf = std::max(split ? 4 : 2, std::min(a.nbuf, tune.c3k_nb));
     const long long lds = ck_lds_px(HH, rpx, a.nbuf, bp);
     if (c3k_lds(a.H, a.W, HH) == 0 || ck_live_px(a.H, a.W, a.bands) > 32 * CK_NW || rpx > 2 * 32 * CK_NW ||
         lds > 160 * 1024 || a.B < 1 || a.ldx % 8 || a.ldy % 8)
         return (int)hipErrorInvalidValue;
     auto k = &c3k_fused<T, HH, HH == 64>;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(k), 160 * 1024)) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)(a.B * a.bands)), dim3(CK_THREADS), (int)lds, s, a);
     return (int)hipGetLastError();
 }
@@ -583,26 +579,26 @@ int c3k_lds(int H, int W, int hh) {
 
 int c3k_region_px(int H, int W, int bands) { return ck_region_px(H, W, bands); }
 
-int c3k_bands(int B, int H, int W, int hh) {
+int c3k_bands(int B, int H, int W, int hh, int first) {
     // enough workgroups for the chip (>= 128) with bands of >= CK_MINRB rows, then as many
-    // more as the regions need to fit; YH_C3K_BANDS overrides the first choice
+    // more as the regions need to fit; first > 0 overrides the first choice
     int r = std::max(1, std::min((128 + B - 1) / B, H / CK_MINRB));
-    if (const char* e = getenv("YH_C3K_BANDS")) r = std::max(1, std::min(atoi(e), H));
+    if (first > 0) r = std::max(1, std::min(first, H));
     if (hh == 64)
         if (const int rs = ck_split_bands(H, W, r)) return rs;
     return ck_fit_bands(hh, H, W, r);
 }
 
-int launch_c3k(int dtype, const C3kArgs& a, hipStream_t s) {
+int launch_c3k(int dtype, const C3kArgs& a, const LaunchCtx& ctx, hipStream_t s) {
     if (a.hh == 32) {
         switch (dtype) {
-            case F16: return launch_c3k_t<_Float16, 32>(a, s);
-            case BF16: return launch_c3k_t<__bf16, 32>(a, s);
+            case F16: return launch_c3k_t<_Float16, 32>(a, ctx.tune, s);
+            case BF16: return launch_c3k_t<__bf16, 32>(a, ctx.tune, s);
         }
     } else if (a.hh == 64) {
         switch (dtype) {
-            case F16: return launch_c3k_t<_Float16, 64>(a, s);
-            case BF16: return launch_c3k_t<__bf16, 64>(a, s);
+            case F16: return launch_c3k_t<_Float16, 64>(a, ctx.tune, s);
+            case BF16: return launch_c3k_t<__bf16, 64>(a, ctx.tune, s);
         }
     }
     return (int)hipErrorInvalidValue;

@@ -530,12 +530,7 @@ int launch_csp_t(const CspArgs& a, int grid, hipStream_t s) {
     if (!csp_span_ok(a.TH, a.TW, a.W, a.ldx, a.ldy) || a.nth * a.ntw != a.tiles) return (int)hipErrorInvalidValue;
 #define YH_CSP_CASE(NI, NC, NO)                                                                              \
     if (a.ni == NI && a.nc == NC && a.no == NO) {                                                            \
-        static bool attr = false;                                                                            \
-        if (!attr) {                                                                                         \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&csp_fused<T, NI, NC, NO>),              \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);               \
-            attr = true;                                                                                     \
-        }                                                                                                    \
+        if (int rc = lds_optin(reinterpret_cast<const void*>(&csp_fused<T, NI, NC, NO>), 160 * 1024)) return rc; \
         hipLaunchKernelGGL((csp_fused<T, NI, NC, NO>), dim3((unsigned)grid), dim3(CSP_THREADS), lds, s, a); \
         return (int)hipGetLastError();                                                                       \
     }

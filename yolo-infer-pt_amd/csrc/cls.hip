@@ -297,12 +297,7 @@ int launch_cls_head_t(const ClsHeadArgs& a, hipStream_t s) {
     if (a.B <= 0 || lds <= 0 || a.G != cls_head_group(a.K, a.HW) || a.G * a.HW > 128 || a.N % 128 || a.wld < a.K ||
         a.wld % 16 || a.ldx % 8)
         return (int)hipErrorInvalidValue;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cls_head<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(&cls_head<T>), 160 * 1024)) return rc;
     hipLaunchKernelGGL((cls_head<T>), dim3((unsigned)((a.B + a.G - 1) / a.G)), dim3(CLS_THREADS), lds, s, a);
     return (int)hipGetLastError();
 }
@@ -313,12 +308,7 @@ int launch_cls_fc_t(const ClsFcArgs& a, hipStream_t s) {
     if (a.B <= 0 || a.nc <= 0 || a.K % 8 || a.wld < a.K || a.wld % 8 || a.ldz < a.nc || lds > 160 * 1024 ||
         (a.B + CLS_FC_TB - 1) / CLS_FC_TB > 65535)
         return (int)hipErrorInvalidValue;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cls_fc<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(&cls_fc<T>), 160 * 1024)) return rc;
     hipLaunchKernelGGL((cls_fc<T>), dim3((unsigned)((a.nc + CLS_FC_TN - 1) / CLS_FC_TN), (unsigned)((a.B + CLS_FC_TB - 1) / CLS_FC_TB)),
                        dim3(256), lds, s, a);
     int rc = (int)hipGetLastError();

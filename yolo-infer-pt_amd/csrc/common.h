@@ -3,12 +3,54 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+#include <set>
+#include <utility>
+
 #include "yolo_hip.h"   // yh_track_params (launch_track)
 
 namespace yh {
 
 enum DType { F32 = 0, F16 = 1, BF16 = 2 };
 inline int dtype_size(int dt) { return dt == F32 ? 4 : 2; }
+
+// Kernel-variant switches of one handle (Options::from_env fills them at yh_create; INTEGRATION.md
+// lists the variables). Every variant of a kernel computes the same bits; 0 in a count or a tile
+// field leaves the choice to the launcher.
+struct Tuning {
+    bool attn_full = true;   // whole-K/V attention kernel where it applies (else chunked + pe_add)
+    bool attn_lds = true;    // chunked attention: the LDS kernel (else the per-wave one)
+    int attn_nw = 0;         // whole-K/V attention: waves per workgroup, 8 or 16
+    int attn_qs = 0;         //   and workgroups per (image, head)
+    bool sppf_fused = true;  // one SPPF launch (else three maxpool5 launches)
+    int sppf_cpw = 0;        // fused SPPF: 8-channel chunks per workgroup
+    int sppf_xcd = 1;        //   and an image's workgroups on one XCD (0: hardware order)
+    int c3k_bands = 0;       // fused C3k: first band count tried
+    int c3k_nb = 0;          //   and an upper bound on its weight ring buffers
+    int csp_th = 0, csp_tw = 0;   // fused C3k2: output tile, used where csp_lds admits it
+    int boxdfl_tpw = 0;      // box_dfl: 32-pixel tiles per wave, 1, 2 or 4 (0: BOX_DFL_TPW)
+    bool pwc_warm = true;    // pw_chain: L2 warm-up of the weights in the prologue
+};
+// what a launcher needs from its handle beside the kernel arguments
+struct LaunchCtx {
+    int num_cus;
+    Tuning tune;
+};
+
+// Opt `kernel` in to `bytes` of dynamic LDS (above the 64 KB default) on the current device. The
+// attribute is per device and a process may hold handles on several, driven from several threads:
+// the pairs already set are kept under a lock. Returns the hipError_t, 0 once the pair is set.
+inline int lds_optin(const void* kernel, int bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<int, const void*>> done;
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return (int)e;
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({dev, kernel})) return 0;
+    if (hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) return (int)e;
+    done.insert({dev, kernel});
+    return 0;
+}
 
 // ACT_SILU_F64: SiLU of (K sum + bias) evaluated in fp64 and rounded once to fp32; only the fp32
 // handle's classifier head conv (conv_gemm's EXACT instances), whose output is held to one ulp
@@ -147,10 +189,6 @@ struct NmsArgs {
 #endif
 };
 
-// Dense-conv kernel of the fp32 handle (conv.hip). The 16-bit handles run the
-// conv_mx family (conv_mx.h).
-enum ConvKernel { CONV_GEMM = 0 };
-
 // Fused cls branch of the detect head (nets/nn.py:244-252), one launch for all levels:
 //   DWConv 3x3 + SiLU -> Conv 1x1 + SiLU -> DWConv 3x3 + SiLU -> Conv 1x1 + SiLU
 //   -> Conv2d 1x1 (+ bias)
@@ -210,9 +248,10 @@ struct C3kArgs {
 int c3k_prm_bytes(int hh);
 void c3k_offsets(int hh, int (&off)[9]);   // w1, w2, residual convs, w3, b1, b2, residual biases, b3, total
 int c3k_lds(int H, int W, int hh);   // 0: no band split fits
-int c3k_bands(int B, int H, int W, int hh);   // row bands per image (one workgroup each)
+// row bands per image (one workgroup each); first > 0: the band count tried first (Tuning::c3k_bands)
+int c3k_bands(int B, int H, int W, int hh, int first);
 int c3k_region_px(int H, int W, int bands);   // LDS pixels of a band's region (band + 4-row halo)
-int launch_c3k(int dtype, const C3kArgs& a, hipStream_t s);
+int launch_c3k(int dtype, const C3kArgs& a, const LaunchCtx& ctx, hipStream_t s);
 
 // Box tail of the detect head, one launch for all levels: the last box conv (Conv2d 1x1
 // + bias, nets/nn.py:241) with DFL (nn.py:222-225), make_anchors (utils/util.py:85-96) and
@@ -267,7 +306,7 @@ inline bool csp_span_ok(int TH, int TW, int W, int ldx, int ldy) {
     return W > 0 && ld > 0 && W < (1 << 24) && ld < (1 << 24) && px < (1 << 24) && (px * ld + ld) * 2 < (1ll << 31);
 }
 
-constexpr int BOX_DFL_TPW = 2;       // 32-pixel tiles per wave (4 waves per workgroup; YH_BOXDFL_TPW: 1 / 2 / 4)
+constexpr int BOX_DFL_TPW = 2;       // 32-pixel tiles per wave (4 waves per workgroup; Tuning::boxdfl_tpw: 1 / 2 / 4)
 int launch_box_dfl(int dtype, const BoxDflArgs& a, hipStream_t s);
 
 // Pointwise chain (pwchain.hip): consecutive 1x1 convs of one map as one launch. A workgroup
@@ -365,13 +404,11 @@ int launch_set_io_cls(void** io, const void* x, float* probs, float* logits, flo
                       hipStream_t s);
 
 // launchers (return hipError_t as int)
-bool conv_kernel_ok(int dtype, int kern, const ConvArgs& a);
-int launch_conv(int dtype, int kern, int BM, int BN, const ConvArgs& a, hipStream_t s);
-int conv_lds_bytes(int dtype, int BM, int BN, int Kp);
+int launch_conv(int dtype, int BM, int BN, const ConvArgs& a, hipStream_t s);   // fp32 handle only (conv.hip)
 int launch_first_conv(int dtype, const FirstConvArgs& a, int B, hipStream_t s);
 int launch_dwconv(int dtype, const DwArgs& a, hipStream_t s);
-int launch_sppf(int dtype, const PoolArgs& a, hipStream_t s);
-int launch_attention(int dtype, const AttnArgs& a, int B, hipStream_t s);
+int launch_sppf(int dtype, const PoolArgs& a, const LaunchCtx& ctx, hipStream_t s);
+int launch_attention(int dtype, const AttnArgs& a, int B, const LaunchCtx& ctx, hipStream_t s);
 int launch_decode(int dtype, const DecodeArgs& a, hipStream_t s);
 int launch_set_io(void** io, const void* x, void* y, hipStream_t s);
 int launch_nms(int dtype, const NmsArgs& a, hipStream_t s);

@@ -225,28 +225,18 @@ template <typename T, int BM, int BN>
 int launch_conv_t(const ConvArgs& a, hipStream_t s) {
     using SM = ConvSmem<T, BM, BN>;
     const int lds = SM::REGION + (a.Kp / 8) * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm<T, BM, BN>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     if (a.act == ACT_SILU_F64) {
         // instantiated for the one layer that asks for it: fp32, 128-cout tiles of 64 or 128 pixels
         // (Net::conv_args keeps to those; the 256-pixel instance would spill)
         if constexpr (sizeof(T) == 4 && BN == 128 && BM <= 128) {
-            static bool attr_x = false;
-            if (!attr_x) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm<T, BM, BN, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_x = true;
-            }
+            if (int rc = lds_optin(reinterpret_cast<const void*>(&conv_gemm<T, BM, BN, true>), 160 * 1024)) return rc;
             hipLaunchKernelGGL((conv_gemm<T, BM, BN, true>), dim3(a.gm * a.gn), dim3(NT_), lds, s, a);
             return (int)hipGetLastError();
         } else {
             return (int)hipErrorInvalidValue;
         }
     }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(&conv_gemm<T, BM, BN>), 160 * 1024)) return rc;
     hipLaunchKernelGGL((conv_gemm<T, BM, BN>), dim3(a.gm * a.gn), dim3(NT_), lds, s, a);
     return (int)hipGetLastError();
 }
@@ -382,81 +372,14 @@ __global__ __launch_bounds__(STEM_TW) void conv_first(const FirstConvArgs p) {
     }
 }
 
-// 16-bit stem on MFMA: K = 27 taps padded to 32 = one v_mfma_f32_16x16x32 per
-// 16 pixels x 16 couts. A = weights (built once per wave from the fp32 [27][Cout]
-// pack), B = the im2col column of 16 pixels gathered from the LDS patch.
-template <typename T, typename U, int NT>
-__global__ __launch_bounds__(STEM_TW) void conv_first_mfma(const FirstConvArgs p) {
-    __shared__ float patch[9][STEM_SEG];
-    const int wo0 = blockIdx.x * STEM_TW, ho = blockIdx.y, n = blockIdx.z;
-    const U* x = reinterpret_cast<const U*>(p.io[0]);
-    const int col0 = 2 * wo0 - 8;
-    stem_stage<T, U>(x, p, n, ho, col0, patch);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int fr = lane & 15, g = lane >> 4;
-    // A fragments: weights[cout = 16i + fr][k = 8g + j]
-    uint4 wf[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        float f[8];
-        const int co = 16 * i + fr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int k = 8 * g + j;
-            f[j] = (k < 27 && co < p.Cout) ? p.w[k * p.Cout + co] : 0.f;
-        }
-        wf[i] = f_to_chunk<T>(f).v[0];
-    }
-    float bv[NT][4];
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int co = 16 * i + 4 * g + r;
-            bv[i][r] = co < p.Cout ? p.bias[co] : 0.f;
-        }
-    __syncthreads();
-#pragma unroll
-    for (int pg = 0; pg < STEM_TW / 2 / 16; ++pg) {   // 4 groups of 16 pixels per wave
-        const int px = wave * (STEM_TW / 2) + pg * 16 + fr;
-        const int lc = 2 * px - 1 + 8;
-        float f[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int k = 8 * g + j;
-            const int seg = k / 3, kw = k - seg * 3;
-            f[j] = k < 27 ? patch[seg][lc + kw] : 0.f;
-        }
-        const uint4 xf = f_to_chunk<T>(f).v[0];
-        const int wo = wo0 + px;
-        const long long m = ((long long)n * p.Ho + ho) * p.Wo + wo;
-        T* out = reinterpret_cast<T*>(p.out) + m * p.ldo;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-            Mma<T>::step(acc, &wf[i], &xf);
-            const int co = 16 * i + 4 * g;
-            if (wo < p.Wo && co < p.Cout) {
-                unsigned u[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = acc[r] + bv[i][r];
-                    if (p.act == ACT_SILU) v = silu<T>(v);
-                    u[r] = (unsigned short)__builtin_bit_cast(short, fromf<T>(v));
-                }
-                *reinterpret_cast<uint2*>(out + co) = make_uint2(u[0] | (u[1] << 16), u[2] | (u[3] << 16));
-            }
-        }
-    }
-}
-
 // 16-bit stem, 2-D tiles: a workgroup = STEM2_TR output rows x STEM2_TW pixels.
 // The 2*TR+1 input rows of each channel are staged once as T (the values the
 // MFMA consumes), so neighbouring output rows share their overlap row in LDS
 // (input read ~(2TR+1)/(2TR) times instead of 1.5x) and every thread keeps
-// STEM2_NCH 16-B loads in flight. Same k order (ci, kh, kw) and epilogue as
-// conv_first_mfma -> identical outputs.
-constexpr int STEM2_TW = 160, STEM2_NT = 256;
+// STEM2_NCH 16-B loads in flight. K = 27 taps padded to 32 = one v_mfma_f32_16x16x32
+// per 16 pixels x 16 couts, k order (ci, kh, kw). The only 16-bit stem kernel; it is
+// launched with STEM2_R rows per workgroup.
+constexpr int STEM2_TW = 160, STEM2_NT = 256, STEM2_R = 4;
 // pixel groups per wave unrolled (all 10: every group's LDS gathers and MFMA in flight
 // together; 2 -> 10 measured 59.3 -> 55.9 us for the v11_n b32 stem)
 #ifndef STEM2_UNROLL
@@ -577,33 +500,18 @@ __global__ __launch_bounds__(STEM2_NT) void conv_first_tile(const FirstConvArgs 
 
 template <typename T, typename U>
 int launch_first_tu(const FirstConvArgs& a, int B, hipStream_t s) {
-    const dim3 grid((a.Wo + STEM_TW - 1) / STEM_TW, a.Ho, B);
     if constexpr (sizeof(T) == 2) {
-        static const bool tile = [] { const char* e = getenv("YH_STEM"); return !e || atoi(e) != 1; }();
-        if (tile) {
-            static const int tr = [] { const char* e = getenv("YH_STEM_TR"); return e ? atoi(e) : 4; }();
-            const dim3 g2((a.Wo + STEM2_TW - 1) / STEM2_TW, (a.Ho + tr - 1) / tr, B);
-#define YH_ST(R)                                                                                              \
-            switch ((a.Cout + 15) / 16) {                                                                     \
-                case 1: hipLaunchKernelGGL((conv_first_tile<T, U, 1, R>), g2, dim3(STEM2_NT), 0, s, a); break; \
-                case 2: hipLaunchKernelGGL((conv_first_tile<T, U, 2, R>), g2, dim3(STEM2_NT), 0, s, a); break; \
-                case 4: hipLaunchKernelGGL((conv_first_tile<T, U, 4, R>), g2, dim3(STEM2_NT), 0, s, a); break; \
-                case 6: hipLaunchKernelGGL((conv_first_tile<T, U, 6, R>), g2, dim3(STEM2_NT), 0, s, a); break; \
-                default: return (int)hipErrorInvalidValue;                                                    \
-            }
-            if (tr == 2) { YH_ST(2) } else if (tr == 8) { YH_ST(8) } else { YH_ST(4) }
-#undef YH_ST
-            return (int)hipGetLastError();
-        }
+        const dim3 g2((a.Wo + STEM2_TW - 1) / STEM2_TW, (a.Ho + STEM2_R - 1) / STEM2_R, B);
         switch ((a.Cout + 15) / 16) {
-            case 1: hipLaunchKernelGGL((conv_first_mfma<T, U, 1>), grid, dim3(STEM_TW), 0, s, a); break;
-            case 2: hipLaunchKernelGGL((conv_first_mfma<T, U, 2>), grid, dim3(STEM_TW), 0, s, a); break;
-            case 4: hipLaunchKernelGGL((conv_first_mfma<T, U, 4>), grid, dim3(STEM_TW), 0, s, a); break;
-            case 6: hipLaunchKernelGGL((conv_first_mfma<T, U, 6>), grid, dim3(STEM_TW), 0, s, a); break;
+            case 1: hipLaunchKernelGGL((conv_first_tile<T, U, 1, STEM2_R>), g2, dim3(STEM2_NT), 0, s, a); break;
+            case 2: hipLaunchKernelGGL((conv_first_tile<T, U, 2, STEM2_R>), g2, dim3(STEM2_NT), 0, s, a); break;
+            case 4: hipLaunchKernelGGL((conv_first_tile<T, U, 4, STEM2_R>), g2, dim3(STEM2_NT), 0, s, a); break;
+            case 6: hipLaunchKernelGGL((conv_first_tile<T, U, 6, STEM2_R>), g2, dim3(STEM2_NT), 0, s, a); break;
             default: return (int)hipErrorInvalidValue;
         }
         return (int)hipGetLastError();
     }
+    const dim3 grid((a.Wo + STEM_TW - 1) / STEM_TW, a.Ho, B);
     switch (a.Cout) {
         case 16: hipLaunchKernelGGL((conv_first<T, U, 2>), grid, dim3(STEM_TW), 0, s, a); break;
         case 24: hipLaunchKernelGGL((conv_first<T, U, 3>), grid, dim3(STEM_TW), 0, s, a); break;
@@ -1004,22 +912,10 @@ int launch_dw_t(const DwArgs& a, hipStream_t s) {
 
 }  // namespace
 
-int conv_lds_bytes(int dtype, int BM, int BN, int Kp) {
-    const int es = dtype_size(dtype);
-    const int main_b = (2 * BM * LDK + 2 * BN * LDK) * es;
-    const int epi = BM * (BN + 8) * es;
-    return (main_b > epi ? main_b : epi) + (Kp / 8) * 4;
-}
-
 // Dense convs of the fp32 handle (the exact-parity mode): conv_gemm on the exact
 // f32 MFMA. The 16-bit handles run the conv_mx family (conv_mx.hip).
-bool conv_kernel_ok(int dtype, int kern, const ConvArgs& a) {
-    (void)a;
-    return dtype == F32 && kern == CONV_GEMM;
-}
-
-int launch_conv(int dtype, int kern, int BM, int BN, const ConvArgs& a, hipStream_t s) {
-    if (!conv_kernel_ok(dtype, kern, a)) return (int)hipErrorInvalidValue;
+int launch_conv(int dtype, int BM, int BN, const ConvArgs& a, hipStream_t s) {
+    if (dtype != F32) return (int)hipErrorInvalidValue;
     return launch_conv_bm<float>(BM, BN, a, s);
 }
 

@@ -1266,13 +1266,8 @@ namespace {
 
 template <typename T, int KS, int S, int NA, int MB, int WN, int WM, int NCB>
 int launch_mx_t(const MxPlan& pl, const MxArgs& a, hipStream_t s) {
-    static bool attr = false;
     auto k = &conv_mx<T, KS, S, NA, MB, WN, WM, NCB>;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(k), 160 * 1024)) return rc;
     hipLaunchKernelGGL(k, dim3(pl.grid), dim3(64 * WN * WM), pl.lds, s, a);
     return (int)hipGetLastError();
 }
@@ -1298,13 +1293,8 @@ int launch_mx_cfg(const MxPlan& pl, const MxArgs& a, hipStream_t s) {
 
 template <typename T, int KS, int S, int NA, int MB, int NCB, int NBI, int NBUF, int NW>
 int launch_mxr_t(const MxPlan& pl, const MxArgs& a, hipStream_t s) {
-    static bool attr = false;
     auto k = &conv_mxr<T, KS, S, NA, MB, NCB, NBI, NW, NBUF>;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(k), 160 * 1024)) return rc;
     hipLaunchKernelGGL(k, dim3(pl.grid), dim3(64 * NW), pl.lds, s, a);
     return (int)hipGetLastError();
 }

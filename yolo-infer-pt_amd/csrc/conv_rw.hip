@@ -711,13 +711,8 @@ template <typename T, int S, int CIN, int NCG, int NPG, int MB, int TW, int NS, 
 int launch_rw_t(const MxPlan& pl, const MxArgs& a, hipStream_t s) {
     const RwGeo g = rw_geo(S, CIN, NCG, NPG, MB, TW, RES, NKC);
     if (g.nbi != pl.nbi || NS * g.slot + g.red + g.epi != pl.lds || RES != (a.res != nullptr)) return (int)hipErrorInvalidValue;
-    static bool attr = false;
     auto k = &conv_rw<T, S, CIN, NCG, NPG, MB, TW, NS, RES, NKC>;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(k), 160 * 1024)) return rc;
     hipLaunchKernelGGL(k, dim3(pl.grid), dim3(64 * NCG * NKC * NPG), pl.lds, s, a);
     return (int)hipGetLastError();
 }

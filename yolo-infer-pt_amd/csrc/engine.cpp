@@ -35,6 +35,8 @@ static int create(const yh_variant* v, int device, int dtype, yh_handle** out, i
         n.task = task;
         n.opt = yh::Options::from_env();
         n.device = device;
+        HIPCHECK(hipDeviceGetAttribute(&n.num_cus, hipDeviceAttributeMultiprocessorCount, device));
+        yh::require(n.num_cus > 0, "device reports no compute units");
         n.dtype = dtype;
         n.es = yh::dtype_size(dtype);
         n.build();

@@ -684,12 +684,7 @@ static int launch_head_cls_t(const HeadClsArgs& a, hipStream_t s) {
         grid += a.B * v.tiles;
         lds = lds > b ? lds : b;
     }
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&head_cls<T>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(&head_cls<T>), 160 * 1024)) return rc;
     hipLaunchKernelGGL((head_cls<T>), dim3((unsigned)grid), dim3(HEAD_CLS_THREADS), lds, s, a);
     return (int)hipGetLastError();
 }

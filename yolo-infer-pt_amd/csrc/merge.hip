@@ -283,12 +283,7 @@ int launch_merge(const float* dets, const int* counts, int tiles, int max_det, c
                  int max_out, float* out, int* out_counts, hipStream_t s) {
     // arguments were checked by yh_merge (yh_merge_check): 1 <= max_tiles, max_tiles * max_det <= YH_MERGE_MAX_CAND
     if (images <= 0) return 0;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(merge_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)MERGE_LDS);
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(merge_kernel), (int)MERGE_LDS)) return rc;
     hipLaunchKernelGGL(merge_kernel, dim3(images), dim3(MERGE_T), MERGE_LDS, s, dets, counts, tiles, max_det, tile_xf,
                        tile_offsets, image_wh, max_tiles, iou_threshold, max_out, out, out_counts);
     return (int)hipGetLastError();

@@ -131,40 +131,25 @@ __global__ __launch_bounds__(256) void sppf_fused(const PoolArgs a, int cpw, int
 }
 
 template <typename T>
-int launch_sppf_t(const PoolArgs& a, hipStream_t s) {
+int launch_sppf_t(const PoolArgs& a, const LaunchCtx& ctx, hipStream_t s) {
     T* b = reinterpret_cast<T*>(a.buf);
     const int M = a.B * a.H * a.W;
+    const Tuning& tune = ctx.tune;
     if constexpr (sizeof(T) == 2) {
-        // YH_SPPF_FUSED=0 (read per launch): the three maxpool5 launches (the tests compare both)
-        const char* ef = getenv("YH_SPPF_FUSED");
-        if (3 * a.H * a.W * 16 <= 160 * 1024 && a.C % 8 == 0 && !(ef && atoi(ef) == 0)) {
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sppf_fused<T>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_set = true;
-            }
+        // sppf_fused off: the three maxpool5 launches (the tests compare both)
+        if (3 * a.H * a.W * 16 <= 160 * 1024 && a.C % 8 == 0 && tune.sppf_fused) {
+            if (int rc = lds_optin(reinterpret_cast<const void*>(&sppf_fused<T>), 160 * 1024)) return rc;
             // chunks per workgroup: 1 while that gives at most 3 workgroups per CU (v11_n b32: 21.2
             // against 22.8 us for 2; v11_x b16 1280: 81.9 against 90.4), else 2 (v11_s b64: 39.4
-            // against 57.7 us for 1; 4 / 8 ran 47 / 86 us at v11_n in round 4); YH_SPPF_CPW
+            // against 57.7 us for 1; 4 / 8 ran 47 / 86 us at v11_n in round 4); sppf_cpw
             // overrides. Halved until it divides the channels and the three planes fit the LDS.
-            static int ncu = 0;
-            if (!ncu) {
-                int dev = 0;
-                (void)hipGetDevice(&dev);
-                if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-                    ncu = 256;
-            }
-            const char* e = getenv("YH_SPPF_CPW");
-            int cpw = e ? std::max(1, atoi(e)) : (a.B * (a.C / 8) <= 3 * ncu ? 1 : 2);
+            int cpw = tune.sppf_cpw > 0 ? tune.sppf_cpw : (a.B * (a.C / 8) <= 3 * ctx.num_cus ? 1 : 2);
             while (cpw > 1 && ((a.C / 8) % cpw || 3 * a.H * a.W * cpw * 16 > 160 * 1024))
                 cpw >>= 1;
-            // an image's chunk workgroups on one XCD (YH_SPPF_XCD=0: hardware order). r06, v11_n b32:
+            // an image's chunk workgroups on one XCD (sppf_xcd = 0: hardware order). r06, v11_n b32:
             // 20.4 -> 16.3 us, PMC traffic 2.34x -> 0.67x algorithmic; v11_x b16 1280: 83 -> 56 us
-            const char* ex = getenv("YH_SPPF_XCD");
-            const int xcd = ex ? atoi(ex) : 1;
             hipLaunchKernelGGL((sppf_fused<T>), dim3((unsigned)(a.B * (a.C / 8 / cpw))), dim3(256),
-                               3 * a.H * a.W * cpw * (int)sizeof(uint4), s, a, cpw, xcd);
+                               3 * a.H * a.W * cpw * (int)sizeof(uint4), s, a, cpw, tune.sppf_xcd);
             return (int)hipGetLastError();
         }
     }
@@ -700,41 +685,26 @@ __global__ __launch_bounds__(256) void pe_add(const AttnArgs p, int B) {
 }
 
 template <typename T>
-int launch_attention_t(const AttnArgs& a, int B, hipStream_t s) {
+int launch_attention_t(const AttnArgs& a, int B, const LaunchCtx& ctx, hipStream_t s) {
     if (a.dk != DK || a.dh != DH) return (int)hipErrorInvalidValue;
+    const Tuning& tune = ctx.tune;
     if constexpr (sizeof(T) == 2) {
-        // YH_ATTN_LDS=0 (read per launch, so per captured graph): the per-wave kernel, which
-        // the tests compare bit for bit
-        // YH_ATTN_FULL=0 (read per launch): the chunked kernel + pe_add where the full one applies
-        const char* ef = getenv("YH_ATTN_FULL");
-        if (a.T <= AF_TMAX && a.Ws > 0 && a.Hs * a.Ws == a.T && !(ef && atoi(ef) == 0)) {
-            static bool attr = false;
-            if (!attr) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&psa_attention_full<T, 16>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&psa_attention_full<T, 8>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr = true;
-            }
+        // attn_full off: the chunked kernel + pe_add where the full one applies; attn_lds off: the
+        // per-wave chunked kernel. The tests compare all three bit for bit.
+        if (a.T <= AF_TMAX && a.Ws > 0 && a.Hs * a.Ws == a.T && tune.attn_full) {
             // Every wave runs one 16-query block's serial chain over all key blocks, so the launch
             // lasts about one chain when each wave has at most one block and every workgroup a CU
             // of its own (one fits per CU: the K / V staging takes ~86 KB of LDS). Default: 8-wave
             // workgroups, ceil(blocks / 8) per (image, head), when those fit the CUs in one round
             // (v11_n, batch 32: 256 workgroups, 20 us); else 16-wave ones, two per (image, head)
-            // (27-28 us there; at one, 64 workgroups, 39 us). YH_ATTN_NW (8 / 16) and YH_ATTN_QS
+            // (27-28 us there; at one, 64 workgroups, 39 us). attn_nw (8 / 16) and attn_qs
             // (workgroups per (image, head)) override.
-            static int ncu = 0;
-            if (!ncu) {
-                int dev = 0;
-                (void)hipGetDevice(&dev);
-                if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-                    ncu = 256;
-            }
             const int nqb = (a.T + 15) >> 4, pairs = a.heads * B, q8 = (nqb + 7) / 8;
-            const char* ew = getenv("YH_ATTN_NW");
-            const int nw = ew ? (atoi(ew) == 8 ? 8 : AF_NW) : (pairs * q8 <= ncu ? 8 : AF_NW);
-            const char* eq = getenv("YH_ATTN_QS");
-            const int qs = std::max(1, std::min(eq ? atoi(eq) : (nw == 8 ? q8 : 2), (nqb + nw - 1) / nw));
+            const int nw = tune.attn_nw ? (tune.attn_nw == 8 ? 8 : AF_NW) : (pairs * q8 <= ctx.num_cus ? 8 : AF_NW);
+            const int qs = std::max(1, std::min(tune.attn_qs > 0 ? tune.attn_qs : (nw == 8 ? q8 : 2), (nqb + nw - 1) / nw));
+            const void* k = nw == 8 ? reinterpret_cast<const void*>(&psa_attention_full<T, 8>)
+                                    : reinterpret_cast<const void*>(&psa_attention_full<T, AF_NW>);
+            if (int rc = lds_optin(k, 160 * 1024)) return rc;
             if (nw == 8)
                 hipLaunchKernelGGL((psa_attention_full<T, 8>), dim3((unsigned)(a.heads * B * qs)), dim3(64 * 8),
                                    af_lds_bytes(a.T), s, a, B);
@@ -743,8 +713,7 @@ int launch_attention_t(const AttnArgs& a, int B, hipStream_t s) {
                                    af_lds_bytes(a.T), s, a, B);
             return (int)hipGetLastError();
         }
-        const char* e = getenv("YH_ATTN_LDS");
-        if (e && atoi(e) == 0) {
+        if (!tune.attn_lds) {
             const dim3 g((a.T + 63) / 64, a.heads, B);
             hipLaunchKernelGGL((psa_attention_mfma<T>), g, dim3(256), 0, s, a);
         } else {
@@ -980,12 +949,7 @@ int launch_decode_t(const DecodeArgs& a, hipStream_t s) {
             const int lds_in = DEC_A * ((a.box ? 8 : 0) + NCC + 1) * 16, lds_out = (4 + a.nc) * DEC_A * 2;
             const int lds = lds_in > lds_out ? lds_in : lds_out;
             auto kern = a.box ? &head_decode_lds<T, NCC, true> : &head_decode_lds<T, NCC, false>;
-            static bool attr_set[2] = {false, false};
-            if (!attr_set[a.box != 0]) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-                attr_set[a.box != 0] = true;
-            }
+            if (int rc = lds_optin(reinterpret_cast<const void*>(kern), 80 * 1024)) return rc;
             hipLaunchKernelGGL(kern, g, dim3(256), lds, s, a);
             return (int)hipGetLastError();
         }
@@ -1006,20 +970,20 @@ __global__ void set_io(void** io, const void* x, void* y) {
 
 }  // namespace
 
-int launch_sppf(int dtype, const PoolArgs& a, hipStream_t s) {
+int launch_sppf(int dtype, const PoolArgs& a, const LaunchCtx& ctx, hipStream_t s) {
     switch (dtype) {
-        case F32: return launch_sppf_t<float>(a, s);
-        case F16: return launch_sppf_t<_Float16>(a, s);
-        case BF16: return launch_sppf_t<__bf16>(a, s);
+        case F32: return launch_sppf_t<float>(a, ctx, s);
+        case F16: return launch_sppf_t<_Float16>(a, ctx, s);
+        case BF16: return launch_sppf_t<__bf16>(a, ctx, s);
     }
     return (int)hipErrorInvalidValue;
 }
 
-int launch_attention(int dtype, const AttnArgs& a, int B, hipStream_t s) {
+int launch_attention(int dtype, const AttnArgs& a, int B, const LaunchCtx& ctx, hipStream_t s) {
     switch (dtype) {
-        case F32: return launch_attention_t<float>(a, B, s);
-        case F16: return launch_attention_t<_Float16>(a, B, s);
-        case BF16: return launch_attention_t<__bf16>(a, B, s);
+        case F32: return launch_attention_t<float>(a, B, ctx, s);
+        case F16: return launch_attention_t<_Float16>(a, B, ctx, s);
+        case BF16: return launch_attention_t<__bf16>(a, B, ctx, s);
     }
     return (int)hipErrorInvalidValue;
 }

@@ -5,6 +5,8 @@
 // graphs), net_launch.cpp (launch arguments, launch_op, autotuner) and net_debug.cpp (per-op
 // accounting, parity taps); engine.cpp exports the handle's C ABI.
 #pragma once
+#include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <functional>
 #include <map>
@@ -108,8 +110,9 @@ struct GraphKey {
     }
 };
 
-// The library's few environment switches, read once per handle at yh_create
-// (INTEGRATION.md lists them): YH_FUSE=0 turns every cross-layer fusion off (the
+// Every environment switch of the library, read once per handle at yh_create / yh_create_cls and
+// at no later moment (INTEGRATION.md lists them): a handle keeps its switches for its life, on the
+// eager path and in every captured graph alike. YH_FUSE=0 turns every cross-layer fusion off (the
 // bit-identity tests compare both), YH_CSP_TAIL=1 forces the C3k2 tail mode where
 // the whole block would fit one launch (tested the same way), YH_CONV=<k> forces
 // candidate plan k of every 16-bit dense conv, YH_TUNE_LOG=1 prints the tuner's timings,
@@ -117,12 +120,34 @@ struct GraphKey {
 // YH_HCLS_WIDE=0 keeps a 256-channel level's cls branch (v11_n 20x20) as per-layer launches,
 // YH_CLSHEAD=1 runs a classifier's head.conv + cls_pool as one launch (cls_head; bit-identical, compared
 // by the tests; off by default because the two launches measured faster).
+// The kernel-variant switches fill `tune` (common.h Tuning), which the launchers get with the CU
+// count: YH_ATTN_FULL, YH_ATTN_LDS, YH_ATTN_NW, YH_ATTN_QS, YH_SPPF_FUSED, YH_SPPF_CPW, YH_SPPF_XCD,
+// YH_C3K_BANDS, YH_C3K_NB, YH_CSP_TILE, YH_BOXDFL_TPW, YH_PWC_WARM.
 struct Options {
     bool fuse = true, csp_tail = false, tune_log = false, c3k = true, hcls_wide = true, pw_chain = true;
     bool cls_head = false;
     int conv_force = -1;
+    Tuning tune;
     static Options from_env() {
         Options o;
+        Tuning& t = o.tune;
+        if (const char* e = getenv("YH_ATTN_FULL")) t.attn_full = atoi(e) != 0;
+        if (const char* e = getenv("YH_ATTN_LDS")) t.attn_lds = atoi(e) != 0;
+        if (const char* e = getenv("YH_ATTN_NW")) t.attn_nw = atoi(e) == 8 ? 8 : 16;
+        // a count that is set is at least 1; the launchers clamp it to what the shape allows
+        if (const char* e = getenv("YH_ATTN_QS")) t.attn_qs = std::max(1, atoi(e));
+        if (const char* e = getenv("YH_SPPF_FUSED")) t.sppf_fused = atoi(e) != 0;
+        if (const char* e = getenv("YH_SPPF_CPW")) t.sppf_cpw = std::max(1, atoi(e));
+        if (const char* e = getenv("YH_SPPF_XCD")) t.sppf_xcd = atoi(e);
+        if (const char* e = getenv("YH_C3K_BANDS")) t.c3k_bands = std::max(1, atoi(e));
+        if (const char* e = getenv("YH_C3K_NB")) t.c3k_nb = std::max(1, atoi(e));
+        if (const char* e = getenv("YH_CSP_TILE")) {
+            int th = 0, tw = 0;
+            if (sscanf(e, "%dx%d", &th, &tw) == 2 && th > 0 && tw > 0) { t.csp_th = th; t.csp_tw = tw; }
+        }
+        if (const char* e = getenv("YH_BOXDFL_TPW"))
+            if (const int v = atoi(e); v == 1 || v == 2 || v == 4) t.boxdfl_tpw = v;
+        if (const char* e = getenv("YH_PWC_WARM")) t.pwc_warm = atoi(e) != 0;
         if (const char* e = getenv("YH_FUSE")) o.fuse = atoi(e) != 0;
         if (const char* e = getenv("YH_PWCHAIN")) o.pw_chain = atoi(e) != 0;
         if (const char* e = getenv("YH_CSP_TAIL")) o.csp_tail = atoi(e) != 0;
@@ -162,7 +187,8 @@ struct Net {
     std::map<GraphKey, std::vector<MxChoice>> conv_kern;
     const std::vector<MxChoice>* cur_kern = nullptr;
     int force_kern = -1;   // candidate index (testing); -1 = autotune
-    int num_cus = 0;
+    int num_cus = 0;       // queried at create
+    LaunchCtx ctx() const { return LaunchCtx{num_cus, opt.tune}; }
     // plan string of every fused C3k2 launch made so far: c3k2_t<TH>x<TW>, per shape and op index
     std::map<std::pair<GraphKey, int>, std::string> csp_plan;
     // the forward at one shape: which ops are launched (fused blocks pick per shape) and their
@@ -238,7 +264,7 @@ struct Net {
 
     // ---------------------------------------------------------- net_launch.cpp
     static int anchor_off(int l, int H, int W);
-    static bool csp_tile(int ni, int nc, int no, int B, int H, int W, int cus, int& TH, int& TW);
+    static bool csp_tile(const Tuning& tune, int ni, int nc, int no, int B, int H, int W, int cus, int& TH, int& TW);
     static bool head_cls_tile(int C0, int c3, int nc, int H, int W, int& TH, int& TW);
     void conv_args(const Op& op, int B, int H, int W, ConvArgs& a, int& BM, int& BN) const;
     MxShape mx_shape(const ConvArgs& a, int B) const;

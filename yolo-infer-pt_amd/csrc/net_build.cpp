@@ -542,13 +542,13 @@ bool Net::fuse_csp(const std::vector<Seg>& in, const std::vector<int>& logical, 
     if (in.size() != 1 || in[0].up || in[0].v.C != logical[0] || logical[0] % 16 || c % 16 || out_ch % 32) return false;
     if (out.coff % 8 || in[0].v.coff % 8) return false;
     int TH, TW;
-    return csp_tile(logical[0] / 16, c / 16, out_ch / 32, 1, 1 << 30, 1 << 30, 1, TH, TW);
+    return csp_tile(opt.tune, logical[0] / 16, c / 16, out_ch / 32, 1, 1 << 30, 1 << 30, 1, TH, TW);
 }
 bool Net::fuse_csp_tail(int c, int out_ch, View out) const {
     if (dtype == F32 || !opt.fuse) return false;
     if (c % 16 || out_ch % 32 || out.coff % 8) return false;
     int TH, TW;
-    return csp_tile(0, c / 16, out_ch / 32, 1, 1 << 30, 1 << 30, 1, TH, TW);
+    return csp_tile(opt.tune, 0, c / 16, out_ch / 32, 1, 1 << 30, 1 << 30, 1, TH, TW);
 }
 // the decode folds into box_dfl + head_cls / a class-rows decode (16-bit handles; the
 // box branch's last conv has 4 or 6 16-channel K blocks)

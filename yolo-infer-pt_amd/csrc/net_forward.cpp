@@ -56,7 +56,7 @@ void Net::check_shape(int B, int H, int W) const {
         if (op.kind == OP_CSP) {
             const int lv = tensors[op.out.t].level;
             int th, tw;
-            require(csp_tile(op.cs[0] >= 0 ? convs[op.cs[0]].cin / 16 : 0, convs[op.cs[1]].cin / 16, convs[op.cs[3]].cout / 32,
+            require(csp_tile(opt.tune, op.cs[0] >= 0 ? convs[op.cs[0]].cin / 16 : 0, convs[op.cs[1]].cin / 16, convs[op.cs[3]].cout / 32,
                              B, H >> lv, W >> lv, 256, th, tw),
                     op.label + ": no tile for a " + std::to_string(H >> lv) + " x " + std::to_string(W >> lv) + " map");
         }

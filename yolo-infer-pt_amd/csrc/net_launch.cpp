@@ -114,7 +114,6 @@ void Net::ensure_tuned(int B, int H, int W, hipStream_t s) {
     const GraphKey key{B, H, W};
     auto it = conv_kern.find(key);
     if (it != conv_kern.end()) { cur_kern = &it->second; return; }
-    if (!num_cus) HIPCHECK(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, device));
     const int forced = force_kern >= 0 ? force_kern : opt.conv_force;
     std::vector<MxChoice> ch(ops.size());
     std::vector<std::vector<MxPlan>> cands(ops.size());
@@ -182,11 +181,6 @@ void Net::ensure_tuned(int B, int H, int W, hipStream_t s) {
         // pick after every candidate is timed: the fastest, except that for 3x3 layers a plan
         // within 3 % of the fastest that re-reads fewer input bytes (halo and cout-slice
         // re-reads) wins - stable choices, less HBM pressure beside the other lanes
-        // YH_TUNE_CU=1 (experiment): rank by CU-time (time x CUs the grid occupies) instead of
-        // time: with lanes overlapping, a plan that leaves CUs to the other lanes can win
-        if (getenv("YH_TUNE_CU"))
-            for (size_t c = 0; c < cands[i].size(); ++c)
-                t_ms[c] *= (float)std::min(cands[i][c].grid, num_cus) / (float)num_cus;
         const float best = *std::min_element(t_ms.begin(), t_ms.end());
         size_t pick = 0;
         for (size_t c = 0; c < cands[i].size(); ++c) {
@@ -286,9 +280,8 @@ PwChainArgs Net::pw_chain_args(const Op& op, int B, int H, int W) {
     a.P = op.pwP;
     a.nst = (int)op.pws.size();
     a.nload = (int)op.pwl.size();
-    // YH_PWC_WARM=0 (read when the arguments are built): no L2 warm-up in the prologue
-    const char* ew = getenv("YH_PWC_WARM");
-    a.sink = ew && atoi(ew) == 0 ? -1 : op.pwLds - 1024;
+    // pwc_warm off: no L2 warm-up in the prologue
+    a.sink = opt.tune.pwc_warm ? op.pwLds - 1024 : -1;
     a.zero = zero_dev;
     for (int z = 0; z < a.nload; ++z) {
         PwcLoad& L = a.ld[z];
@@ -413,10 +406,7 @@ BoxDflArgs Net::box_dfl_args(const Op& op, int B, int H, int W) {
     a.A = anchor_off(3, H, W);
     a.io = (const void* const*)io_dev;
     a.nk = op.bx[0].C / 16;
-    // tiles per wave (YH_BOXDFL_TPW: 1 / 2 / 4, read when the arguments are built)
-    const char* et = getenv("YH_BOXDFL_TPW");
-    a.tpw = BOX_DFL_TPW;
-    if (et && (atoi(et) == 1 || atoi(et) == 2 || atoi(et) == 4)) a.tpw = atoi(et);
+    a.tpw = opt.tune.boxdfl_tpw ? opt.tune.boxdfl_tpw : BOX_DFL_TPW;
     int wg = 0;
     for (int l = 0; l < 3; ++l) {
         BoxDflLevel& v = a.lv[a.nlv++];
@@ -447,18 +437,15 @@ static int csp_items(int TH, int TW, int ni, int nc, int no) {
     return (ni ? nc * nb((TH + 4) * (TW + 4)) : 0) + nb((TH + 2) * (TW + 2)) + ((nc + 1) / 2 + no) * nb(TH * TW);
 }
 // Output tile of a fused C3k2 launch over B maps of H x W on `cus` persistent workgroups.
-bool Net::csp_tile(int ni, int nc, int no, int B, int H, int W, int cus, int& TH, int& TW) {
-    // YH_CSP_TILE=<TH>x<TW> (experiments, tests): that tile first where it fits one workgroup
-    // (a tile larger than the map is clipped like any edge tile). csp_lds admits a tile only
-    // if every multiply-shift quotient of the kernel's index math is exact for it, here and
+bool Net::csp_tile(const Tuning& tune, int ni, int nc, int no, int B, int H, int W, int cus, int& TH, int& TW) {
+    // Tuning::csp_th x csp_tw (YH_CSP_TILE; experiments, tests): that tile first where it fits one
+    // workgroup (a tile larger than the map is clipped like any edge tile). csp_lds admits a tile
+    // only if every multiply-shift quotient of the kernel's index math is exact for it, here and
     // for the default choice below.
-    if (const char* e = getenv("YH_CSP_TILE")) {
-        int th = 0, tw = 0;
-        if (sscanf(e, "%dx%d", &th, &tw) == 2 && th > 0 && tw > 0 && csp_lds(th, tw, ni, nc, no) > 0) {
-            TH = th;
-            TW = tw;
-            return true;
-        }
+    if (tune.csp_th > 0 && tune.csp_tw > 0 && csp_lds(tune.csp_th, tune.csp_tw, ni, nc, no) > 0) {
+        TH = tune.csp_th;
+        TW = tune.csp_tw;
+        return true;
     }
     if (CSP_THREADS >= 1024) {
         // 16-wave workgroups, one per CU: the tile that minimises rounds x cycles per tile.
@@ -523,8 +510,7 @@ CspArgs Net::csp_args(size_t oi, int B, int H, int W, int& grid) {
     a.ni = op.cs[0] >= 0 ? convs[op.cs[0]].cin / 16 : 0;
     a.nc = convs[op.cs[1]].cin / 16;
     a.no = convs[op.cs[3]].cout / 32;
-    if (!num_cus) HIPCHECK(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, device));
-    require(csp_tile(a.ni, a.nc, a.no, B, a.H, a.W, num_cus, a.TH, a.TW), op.label + ": no LDS tile");
+    require(csp_tile(opt.tune, a.ni, a.nc, a.no, B, a.H, a.W, num_cus, a.TH, a.TW), op.label + ": no LDS tile");
     csp_plan[{GraphKey{B, H, W}, (int)oi}] = "c3k2_t" + std::to_string(a.TH) + "x" + std::to_string(a.TW);
     a.ntw = (a.W + a.TW - 1) / a.TW;
     // the kernel's per-lane offsets are 32-bit from the tile's origin pixel: a bound on the
@@ -601,12 +587,12 @@ void Net::launch_op(size_t oi, int B, int H, int W, hipStream_t s) {
             ConvArgs a{};
             int BM, BN;
             conv_args(op, B, H, W, a, BM, BN);
-            rc = launch_conv(dtype, CONV_GEMM, BM, BN, a, s);
+            rc = launch_conv(dtype, BM, BN, a, s);
             break;
         }
         case OP_DW: rc = launch_dwconv(dtype, dw_args(op, B, H, W), s); break;
-        case OP_SPPF: rc = launch_sppf(dtype, pool_args(op, B, H, W), s); break;
-        case OP_ATTN: rc = launch_attention(dtype, attn_args(op, H, W), B, s); break;
+        case OP_SPPF: rc = launch_sppf(dtype, pool_args(op, B, H, W), ctx(), s); break;
+        case OP_ATTN: rc = launch_attention(dtype, attn_args(op, H, W), B, ctx(), s); break;
         case OP_HEADCLS: rc = launch_head_cls(dtype, head_cls_args(op, B, H, W), s); break;
         case OP_DECODE: rc = launch_decode(dtype, decode_args(op, B, H, W), s); break;
         case OP_BOXDFL: rc = launch_box_dfl(dtype, box_dfl_args(op, B, H, W), s); break;
@@ -618,7 +604,7 @@ void Net::launch_op(size_t oi, int B, int H, int W, hipStream_t s) {
             rc = launch_csp(dtype, a, grid, s);
             break;
         }
-        case OP_C3K: rc = launch_c3k(dtype, c3k_args(op, B, H, W), s); break;
+        case OP_C3K: rc = launch_c3k(dtype, c3k_args(op, B, H, W), ctx(), s); break;
         case OP_CLSPOOL: rc = launch_cls_pool(dtype, cls_pool_args(op, B, H, W), s); break;
         case OP_CLSHEAD: rc = launch_cls_head(dtype, cls_head_args(op, B, H, W), s); break;
         case OP_CLSFC: rc = launch_cls_fc(dtype, cls_fc_args(op, B), s); break;

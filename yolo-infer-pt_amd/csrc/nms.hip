@@ -1154,17 +1154,11 @@ __global__ __launch_bounds__(NMS_T) void nms_finish(const NmsArgs p) {
 
 template <typename T>
 int launch_nms_t(const NmsArgs& a, hipStream_t s) {
+    if (int rc = lds_optin(reinterpret_cast<const void*>(&nms_prep<T>), (int)sizeof(NmsSmem))) return rc;
+    if (int rc = lds_optin(reinterpret_cast<const void*>(&nms_finish<T>), (int)sizeof(NmsSmem))) return rc;
     hipLaunchKernelGGL(nms_zero, dim3((a.B * NBINS + 255) / 256), dim3(256), 0, s, a.counts, a.hist, a.state, a.B);
     const int per_block = EMIT_CHUNKS * EMIT_APT;
     hipLaunchKernelGGL((nms_emit<T>), dim3((a.A + per_block - 1) / per_block, a.B), dim3(256), 0, s, a);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_prep<T>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(NmsSmem));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_finish<T>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(NmsSmem));
-        attr = true;
-    }
     hipLaunchKernelGGL((nms_gather<T>), dim3(GATHER_G, a.B), dim3(NMS_T), 0, s, a);
     hipLaunchKernelGGL((nms_prep<T>), dim3(a.B), dim3(NMS_T), sizeof(NmsSmem), s, a);
     // about one 64 x 64 tile per wave at the typical first batch (~1000 entries: 136 tiles per image)

@@ -305,12 +305,7 @@ int launch_pw_chain_t(const PwChainArgs& a, int lds, hipStream_t s) {
             st.ldo % 4)
             return (int)hipErrorInvalidValue;
     }
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_chain<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(&pw_chain<T>), 160 * 1024)) return rc;
     const long long grid = (a.M + a.P - 1) / a.P;
     hipLaunchKernelGGL((pw_chain<T>), dim3((unsigned)grid), dim3(PWC_THREADS), lds, s, a);
     return (int)hipGetLastError();

@@ -404,13 +404,7 @@ int launch_track(const float* dets, const int* counts, int batch, int max_det, c
     // arguments were checked by yh_track (yh_track_check): 1 <= max_tracks <= YH_TRACK_MAX_TRACKS,
     // 0 <= max_det <= YH_TRACK_MAX_DET
     if (batch <= 0) return 0;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(track_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET));
-        attr = true;
-    }
+    if (int rc = lds_optin(reinterpret_cast<const void*>(track_kernel), (int)track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET))) return rc;
     hipLaunchKernelGGL(track_kernel, dim3(batch), dim3(TRACK_T), track_lds(max_tracks, max_det), s, dets, counts, max_det,
                        stream_ids, static_cast<uint32_t*>(state), streams, max_tracks, p, max_out, out, ids, det_index,
                        out_counts);
