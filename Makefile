@@ -23,7 +23,8 @@ HOSTCXX := match_host merge_host track_host
 
 objs = $(patsubst %,$(OBJDIR)/%.o,$(1))
 OBJS := $(call objs,$(NET) $(HOSTHIP) $(KERNELS) $(KERNELS_NOFMA) $(HOSTCXX))
-HOST_H := $(SRC)/host_util.h $(SRC)/match_host.h $(SRC)/merge_host.h $(SRC)/track_host.h
+HOST_H := $(SRC)/host_util.h $(SRC)/host_parallel.h $(SRC)/box_math.h \
+          $(SRC)/match_host.h $(SRC)/merge_host.h $(SRC)/track_host.h
 
 all: $(OUT)
 
@@ -42,15 +43,15 @@ $(call objs,$(KERNELS)): $(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h $(SRC)/dtyp
 $(call objs,$(KERNELS_NOFMA)): $(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h $(SRC)/dtypes.h include/yolo_hip.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 
-$(call objs,$(HOSTCXX)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/%.h include/yolo_hip.h | $(OBJDIR)
+$(call objs,$(HOSTCXX)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/%.h $(SRC)/box_math.h $(SRC)/host_parallel.h include/yolo_hip.h | $(OBJDIR)
 	$(HIPCC) -x c++ -O3 -fPIC -std=c++17 -Iinclude -I$(SRC) -ffp-contract=off -c $< -o $@
 
 # headers only some units of a group include
 $(call objs,conv_mx conv_rw): $(SRC)/conv_mx.h
-# shares its arithmetic with track_host.o through track_host.h
-$(OBJDIR)/track.o: $(SRC)/track_host.h
-# reports its argument errors through host_util.h's guarded()
-$(OBJDIR)/preprocess.o: $(SRC)/host_util.h
+# each shares its arithmetic with its host twin through box_math.h and the twin's header
+$(call objs,match merge track): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
+# reports its argument errors through host_util.h's guarded(); its host functions use the pool
+$(OBJDIR)/preprocess.o: $(SRC)/host_util.h $(SRC)/host_parallel.h
 
 $(OUT): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)

@@ -80,5 +80,37 @@ inline uint16_t f2h(float f) {
     if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h;
     return (uint16_t)(sign | h);
 }
+inline float bf2f(uint16_t h) {
+    const uint32_t u = (uint32_t)h << 16;
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+inline float h2f(uint16_t h) {
+    const uint32_t s = (uint32_t)(h & 0x8000) << 16, e = (h >> 10) & 0x1f, m = h & 0x3ff;
+    uint32_t u;
+    if (e == 0) {
+        if (m == 0) {
+            u = s;
+        } else {  // subnormal
+            int ee = -1;
+            uint32_t mm = m;
+            do { ++ee; mm <<= 1; } while (!(mm & 0x400));
+            u = s | ((uint32_t)(127 - 15 - ee) << 23) | ((mm & 0x3ff) << 13);
+        }
+    } else if (e == 31) {
+        u = s | 0x7f800000u | (m << 13);
+    } else {
+        u = s | ((e + 127 - 15) << 23) | (m << 13);
+    }
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+// f rounded to the dtype (YH_F32 / YH_F16 / YH_BF16) and back: round to nearest even, as torch's
+// casts. The device and the host NMS round the confidence threshold with this.
+inline float round_to_dtype(int dtype, float f) {
+    return dtype == YH_F16 ? h2f(f2h(f)) : (dtype == YH_BF16 ? bf2f(f2bf(f)) : f);
+}
 
 }  // namespace yh

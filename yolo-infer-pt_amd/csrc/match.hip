@@ -1,7 +1,8 @@
 // Batched matching of NMS detections to ground-truth labels (yh_match): the reference's
 // compute_metric (utils/util.py:99-120) for a whole batch in one launch, straight from the
-// fixed-size NMS output dets (B, max_det, 6) / counts (B). The host twin with the same
-// formulas is csrc/match_host.cpp; the semantics are stated there and in include/yolo_hip.h.
+// fixed-size NMS output dets (B, max_det, 6) / counts (B). The host twin is
+// csrc/match_host.cpp; the semantics are stated there and in include/yolo_hip.h. The IoU is
+// shared with it through csrc/match_host.h.
 //
 // One workgroup of MATCH_T threads per image, no communication between workgroups.
 //   phase 1  every thread owns the detections d = tid, tid + MATCH_T, ...; the image's labels
@@ -19,6 +20,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "match_host.h"
 #include "yolo_hip.h"
 
 namespace yh {
@@ -30,11 +32,6 @@ constexpr int MATCH_CHUNK = 256;   // labels per LDS chunk
 // LDS plan: 12 B per detection slot + 6 KiB of labels; the ABI's cap must fit the 64 KiB a
 // workgroup may request without an attribute
 static_assert((size_t)YH_MATCH_MAX_DET * 12 + 6 * MATCH_CHUNK * sizeof(float) <= 64 * 1024, "LDS plan");
-
-// written as in csrc/match_host.cpp (bit-identical host twin); inputs must be finite
-__device__ inline float lesser(float a, float b) { return b < a ? b : a; }
-__device__ inline float greater(float a, float b) { return a < b ? b : a; }
-__device__ inline float clamp0(float v) { return v < 0.0f ? 0.0f : v; }
 
 // dynamic LDS only, every carve a multiple of 16 bytes (max_det is rounded up to 4 entries)
 __global__ __launch_bounds__(MATCH_T) void match_kernel(const float* __restrict__ dets, const int* __restrict__ counts,
@@ -87,11 +84,9 @@ __global__ __launch_bounds__(MATCH_T) void match_kernel(const float* __restrict_
             float bi = biou[d];
             for (int i = 0; i < n; ++i) {
                 if (!(lab[i] == cls)) continue;
-                const float iw = clamp0(lesser(lab[3 * MATCH_CHUNK + i], bx2) - greater(lab[MATCH_CHUNK + i], bx1));
-                const float ih = clamp0(lesser(lab[4 * MATCH_CHUNK + i], by2) - greater(lab[2 * MATCH_CHUNK + i], by1));
-                const float inter = iw * ih;
-                const float den = ((lab[5 * MATCH_CHUNK + i] + area_b) - inter) + 1e-7f;
-                const float iou = inter / den;
+                const float iou = yh_match_iou(lab[MATCH_CHUNK + i], lab[2 * MATCH_CHUNK + i], lab[3 * MATCH_CHUNK + i],
+                                               lab[4 * MATCH_CHUNK + i], lab[5 * MATCH_CHUNK + i], bx1, by1, bx2, by2,
+                                               area_b);
                 if (iou > bi) {
                     bi = iou;
                     bl = base + i;

@@ -9,26 +9,17 @@
 //   2. tp[d, t] = 1 iff d has a best label, biou[d] >= iou_v[t], and no e < d has
 //      best[e] == best[d] and biou[e] >= iou_v[t].
 // IoU in fp32, the operation order of metrics._iou: iw = min(x2) - max(x1) clamped at 0, ih
-// likewise, inter = iw * ih, den = ((areaA + areaB) - inter) + 1e-7f, iou = inter / den.
+// likewise, inter = iw * ih, den = ((areaA + areaB) - inter) + 1e-7f, iou = inter / den
+// (yh_match_iou in csrc/match_host.h, shared with the kernel).
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
-#include <thread>
 #include <vector>
 
+#include "host_parallel.h"
 #include "match_host.h"
 
-#define YH_STR_(x) #x
-#define YH_STR(x) YH_STR_(x)
-
 namespace {
-
-// The same three helpers, written the same way, in csrc/match.hip: host and device agree bit for
-// bit on every input. They agree with torch (whose min / max propagate NaN) for finite boxes;
-// the inputs must be finite, as NMS output and labels are.
-inline float lesser(float a, float b) { return b < a ? b : a; }
-inline float greater(float a, float b) { return a < b ? b : a; }
-inline float clamp0(float v) { return v < 0.0f ? 0.0f : v; }
 
 void match_image(const float* dets, int cnt, int max_det, const float* labels, int lo, int hi, const float* iou_v,
                  int T, uint8_t* tp, float* score_cls) {
@@ -41,12 +32,8 @@ void match_image(const float* dets, int cnt, int max_det, const float* labels, i
         for (int l = lo; l < hi; ++l) {
             const float* g = labels + 5 * (size_t)l;
             if (!(g[0] == cls)) continue;
-            const float iw = clamp0(lesser(g[3], bx2) - greater(g[1], bx1));
-            const float ih = clamp0(lesser(g[4], by2) - greater(g[2], by1));
-            const float inter = iw * ih;
             const float area_a = (g[3] - g[1]) * (g[4] - g[2]);
-            const float den = ((area_a + area_b) - inter) + 1e-7f;
-            const float iou = inter / den;
+            const float iou = yh_match_iou(g[1], g[2], g[3], g[4], area_a, bx1, by1, bx2, by2, area_b);
             if (iou > biou[d]) { biou[d] = iou; best[d] = l; }
         }
     }
@@ -99,17 +86,6 @@ int yh_match_host_run(const float* dets, const int* counts, int batch, int max_d
                     score_cls ? score_cls + (size_t)b * max_det * 2 : nullptr);
         if (counts_out) counts_out[b] = cnt;
     };
-    int nt = threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    nt = std::min(nt, batch);
-    if (nt <= 1) {
-        for (int b = 0; b < batch; ++b) run(b);
-        return 0;
-    }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t)
-        pool.emplace_back([&, t] {
-            for (int b = t; b < batch; b += nt) run(b);
-        });
-    for (auto& th : pool) th.join();
+    yh::parallel_strided(batch, threads, run);
     return 0;
 }

@@ -1,8 +1,8 @@
 // Cross-tile detection merge (yh_merge): maps the NMS output of a batch of tiles back to the
 // source images (inverse letterbox + crop offset, clipped) and, for images cut into several
 // tiles, removes duplicates with a second greedy NMS - one launch for all images of a call.
-// The host twin with the same formulas is csrc/merge_host.cpp; the semantics are stated there
-// and in include/yolo_hip.h.
+// The host twin is csrc/merge_host.cpp; the semantics are stated there and in include/yolo_hip.h.
+// The map, the sort key and the kill test of a row are shared with it through csrc/merge_host.h.
 //
 // One workgroup of MERGE_T threads per image, no communication between workgroups, no atomics.
 //   phase 1  slot s = (tile, row) of the image's tile range gets a 64-bit key in LDS: inverted
@@ -32,6 +32,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "merge_host.h"
 #include "yolo_hip.h"
 
 namespace yh {
@@ -48,44 +49,6 @@ constexpr size_t MERGE_LDS = (size_t)YH_MERGE_MAX_CAND * 8 + 6 * 64 * sizeof(flo
 // above the 64 KiB a workgroup gets by default: launch_merge requests the size with the attribute
 // csrc/c3k.hip uses (up to 160 KiB per workgroup on gfx950)
 static_assert(MERGE_LDS <= 160 * 1024, "LDS plan");
-
-// written as in csrc/merge_host.cpp (bit-identical host twin)
-__device__ inline float lesser(float a, float b) { return b < a ? b : a; }
-__device__ inline float greater(float a, float b) { return a < b ? b : a; }
-__device__ inline float clamp0(float v) { return v < 0.0f ? 0.0f : v; }
-
-__device__ inline uint64_t sort_key(float score, uint32_t pos) {
-    uint32_t u = __float_as_uint(score);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)(~u) << 32) | pos;
-}
-
-struct Box {
-    float x1, y1, x2, y2;
-};
-
-// the map of one row; false: dropped
-__device__ inline bool map_row(const float* __restrict__ d, const float* __restrict__ xf, float W, float H, Box& b) {
-    const float sx = xf[0], sy = xf[1], px = xf[2], py = xf[3], ox = xf[4], oy = xf[5];
-    float x1 = d[0] - px, y1 = d[1] - py, x2 = d[2] - px, y2 = d[3] - py;
-    x1 = x1 * sx; y1 = y1 * sy; x2 = x2 * sx; y2 = y2 * sy;
-    x1 = x1 + ox; y1 = y1 + oy; x2 = x2 + ox; y2 = y2 + oy;
-    x1 = lesser(greater(x1, 0.0f), W); y1 = lesser(greater(y1, 0.0f), H);
-    x2 = lesser(greater(x2, 0.0f), W); y2 = lesser(greater(y2, 0.0f), H);
-    b.x1 = x1; b.y1 = y1; b.x2 = x2; b.y2 = y2;
-    return !(x2 <= x1 || y2 <= y1);
-}
-
-// does the kept box (k*, area ka) kill the later box b (area ba)? Disjoint boxes (most pairs) skip
-// the division: their quotient is 0 (or NaN), never above a threshold >= 0. Same in the host twin.
-__device__ inline bool kills(float kx1, float ky1, float kx2, float ky2, float ka, const Box& b, float ba, double iou) {
-    const float w = clamp0(lesser(kx2, b.x2) - greater(kx1, b.x1));
-    const float h = clamp0(lesser(ky2, b.y2) - greater(ky1, b.y1));
-    const float inter = w * h;
-    if (inter == 0.0f && iou >= 0.0) return false;
-    const float ovr = inter / ((ka + ba) - inter);
-    return (double)ovr > iou;
-}
 
 // lane i's value of v, i wave-uniform (v_readlane_b32: no LDS round trip)
 __device__ inline float lane_value(float v, int i) {
@@ -128,9 +91,9 @@ __global__ __launch_bounds__(MERGE_T) void merge_kernel(const float* __restrict_
             cnt = cnt < 0 ? 0 : (cnt > max_det ? max_det : cnt);
             if (r < cnt) {
                 const float* d = dets + ((size_t)t * max_det + r) * 6;
-                Box b;
-                if (map_row(d, tile_xf + 6 * (size_t)t, W, H, b))
-                    key = suppress ? sort_key(d[4], (uint32_t)s) : (uint64_t)(uint32_t)s;
+                yh_merge_box b;
+                if (yh_merge_map_row(d, tile_xf + 6 * (size_t)t, W, H, b))
+                    key = suppress ? yh_merge_sort_key(d[4], (uint32_t)s) : (uint64_t)(uint32_t)s;
             }
         }
         keys[s] = key;
@@ -157,7 +120,7 @@ __global__ __launch_bounds__(MERGE_T) void merge_kernel(const float* __restrict_
         }
     }
     // phase 3
-    Box box[MERGE_SLOTS];
+    yh_merge_box box[MERGE_SLOTS];
     float score[MERGE_SLOTS], cls[MERGE_SLOTS], area[MERGE_SLOTS];
     bool alive[MERGE_SLOTS];
 #pragma unroll
@@ -165,13 +128,13 @@ __global__ __launch_bounds__(MERGE_T) void merge_kernel(const float* __restrict_
         const int s = k * MERGE_T + tid;
         const uint64_t key = s < n2 ? keys[s] : MERGE_NONE;
         alive[k] = key != MERGE_NONE;
-        box[k] = Box{0.0f, 0.0f, 0.0f, 0.0f};
+        box[k] = yh_merge_box{0.0f, 0.0f, 0.0f, 0.0f};
         score[k] = cls[k] = area[k] = 0.0f;
         if (alive[k]) {
             const int pos = (int)(uint32_t)key;         // < used
             const int tl = pos / max_det, r = pos - tl * max_det, t = lo + tl;
             const float* d = dets + ((size_t)t * max_det + r) * 6;
-            map_row(d, tile_xf + 6 * (size_t)t, W, H, box[k]);
+            yh_merge_map_row(d, tile_xf + 6 * (size_t)t, W, H, box[k]);
             score[k] = d[4];
             cls[k] = d[5];
             area[k] = (box[k].x2 - box[k].x1) * (box[k].y2 - box[k].y1);
@@ -205,8 +168,8 @@ __global__ __launch_bounds__(MERGE_T) void merge_kernel(const float* __restrict_
                 if (alive[k]) {
                     for (int q = 0; q < nq; ++q) {
                         if (cls[k] == kbox[256 + q] &&
-                            kills(kbox[q], kbox[64 + q], kbox[128 + q], kbox[192 + q], kbox[320 + q], box[k], area[k],
-                                  iou)) {
+                            yh_merge_kills(kbox[q], kbox[64 + q], kbox[128 + q], kbox[192 + q], kbox[320 + q], box[k],
+                                           area[k], iou)) {
                             alive[k] = false;
                             break;
                         }
@@ -231,7 +194,7 @@ __global__ __launch_bounds__(MERGE_T) void merge_kernel(const float* __restrict_
                         const float kx2 = lane_value(box[k].x2, i), ky2 = lane_value(box[k].y2, i);
                         const float kc = lane_value(cls[k], i), ka = lane_value(area[k], i);
                         const bool kill = lane > i && ((live >> lane) & 1ull) && cls[k] == kc &&
-                                          kills(kx1, ky1, kx2, ky2, ka, box[k], area[k], iou);
+                                          yh_merge_kills(kx1, ky1, kx2, ky2, ka, box[k], area[k], iou);
                         live &= ~__ballot(kill);
                     }
                 }
@@ -262,7 +225,8 @@ __global__ __launch_bounds__(MERGE_T) void merge_kernel(const float* __restrict_
             if (suppress && alive[k] && k * MERGE_T + tid >= base + 64) {   // the later candidates of this slot
                 for (int q = 0; q < nk; ++q) {
                     if (cls[k] == kbox[256 + q] &&
-                        kills(kbox[q], kbox[64 + q], kbox[128 + q], kbox[192 + q], kbox[320 + q], box[k], area[k], iou)) {
+                        yh_merge_kills(kbox[q], kbox[64 + q], kbox[128 + q], kbox[192 + q], kbox[320 + q], box[k],
+                                       area[k], iou)) {
                         alive[k] = false;
                         break;
                     }

@@ -1,6 +1,7 @@
 // Host (CPU) twin of the cross-tile detection merge (csrc/merge.hip), and the argument check
 // both entry points share. HIP-free on purpose: this file compiles alone with any C++17
-// compiler (build it with -ffp-contract=off, as the device file is).
+// compiler (build it with -ffp-contract=off, as the device file is). The arithmetic of a row is
+// in csrc/merge_host.h, shared with the kernel.
 //
 // Semantics, per image i (tiles tile_offsets[i] .. tile_offsets[i + 1], the range clamped to
 // [0, tiles] and to max_tiles tiles):
@@ -11,8 +12,8 @@
 //      a row whose clipped box has x2 <= x1 or y2 <= y1 is dropped;
 //   3. an image of exactly one tile writes its surviving rows in input order, up to max_out;
 //   4. an image of two or more tiles orders its candidates by score descending (ties: the lower
-//      position; the order is that of the 64-bit key below) and walks them greedily: a live
-//      candidate is kept and kills every later one of equal class (f32 ==) whose
+//      position; the order is that of yh_merge_sort_key's 64-bit key) and walks them greedily:
+//      a live candidate is kept and kills every later one of equal class (f32 ==) whose
 //      inter / (area_i + area_j - inter) in fp32 is, as a double, > iou_threshold
 //      (torchvision.ops.nms, as csrc/nms_host.cpp states it, without the class offset); it stops
 //      at max_out kept;
@@ -20,34 +21,16 @@
 //      the count are 0.
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
-#include <thread>
 #include <vector>
 
+#include "host_parallel.h"
 #include "merge_host.h"
-
-#define YH_STR_(x) #x
-#define YH_STR(x) YH_STR_(x)
 
 namespace {
 
-// The same helpers, written the same way, in csrc/merge.hip (and csrc/match.hip): host and
-// device agree bit for bit on every input.
-inline float lesser(float a, float b) { return b < a ? b : a; }
-inline float greater(float a, float b) { return a < b ? b : a; }
-inline float clamp0(float v) { return v < 0.0f ? 0.0f : v; }
-
-// Ascending key = descending score, then ascending position. The score's bits are mapped to an
-// unsigned that orders like the float (negative floats included) and inverted.
-inline uint64_t sort_key(float score, uint32_t pos) {
-    uint32_t u;
-    std::memcpy(&u, &score, 4);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)(~u) << 32) | pos;
-}
-
 struct Cand {
-    float x1, y1, x2, y2, score, cls, area;
+    yh_merge_box b;
+    float score, cls, area;
     uint64_t key;
 };
 
@@ -57,25 +40,19 @@ void merge_image(const float* dets, const int* counts, int max_det, const float*
     std::vector<Cand> c;
     for (int t = lo; t < hi; ++t) {
         const int cnt = std::min(std::max(counts[t], 0), max_det);
-        const float* xf = tile_xf + 6 * (size_t)t;
-        const float sx = xf[0], sy = xf[1], px = xf[2], py = xf[3], ox = xf[4], oy = xf[5];
         for (int r = 0; r < cnt; ++r) {
             const float* d = dets + ((size_t)t * max_det + r) * 6;
-            float x1 = d[0] - px, y1 = d[1] - py, x2 = d[2] - px, y2 = d[3] - py;
-            x1 = x1 * sx; y1 = y1 * sy; x2 = x2 * sx; y2 = y2 * sy;
-            x1 = x1 + ox; y1 = y1 + oy; x2 = x2 + ox; y2 = y2 + oy;
-            x1 = lesser(greater(x1, 0.0f), W); y1 = lesser(greater(y1, 0.0f), H);
-            x2 = lesser(greater(x2, 0.0f), W); y2 = lesser(greater(y2, 0.0f), H);
-            if (x2 <= x1 || y2 <= y1) continue;
+            yh_merge_box b;
+            if (!yh_merge_map_row(d, tile_xf + 6 * (size_t)t, W, H, b)) continue;
             const uint32_t pos = (uint32_t)(t - lo) * (uint32_t)max_det + (uint32_t)r;
-            c.push_back({x1, y1, x2, y2, d[4], d[5], (x2 - x1) * (y2 - y1), sort_key(d[4], pos)});
+            c.push_back({b, d[4], d[5], (b.x2 - b.x1) * (b.y2 - b.y1), yh_merge_sort_key(d[4], pos)});
         }
     }
     const int n = (int)c.size();
     int kept = 0;
     auto emit = [&](const Cand& k) {
         float* o = out + 6 * (size_t)kept++;
-        o[0] = k.x1; o[1] = k.y1; o[2] = k.x2; o[3] = k.y2; o[4] = k.score; o[5] = k.cls;
+        o[0] = k.b.x1; o[1] = k.b.y1; o[2] = k.b.x2; o[3] = k.b.y2; o[4] = k.score; o[5] = k.cls;
     };
     if (hi - lo == 1) {
         for (int i = 0; i < n && kept < max_out; ++i) emit(c[i]);
@@ -90,12 +67,7 @@ void merge_image(const float* dets, const int* counts, int max_det, const float*
         const Cand& k = c[i];
         for (int j = i + 1; j < n; ++j) {
             if (dead[j] || !(c[j].cls == k.cls)) continue;
-            const float w = clamp0(lesser(k.x2, c[j].x2) - greater(k.x1, c[j].x1));
-            const float h = clamp0(lesser(k.y2, c[j].y2) - greater(k.y1, c[j].y1));
-            const float inter = w * h;
-            if (inter == 0.0f && iou >= 0.0) continue;   // quotient 0 (or NaN): never above the threshold
-            const float ovr = inter / ((k.area + c[j].area) - inter);
-            if ((double)ovr > iou) dead[j] = 1;
+            if (yh_merge_kills(k.b.x1, k.b.y1, k.b.x2, k.b.y2, k.area, c[j].b, c[j].area, iou)) dead[j] = 1;
         }
     }
     *out_count = kept;
@@ -131,17 +103,6 @@ int yh_merge_host_run(const float* dets, const int* counts, int tiles, int max_d
         merge_image(dets, counts, max_det, tile_xf, lo, hi, image_wh[2 * (size_t)i], image_wh[2 * (size_t)i + 1],
                     iou_threshold, max_out, out + (size_t)i * max_out * 6, out_counts + i);
     };
-    int nt = threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    nt = std::min(nt, images);
-    if (nt <= 1) {
-        for (int i = 0; i < images; ++i) run(i);
-        return 0;
-    }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t)
-        pool.emplace_back([&, t] {
-            for (int i = t; i < images; i += nt) run(i);
-        });
-    for (auto& th : pool) th.join();
+    yh::parallel_strided(images, threads, run);
     return 0;
 }

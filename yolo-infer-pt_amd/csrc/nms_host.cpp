@@ -15,59 +15,14 @@
 //     +1, in float32), first max_det kept (util.py:163);
 //   * no wall-clock cutoff (util.py:133-134, 166-167).
 #include <algorithm>
-#include <cmath>
 #include <cstdint>
-#include <cstring>
-#include <numeric>
-#include <string>
-#include <thread>
 #include <vector>
 
+#include "host_parallel.h"
+#include "host_util.h"
 #include "yolo_hip.h"
 
 namespace {
-
-inline float bf16_to_f(uint16_t h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-inline float f16_to_f(uint16_t h) {
-    const uint32_t s = (uint32_t)(h & 0x8000) << 16, e = (h >> 10) & 0x1f, m = h & 0x3ff;
-    uint32_t u;
-    if (e == 0) {
-        if (m == 0) {
-            u = s;
-        } else {  // subnormal
-            int ee = -1;
-            uint32_t mm = m;
-            do { ++ee; mm <<= 1; } while (!(mm & 0x400));
-            u = s | ((uint32_t)(127 - 15 - ee) << 23) | ((mm & 0x3ff) << 13);
-        }
-    } else if (e == 31) {
-        u = s | 0x7f800000u | (m << 13);
-    } else {
-        u = s | ((e + 127 - 15) << 23) | (m << 13);
-    }
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-// round a float to the dtype and back (round to nearest even, as torch's casts)
-inline float round_bf16(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return f;
-    u = (u + 0x7fffu + ((u >> 16) & 1)) & 0xffff0000u;
-    float r;
-    std::memcpy(&r, &u, 4);
-    return r;
-}
-inline float round_f16(float f) {
-    _Float16 h = (_Float16)f;
-    return (float)h;
-}
 
 struct Cand {
     float score;
@@ -80,9 +35,9 @@ void nms_image(int dtype, const void* y, int nc, int A, float thr, double iou, i
         const size_t k = (size_t)row * A + a;
         if (dtype == YH_F32) return static_cast<const float*>(y)[k];
         const uint16_t h = static_cast<const uint16_t*>(y)[k];
-        return dtype == YH_BF16 ? bf16_to_f(h) : f16_to_f(h);
+        return dtype == YH_BF16 ? yh::bf2f(h) : yh::h2f(h);
     };
-    auto rnd = [&](float f) { return dtype == YH_F32 ? f : (dtype == YH_BF16 ? round_bf16(f) : round_f16(f)); };
+    auto rnd = [&](float f) { return yh::round_to_dtype(dtype, f); };
     std::vector<Cand> c;
     for (int a = 0; a < A; ++a)
         for (int k = 0; k < nc; ++k) {
@@ -134,8 +89,7 @@ extern "C" int yh_nms_host(int dtype, const void* y, int batch, int num_classes,
     if (!y || !dets || !counts || batch < 0 || num_classes < 1 || anchors < 0 || max_det < 0 || max_nms < 0)
         return YH_EINVAL;
     if (dtype != YH_F32 && dtype != YH_F16 && dtype != YH_BF16) return YH_EINVAL;
-    const float thr = dtype == YH_F32 ? conf_threshold
-                                      : (dtype == YH_BF16 ? round_bf16(conf_threshold) : round_f16(conf_threshold));
+    const float thr = yh::round_to_dtype(dtype, conf_threshold);
     const size_t es = dtype == YH_F32 ? 4 : 2;
     const size_t img = (size_t)(4 + num_classes) * anchors * es;
     std::fill(dets, dets + (size_t)batch * max_det * 6, 0.0f);
@@ -143,17 +97,6 @@ extern "C" int yh_nms_host(int dtype, const void* y, int batch, int num_classes,
         nms_image(dtype, static_cast<const char*>(y) + (size_t)b * img, num_classes, anchors, thr, iou_threshold,
                   max_det, max_nms, max_wh, dets + (size_t)b * max_det * 6, counts + b);
     };
-    int nt = threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    nt = std::min(nt, batch);
-    if (nt <= 1) {
-        for (int b = 0; b < batch; ++b) run(b);
-        return YH_OK;
-    }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t)
-        pool.emplace_back([&, t] {
-            for (int b = t; b < batch; b += nt) run(b);
-        });
-    for (auto& th : pool) th.join();
+    yh::parallel_strided(batch, threads, run);
     return YH_OK;
 }

@@ -61,17 +61,7 @@ int yh_nms(int dtype, const void* y, int batch, int num_classes, int anchors, fl
         a.y = y; a.B = batch; a.A = anchors; a.nc = num_classes;
         // compare in the input dtype: torch rounds the Python-float threshold to
         // the tensor dtype before comparing (util.py:130,147)
-        float conf = conf_threshold;
-        if (dtype == YH_F16) {
-            const uint16_t hb = yh::f2h(conf);
-            const uint32_t ex = (hb >> 10) & 0x1f, mt = hb & 0x3ff;
-            conf = ex == 0 ? std::ldexp((float)mt, -24)
-                 : ex == 31 ? INFINITY : std::ldexp((float)(mt | 0x400), (int)ex - 25);
-        } else if (dtype == YH_BF16) {
-            const uint32_t u = (uint32_t)yh::f2bf(conf) << 16;
-            std::memcpy(&conf, &u, 4);
-        }
-        a.conf = conf;
+        a.conf = yh::round_to_dtype(dtype, conf_threshold);
         // largest float <= iou_threshold: for any float ovr, ovr > thr (double) <=> ovr > a.iou
         float t = (float)iou_threshold;
         if ((double)t > iou_threshold) t = std::nextafter(t, -INFINITY);

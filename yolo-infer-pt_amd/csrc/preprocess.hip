@@ -37,10 +37,10 @@
 // the source: one fixed-size crop per detection.
 #include <cmath>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "common.h"
+#include "host_parallel.h"
 #include "host_util.h"
 #include "yolo_hip.h"
 
@@ -300,15 +300,7 @@ void lb_host(const yh_frame& f, int ch, int cw, void* dst, int threads) {
             }
         }
     };
-    int nt = threads > 0 ? threads : 1;
-    nt = nt < ch ? nt : ch;
-    if (nt <= 1) {
-        rows(0, ch);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t) pool.emplace_back(rows, (int)((long long)ch * t / nt), (int)((long long)ch * (t + 1) / nt));
-    for (auto& th : pool) th.join();
+    parallel_blocks(ch, threads > 0 ? threads : 1, rows);   // threads <= 0: the caller's thread alone
 }
 
 inline yh_frame lb_bgr_frame(const void* src, int height, int width, int stride) {
@@ -578,16 +570,7 @@ void crop_host(const CropArgs& a, int threads) {
             }
         }
     };
-    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
-    nt = nt < a.capacity ? nt : a.capacity;
-    if (nt <= 1) {
-        slots(0, a.capacity);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t)
-        pool.emplace_back(slots, (int)((long long)a.capacity * t / nt), (int)((long long)a.capacity * (t + 1) / nt));
-    for (auto& th : pool) th.join();
+    parallel_blocks(a.capacity, threads, slots);
 }
 
 }  // namespace yh

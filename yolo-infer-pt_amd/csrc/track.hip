@@ -102,7 +102,7 @@ __device__ inline unsigned long long group_max(unsigned long long k, int g) {
 
 // the pair order of the specification as one number: larger is earlier. Never 0 for a candidate.
 __device__ inline unsigned long long pair_key(float iou, int index) {
-    return ((unsigned long long)yh_trk_ord(iou) << 32) | (0xFFFFFFFFu - (uint32_t)index);
+    return ((unsigned long long)float_order(iou) << 32) | (0xFFFFFFFFu - (uint32_t)index);
 }
 __device__ inline int key_index(unsigned long long k) { return (int)(0xFFFFFFFFu - (uint32_t)k); }
 

@@ -10,18 +10,16 @@
 // is preceded by no pair that shares a side with it, so the walk takes it; removing it and
 // repeating is the walk.
 #include <algorithm>
-#include <thread>
+#include <cstring>
 #include <vector>
 
+#include "host_parallel.h"
 #include "track_host.h"
-
-#define YH_STR_(x) #x
-#define YH_STR(x) YH_STR_(x)
 
 namespace {
 
 struct Pair {
-    uint32_t ord;   // yh_trk_ord(iou)
+    uint32_t ord;   // yh::float_order(iou)
     int t, d;
 };
 
@@ -49,7 +47,7 @@ void assoc(Frame& fr, FS slot_live, FR row_live, float thr, int class_aware) {
             if (class_aware && !(fr.tcls[t] == r[5])) continue;
             float iou;
             if (!yh_trk_pair(fr.tbox[t], row_box(r), thr, iou)) continue;
-            pairs.push_back({yh_trk_ord(iou), t, d});
+            pairs.push_back({yh::float_order(iou), t, d});
         }
     }
     std::sort(pairs.begin(), pairs.end(), [](const Pair& p, const Pair& q) {
@@ -215,17 +213,6 @@ int yh_track_host_run(const float* dets, const int* counts, int batch, int max_d
                      static_cast<uint32_t*>(state) + (size_t)s * words, max_tracks, *p, max_out, o, oi, od,
                      out_counts + b);
     };
-    int nt = threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    nt = std::min(nt, batch);
-    if (nt <= 1) {
-        for (int b = 0; b < batch; ++b) run(b);
-        return 0;
-    }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t)
-        pool.emplace_back([&, t] {
-            for (int b = t; b < batch; b += nt) run(b);
-        });
-    for (auto& th : pool) th.join();
+    yh::parallel_strided(batch, threads, run);
     return 0;
 }

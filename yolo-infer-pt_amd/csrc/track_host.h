@@ -8,15 +8,9 @@
 
 #include <cstddef>
 #include <cstdint>
-#include <cstring>
 
+#include "box_math.h"
 #include "yolo_hip.h"
-
-#ifdef __HIPCC__
-#define YH_TRACK_HD __host__ __device__ inline
-#else
-#define YH_TRACK_HD inline
-#endif
 
 // State of one stream, in 32-bit words (no pointers; host and device use the same bytes):
 //   [0] frame counter f   [1] ids handed out so far (next_id - 1)   [2] [3] zero
@@ -38,7 +32,7 @@ enum {
     YH_TRACK_FIELDS = 24
 };
 
-YH_TRACK_HD size_t yh_track_stream_words(int max_tracks) {
+YH_HD size_t yh_track_stream_words(int max_tracks) {
     return (size_t)YH_TRACK_HDR + (size_t)YH_TRACK_FIELDS * (size_t)max_tracks;
 }
 
@@ -51,17 +45,13 @@ struct yh_track_box {
     float x1, y1, x2, y2;
 };
 
-// Written as in csrc/merge_host.cpp / csrc/merge.hip.
-YH_TRACK_HD float yh_trk_lesser(float a, float b) { return b < a ? b : a; }
-YH_TRACK_HD float yh_trk_greater(float a, float b) { return a < b ? b : a; }
-YH_TRACK_HD float yh_trk_clamp0(float v) { return v < 0.0f ? 0.0f : v; }
-YH_TRACK_HD float yh_trk_sq(float c, float u) {
+YH_HD float yh_trk_sq(float c, float u) {
     const float s = c * u;
     return s * s;
 }
 
 // step 1 of one non-free slot (status: as stored, before this frame)
-YH_TRACK_HD void yh_trk_predict(yh_track_kal& k, int status) {
+YH_HD void yh_trk_predict(yh_track_kal& k, int status) {
     if (status != 2) k.v[3] = 0.0f;
     const float w = k.x[2], h = k.x[3];
     for (int i = 0; i < 4; ++i) {
@@ -76,7 +66,7 @@ YH_TRACK_HD void yh_trk_predict(yh_track_kal& k, int status) {
 }
 
 // the box of a state (steps 1 and 6)
-YH_TRACK_HD yh_track_box yh_trk_box(const yh_track_kal& k) {
+YH_HD yh_track_box yh_trk_box(const yh_track_kal& k) {
     const float hw = k.x[2] * 0.5f, hh = k.x[3] * 0.5f;
     yh_track_box b;
     b.x1 = k.x[0] - hw;
@@ -87,7 +77,7 @@ YH_TRACK_HD yh_track_box yh_trk_box(const yh_track_kal& k) {
 }
 
 // the measurement of a detection row
-YH_TRACK_HD void yh_trk_measure(const yh_track_box& d, float z[4]) {
+YH_HD void yh_trk_measure(const yh_track_box& d, float z[4]) {
     z[0] = (d.x1 + d.x2) * 0.5f;
     z[1] = (d.y1 + d.y2) * 0.5f;
     z[2] = d.x2 - d.x1;
@@ -95,7 +85,7 @@ YH_TRACK_HD void yh_trk_measure(const yh_track_box& d, float z[4]) {
 }
 
 // step 4 of a matched slot
-YH_TRACK_HD void yh_trk_update(yh_track_kal& k, const yh_track_box& d) {
+YH_HD void yh_trk_update(yh_track_kal& k, const yh_track_box& d) {
     float z[4];
     yh_trk_measure(d, z);
     const float w = k.x[2], h = k.x[3];
@@ -116,7 +106,7 @@ YH_TRACK_HD void yh_trk_update(yh_track_kal& k, const yh_track_box& d) {
 }
 
 // step 5 of a new slot
-YH_TRACK_HD void yh_trk_birth(yh_track_kal& k, const yh_track_box& d) {
+YH_HD void yh_trk_birth(yh_track_kal& k, const yh_track_box& d) {
     float z[4];
     yh_trk_measure(d, z);
     for (int i = 0; i < 4; ++i) {
@@ -130,28 +120,15 @@ YH_TRACK_HD void yh_trk_birth(yh_track_kal& k, const yh_track_box& d) {
 }
 
 // step 3: is (slot box t, row box d) a candidate pair at threshold thr, and with which IoU?
-// (the class test is the caller's)
-YH_TRACK_HD bool yh_trk_pair(const yh_track_box& t, const yh_track_box& d, float thr, float& iou) {
-    const float w = yh_trk_clamp0(yh_trk_lesser(t.x2, d.x2) - yh_trk_greater(t.x1, d.x1));
-    const float h = yh_trk_clamp0(yh_trk_lesser(t.y2, d.y2) - yh_trk_greater(t.y1, d.y1));
-    const float inter = w * h;
+// (the class test is the caller's) The pair order is yh::float_order(iou) descending, then the
+// slot, then the row.
+YH_HD bool yh_trk_pair(const yh_track_box& t, const yh_track_box& d, float thr, float& iou) {
+    const float inter = yh::intersection(t.x1, t.y1, t.x2, t.y2, d.x1, d.y1, d.x2, d.y2);
     if (inter == 0.0f) return false;
     const float at = (t.x2 - t.x1) * (t.y2 - t.y1);
     const float ad = (d.x2 - d.x1) * (d.y2 - d.y1);
     iou = inter / ((at + ad) - inter);
     return iou >= thr;
-}
-
-// An unsigned that orders like the float (merge's sort key): the pair order of step 3 is this
-// value descending, then the slot, then the row.
-YH_TRACK_HD uint32_t yh_trk_ord(float v) {
-    uint32_t u;
-#ifdef __HIP_DEVICE_COMPILE__
-    u = __float_as_uint(v);
-#else
-    std::memcpy(&u, &v, 4);
-#endif
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 // NULL when the arguments are acceptable, else the message for yh_last_error() (YH_EINVAL).
