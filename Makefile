@@ -37,7 +37,7 @@ $(call objs,$(NET)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/net.h $(SRC)/host_util.h
 $(call objs,$(HOSTHIP)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/common.h $(HOST_H) include/yolo_hip.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(call objs,$(KERNELS)): $(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h $(SRC)/dtypes.h include/yolo_hip.h | $(OBJDIR)
+$(call objs,$(KERNELS)): $(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h $(SRC)/dtypes.h $(SRC)/mfma32.h $(SRC)/conv_mx.h include/yolo_hip.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(call objs,$(KERNELS_NOFMA)): $(OBJDIR)/%.o: $(SRC)/%.hip $(SRC)/common.h $(SRC)/dtypes.h include/yolo_hip.h | $(OBJDIR)
@@ -47,7 +47,6 @@ $(call objs,$(HOSTCXX)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/%.h $(SRC)/box_math.
 	$(HIPCC) -x c++ -O3 -fPIC -std=c++17 -Iinclude -I$(SRC) -ffp-contract=off -c $< -o $@
 
 # headers only some units of a group include
-$(call objs,conv_mx conv_rw): $(SRC)/conv_mx.h
 # each shares its arithmetic with its host twin through box_math.h and the twin's header
 $(call objs,match merge track): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
 # reports its argument errors through host_util.h's guarded(); its host functions use the pool

@@ -26,7 +26,7 @@
 // for 16-channel block: for tap: one v_mfma_f32_32x32x16 step, + bias, SiLU, one rounding
 // (pack2, as mx_epi); the residual is added to the rounded value in fp32 and rounded again.
 #include "common.h"
-#include "dtypes.h"
+#include "mfma32.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -35,49 +35,9 @@ namespace yh {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((ext_vector_type(2))) float ck_f32x2;
-
 constexpr int CK_NW = 16;                // waves per workgroup
 constexpr int CK_THREADS = 64 * CK_NW;
 constexpr int CK_MINRB = 4;              // rows per band at least (the 4-row halo recomputation)
-
-template <typename T> struct KMfma;
-template <> struct KMfma<__bf16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                       0, 0);
-    }
-};
-template <> struct KMfma<_Float16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                      0);
-    }
-};
-template <typename T> struct KPk2;
-template <> struct KPk2<__bf16> { typedef __attribute__((ext_vector_type(2))) __bf16 v2; };
-template <> struct KPk2<_Float16> { typedef __attribute__((ext_vector_type(2))) _Float16 v2; };
-// the rounding of conv_mx's epilogue (mx_epi's pack2)
-template <typename T>
-__device__ __forceinline__ unsigned ck_pack2(float a, float b) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(ck_f32x2{a, b}, typename KPk2<T>::v2));
-}
-template <typename T>
-__device__ __forceinline__ float ck_lo(unsigned u) { return (float)__builtin_bit_cast(T, (unsigned short)(u & 0xffffu)); }
-template <typename T>
-__device__ __forceinline__ float ck_hi(unsigned u) { return (float)__builtin_bit_cast(T, (unsigned short)(u >> 16)); }
-
-__device__ __forceinline__ void ck_glds(const void* src, unsigned lds_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds_addr) : "memory");
-#else
-    (void)src; (void)lds_addr;
-#endif
-}
-__device__ __forceinline__ void ck_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // swizzled 16-B chunk c of pixel p (C1 / T, HH channels = HH / 8 chunks per pixel):
 // consecutive pixels spread over the bank slots
@@ -94,7 +54,7 @@ __device__ __forceinline__ void ck_act(const f32x16& acc, const float* b, unsign
     for (int i = 0; i < 4; ++i) bv[i] = reinterpret_cast<const f32x4*>(b)[i];
 #pragma unroll
     for (int e = 0; e < 16; e += 2)
-        w[e >> 1] = ck_pack2<T>(silu<T>(acc[e] + bv[e >> 2][e & 3]), silu<T>(acc[e + 1] + bv[e >> 2][(e + 1) & 3]));
+        w[e >> 1] = pack2<T>(silu<T>(acc[e] + bv[e >> 2][e & 3]), silu<T>(acc[e + 1] + bv[e >> 2][(e + 1) & 3]));
 }
 
 // 1x1 conv step chain of one 32-cout tile: NK K blocks, A fragments from LDS at w (read
@@ -114,7 +74,7 @@ __device__ __forceinline__ f32x16 ck_1x1(const char* w, int lane, const uint4 (&
 #pragma unroll
     for (int st = 0; st < NK; ++st) {
         if (st + PF < NK) fa[(st + PF) % (PF + 1)] = *reinterpret_cast<const uint4*>(w + ((st + PF) * 64 + lane) * 16);
-        acc = KMfma<T>::step(fa[st % (PF + 1)], bv[st], acc);
+        acc = Mfma32<T>::step(fa[st % (PF + 1)], bv[st], acc);
     }
     __builtin_amdgcn_sched_group_barrier(0x100, PF, 0);
 #pragma unroll
@@ -244,7 +204,7 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
     if (r0 >= A.H) return;   // workgroup-uniform (no band rows: nothing issued yet)
     // LDS-DMA of `kb` 1-KB pieces from the parameter image at `src` to LDS offset `dst`
     auto dma = [&](int src, int dst, int kb) {
-        for (int i = wv; i < kb; i += CK_NW) ck_glds(prm + src + i * 1024 + lane * 16, lds0 + (unsigned)(dst + i * 1024));
+        for (int i = wv; i < kb; i += CK_NW) glds16(prm + src + i * 1024 + lane * 16, lds0 + (unsigned)(dst + i * 1024));
     };
     // ring item i -> buffer i % NB: the 3x3 sub-phases' 18-step weight images, then conv3's
     // weights in 16 KB items; waves 0..8 issue two 1-KB pieces each (pieces past an item's
@@ -264,7 +224,7 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int pc = 2 * wv + k;
-            ck_glds(prm + src + (pc < np ? pc : 0) * 1024 + lane * 16, dst + (unsigned)(pc * 1024));
+            glds16(prm + src + (pc < np ? pc : 0) * 1024 + lane * 16, dst + (unsigned)(pc * 1024));
         }
     };
 
@@ -302,8 +262,8 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
     }
     for (int i = 0; i < NB - NS; ++i) issue(i);
     if (wv < CK_IW) ck_wait_items(min(NB - NS, NITEMS));   // all but the ring items
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ck_barrier();
+    else vm_wait<0>();
+    lds_barrier();
     CK_STAMP(1);
 
     // ---- A: C1 = SiLU(conv1(x)) -> LDS; conv2(x) -> registers (its rows permuted: registers
@@ -340,7 +300,7 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
                     unsigned w[4];
 #pragma unroll
                     for (int e = 0; e < 8; e += 2)
-                        w[e >> 1] = ck_pack2<T>(silu<T>(acc[8 * jj + e] + bj[e]), silu<T>(acc[8 * jj + e + 1] + bj[e + 1]));
+                        w[e >> 1] = pack2<T>(silu<T>(acc[8 * jj + e] + bj[e]), silu<T>(acc[8 * jj + e + 1] + bj[e + 1]));
                     if (SPLIT) {
                         if (bv) *reinterpret_cast<uint4*>(C2 + ck_off<HH>(bp, 4 * t + 2 * jj + h)) = make_uint4(w[0], w[1], w[2], w[3]);
                     } else {
@@ -357,7 +317,7 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
         const T* xq = xrow(qv ? q : NRP - 1);
 #pragma unroll
         for (int kb = 0; kb < NK1; ++kb) xb[kb] = *reinterpret_cast<const uint4*>(xq + 16 * kb);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (ring items too: rare, harmless)
+        vm_wait<0>();   // (ring items too: rare, harmless)
         conv1_tile(q, qv);
     }
 
@@ -389,7 +349,7 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
         // this wave's pieces of the step's items landed (items issued so far: min(i0 + NB - NS,
         // NITEMS); the ones after the step's may stay in flight)
         if (wv < CK_IW) ck_wait_items(min(i0 + NB - NS, NITEMS) - min(i0 + NS, NITEMS));
-        ck_barrier();   // ... and everyone's; step j - 1's buffers and the previous phase are done
+        lds_barrier();   // ... and everyone's; step j - 1's buffers and the previous phase are done
         CK_STAMP(3 + j);
 #pragma unroll
         for (int k = 0; k < NS; ++k) issue(i0 + NB - NS + k);
@@ -462,7 +422,7 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
 #pragma unroll
         for (int st = 0; st < 18; ++st) {
             if (st + CK_PF < 18) ld(st + CK_PF);
-            acc = KMfma<T>::step(fa[st % (CK_PF + 1)], fb[st % (CK_PF + 1)], acc);
+            acc = Mfma32<T>::step(fa[st % (CK_PF + 1)], fb[st % (CK_PF + 1)], acc);
         }
         // keep that order through scheduling (it would otherwise sink the reads to one step ahead)
         __builtin_amdgcn_sched_group_barrier(0x100, 2 * CK_PF, 0);
@@ -481,7 +441,7 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
                 const uint4 q1 = *reinterpret_cast<const uint4*>(C1 + o1);
                 const unsigned rv[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
 #pragma unroll
-                for (int q = 0; q < 8; ++q) w[q] = ck_pack2<T>(ck_lo<T>(w[q]) + ck_lo<T>(rv[q]), ck_hi<T>(w[q]) + ck_hi<T>(rv[q]));
+                for (int q = 0; q < 8; ++q) w[q] = pack2<T>(lo16<T>(w[q]) + lo16<T>(rv[q]), hi16<T>(w[q]) + hi16<T>(rv[q]));
             }
             *reinterpret_cast<uint4*>(dst + o0) = make_uint4(w[0], w[1], w[2], w[3]);
             *reinterpret_cast<uint4*>(dst + o1) = make_uint4(w[4], w[5], w[6], w[7]);

@@ -26,40 +26,13 @@
 // tile a holds couts 32a + 16hh .. +15 in its 16 accumulator registers, so every
 // epilogue store is two 16-B chunks.
 #include "common.h"
-#include "dtypes.h"
+#include "mfma32.h"
 
 namespace yh {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <typename T> struct CMfma;
-template <> struct CMfma<__bf16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                       0, 0);
-    }
-};
-template <> struct CMfma<_Float16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                      0);
-    }
-};
-
 constexpr int NWV = CSP_THREADS / 64;
-
-__device__ __forceinline__ void cs_glds(const void* src, unsigned lds_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds_addr) : "memory");
-#else
-    (void)src; (void)lds_addr;
-#endif
-}
-__device__ __forceinline__ void cs_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // s_waitcnt vmcnt(N) for the largest encodable N <= n of {8, 4, 2, 0} (n wave-uniform)
 __device__ __forceinline__ void cs_wait_vm(int n) {
@@ -251,8 +224,8 @@ __device__ __forceinline__ void cs_phase(unsigned aimg, int npx, HcDiv dv, int R
             for (int k = 0; k < NK; ++k) {
                 const uint4 f0 = cs_rd(ai0 + k * 1024), f1 = NA > 1 ? cs_rd(ai1 + k * 1024) : f0;
                 const uint4 x0 = cs_rd(baddr(B0, k)), x1 = cs_rd(baddr(B1, k));
-                acc0 = CMfma<T>::step(f0, x0, k ? acc0 : zero);
-                acc1 = CMfma<T>::step(f1, x1, k ? acc1 : zero);
+                acc0 = Mfma32<T>::step(f0, x0, k ? acc0 : zero);
+                acc1 = Mfma32<T>::step(f1, x1, k ? acc1 : zero);
             }
             if (p0 < npx) epi(a0, p0, r0, cc0, acc0);
             if (p1 < npx) epi(a1, p1, r1, cc1, acc1);
@@ -260,7 +233,7 @@ __device__ __forceinline__ void cs_phase(unsigned aimg, int npx, HcDiv dv, int R
             f32x16 acc0;
 #pragma unroll
             for (int k = 0; k < NK; ++k)
-                acc0 = CMfma<T>::step(cs_rd(ai0 + k * 1024), cs_rd(baddr(B0, k)), k ? acc0 : zero);
+                acc0 = Mfma32<T>::step(cs_rd(ai0 + k * 1024), cs_rd(baddr(B0, k)), k ? acc0 : zero);
             if (p0 < npx) epi(a0, p0, r0, cc0, acc0);
         }
     }
@@ -290,7 +263,7 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
     // parameters: once per workgroup
     {
         const char* prm = reinterpret_cast<const char*>(A.prm);
-        for (int i0 = wvu * 64; i0 < L.prm / 16; i0 += CSP_THREADS) cs_glds(prm + (size_t)(i0 + lane) * 16, lds0 + i0 * 16);
+        for (int i0 = wvu * 64; i0 < L.prm / 16; i0 += CSP_THREADS) glds16(prm + (size_t)(i0 + lane) * 16, lds0 + i0 * 16);
     }
     // tail mode (NI == 0): the block input is conv1's output [a | b] (2c channels, computed
     // by its own launch) and lands straight in T1; P1 is skipped
@@ -330,7 +303,7 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                 const unsigned r = d_rc[j] & 0xffffu, cc = d_rc[j] >> 16;
                 const bool ok = r - rlo < rn && cc - clo < cn;
                 const void* src = ok ? (const void*)(base + d_off[j]) : A.zero;
-                cs_glds(src, LD + i0 * 16);
+                glds16(src, LD + i0 * 16);
             }
         }
     };
@@ -380,7 +353,7 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
         CS_STAMP(0);
         cs_wait_vm(young);   // this wave's input DMAs of this tile have landed
         CS_STAMP(1);
-        cs_barrier();
+        lds_barrier();
         CS_STAMP(2);
 
         // P1: conv1 over the halo tile, X -> T1 (zero outside the image)
@@ -398,7 +371,7 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                     cs_wr(d + 16, o[1]);
                 });
         CS_STAMP(3);
-        cs_barrier();
+        lds_barrier();
         CS_STAMP(4);
         if (t + NG < A.ntiles) load_x(nn, nty, ntx);   // X is dead: next tile's input
         }
@@ -432,7 +405,7 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                 cs_wr(d + 16, o[1]);
             });
         CS_STAMP(5);
-        cs_barrier();
+        lds_barrier();
         CS_STAMP(6);
 
         // P3: Residual conv2 (3x3, R1 -> C2) + b over the tile
@@ -481,7 +454,7 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                     cs_wr(d + 16, o[1]);
                 });
         CS_STAMP(7);
-        cs_barrier();
+        lds_barrier();
         CS_STAMP(8);
 
         // P4: conv2 over cat [a | b | C2] -> block output
@@ -507,14 +480,14 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
         CS_STAMP(9);
         if constexpr (!TAIL) young = h0 + TH <= A.H && w0 + TW <= A.W ? p4_stores : 0;
         if constexpr (TAIL) {   // T1 is read until here: the next tile's input after a barrier
-            cs_barrier();
+            lds_barrier();
             if (t + NG < A.ntiles) load_x(nn, nty, ntx);
         }
         n = nn;
         ty = nty;
         tx = ntx;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
 }
 
 // instantiated (ni, nc, no): v11_n p2.1 (2, 1, 2), p3.1 and v11_s p2.1 (4, 2, 4); tail mode

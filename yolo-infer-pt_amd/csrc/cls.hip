@@ -13,27 +13,11 @@
 // dtype, exactly what the per-layer conv stores. Nothing in the order depends on the batch size, on
 // the image's place in the batch or on the conv plan.
 #include "common.h"
-#include "dtypes.h"
+#include "mfma32.h"
 
 namespace yh {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <typename T> struct CMfma;
-template <> struct CMfma<__bf16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                       0, 0);
-    }
-};
-template <> struct CMfma<_Float16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                      0);
-    }
-};
 
 // v as an fp32 register value. Without it the compiler folds SiLU's last multiplication and the
 // conversion to fp16 into one v_fma_mixlo_f16, i.e. one rounding, where the per-layer conv rounds
@@ -124,7 +108,7 @@ __global__ __launch_bounds__(CLS_THREADS) void cls_head(const ClsHeadArgs A) {
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (j < nt) acc[j] = CMfma<T>::step(f[ih * 4 + i], x[j][i], acc[j]);
+                        if (j < nt) acc[j] = Mfma32<T>::step(f[ih * 4 + i], x[j][i], acc[j]);
             }
         }
         // register i of lane (l32, h): cout 32 a + (i & 3) + 8 (i >> 2) + 4 h, pixel 32 j + l32

@@ -15,7 +15,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "dtypes.h"
+#include "mfma32.h"
 
 namespace yh {
 
@@ -81,9 +81,7 @@ __global__ __launch_bounds__(NT_) void conv_gemm(const ConvArgs p) {
     const long long bs1 = (long long)p.h1 * p.w1 * p.ldc1;
 
     Chunk<T> ra[CA];
-    Chunk<T> rb;
     const int bchunks = BN * (BK / 8);
-    const bool bload = tid < bchunks || bchunks > NT_;  // BN <= 128 -> bchunks <= 512
     constexpr int CB = (BN * (BK / 8) + NT_ - 1) / NT_;
     Chunk<T> rbv[CB];
 
@@ -128,7 +126,6 @@ __global__ __launch_bounds__(NT_) void conv_gemm(const ConvArgs p) {
             if (c < bchunks) st_chunk(b + (c >> 2) * LDK + (c & 3) * 8, rbv[j]);
         }
     };
-    (void)rb; (void)bload;
 
     typename Mma<T>::acc_t acc[NTL][MT];
 #pragma unroll
@@ -548,24 +545,6 @@ constexpr int S2_IR = 2 * S2_SR + 1;                          // input rows per 
 constexpr int S2_ICH = (4 * S2_TW + 32) / 8;                  // 8-element chunks per input row
 constexpr int S2_ISEG = 8 * S2_ICH;                           // staged columns (from 4 wo0 - 32: 64-B aligned)
 constexpr int S2_NPX = S2_SR * S2_SC;                         // stem pixels per tile
-typedef __attribute__((ext_vector_type(16))) float f32x16_s;
-
-template <typename T>
-__device__ __forceinline__ f32x16_s s2_mfma(const uint4& a, const uint4& b, const f32x16_s& c) {
-    if constexpr (std::is_same<T, __bf16>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                       0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                      0);
-}
-template <typename T>
-__device__ __forceinline__ unsigned s2_pack2(float a, float b) {
-    typedef __attribute__((ext_vector_type(2))) float f2;
-    typedef __attribute__((ext_vector_type(2))) T t2;
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, t2));
-}
-
 // byte offset of stem tap k = ci*9 + kh*3 + kw in the staged window (0 for the K padding)
 constexpr int s2_tap(int k) {
     return k < 27 ? 2 * ((k / 9 * S2_IR + k % 9 / 3) * S2_ISEG + k % 3) : 0;
@@ -681,8 +660,8 @@ __global__ __launch_bounds__(S2_NT) void stem_fused(const Stem2Args p) {
             for (int i = 0; i < C1; ++i) {
                 f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
                 Mma<T>::step(acc, &wf[i], &xf);
-                const unsigned u01 = s2_pack2<T>(silu<T>(acc[0] + bv[i].x), silu<T>(acc[1] + bv[i].y));
-                const unsigned u23 = s2_pack2<T>(silu<T>(acc[2] + bv[i].z), silu<T>(acc[3] + bv[i].w));
+                const unsigned u01 = pack2<T>(silu<T>(acc[0] + bv[i].x), silu<T>(acc[1] + bv[i].y));
+                const unsigned u23 = pack2<T>(silu<T>(acc[2] + bv[i].z), silu<T>(acc[3] + bv[i].w));
                 *reinterpret_cast<uint2*>(so + 32 * i) = make_uint2(live ? u01 : 0u, live ? u23 : 0u);
             }
         };
@@ -720,21 +699,21 @@ __global__ __launch_bounds__(S2_NT) void stem_fused(const Stem2Args p) {
 #pragma unroll
         for (int k = 0; k < RPW; ++k) {
             const int r = wave / C2 + k * (4 / C2);
-            f32x16_s acc;
+            f32x16 acc;
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 const int cb = s / 9, tap = s - 9 * cb, kh = tap / 3, kw = tap - 3 * kh;
                 const int q = (2 * r + kh) * S2_SC + 2 * l32 + kw;
-                acc = s2_mfma<T>(af[s], sout[q * PS + 2 * cb + h], acc);
+                acc = Mfma32<T>::step(af[s], sout[q * PS + 2 * cb + h], acc);
             }
             // the row's 32 pixels x 32 couts through the wave's 2 KB of the (dead) input window:
             // 4 lanes per pixel store 64 contiguous bytes (one pixel per lane would write 2 x 16 B
             // of each of 32 pixels per instruction; conv_mx.hip co_stage)
             unsigned w[8];
 #pragma unroll
-            for (int e = 0; e < 16; e += 2) w[e >> 1] = s2_pack2<T>(silu<T>(acc[e] + b2[e]), silu<T>(acc[e + 1] + b2[e + 1]));
+            for (int e = 0; e < 16; e += 2) w[e >> 1] = pack2<T>(silu<T>(acc[e] + b2[e]), silu<T>(acc[e + 1] + b2[e + 1]));
             char* E = reinterpret_cast<char*>(&patch[0][0]) + wave * 2048;
             const int sw = (l32 >> 1) & 3;
             *reinterpret_cast<uint4*>(E + (l32 * 4 + ((2 * h) ^ sw)) * 16) = make_uint4(w[0], w[1], w[2], w[3]);

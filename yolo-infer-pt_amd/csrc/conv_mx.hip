@@ -6,7 +6,7 @@
 //   * a task is an output tile of one image (3x3: TH rows x TW cols; 1x1: TW
 //     consecutive pixels) times one BN-wide cout slice;
 //   * its K walk is cut into stages of NCB 16-channel blocks. A stage brings two
-//     LDS images in by LDS-DMA (global_load_lds_dwordx4, 16 B per lane, linear
+//     LDS images in by LDS-DMA (glds16 in mfma32.h, 16 B per lane, linear
 //     destination): the weight image of the stage (pre-packed in HBM exactly as
 //     it lies in LDS) and the input PATCH of the task for those channels (every
 //     input pixel the tile's taps touch, with a zero border, once: the 3x3 halo is
@@ -21,14 +21,12 @@
 //     residual) stores 16-B chunks straight from registers.
 // Reduction order: see conv_mx.h (for cb16: for tap: one MFMA step).
 #include "conv_mx.h"
-#include "dtypes.h"
+#include "mfma32.h"
 
 #include <algorithm>
 #include <cstring>
 
 namespace yh {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // ablation switches of the micro benchmark (tools/micro, -DYH_ABLATION); constant 0 / off
 // in the shipped library
@@ -42,80 +40,35 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace {
 
-// 16-byte LDS-DMA hidden from hipcc's waitcnt pass (ordering: the kernel's own
-// counted vmcnt + barrier). M0 is saved and restored inside the statement.
-__device__ __forceinline__ void mx_glds(const void* src, unsigned lds_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds_addr) : "memory");
-#else
-    (void)src; (void)lds_addr;
-#endif
-}
-
 __device__ __forceinline__ void mx_vmwait(int n) {
     switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-        case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-        case 17: asm volatile("s_waitcnt vmcnt(17)" ::: "memory"); break;
-        case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-        case 19: asm volatile("s_waitcnt vmcnt(19)" ::: "memory"); break;
-        case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-        case 21: asm volatile("s_waitcnt vmcnt(21)" ::: "memory"); break;
-        case 22: asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); break;
-        case 23: asm volatile("s_waitcnt vmcnt(23)" ::: "memory"); break;
-        case 24: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+        case 0: vm_wait<0>(); break;
+        case 1: vm_wait<1>(); break;
+        case 2: vm_wait<2>(); break;
+        case 3: vm_wait<3>(); break;
+        case 4: vm_wait<4>(); break;
+        case 5: vm_wait<5>(); break;
+        case 6: vm_wait<6>(); break;
+        case 7: vm_wait<7>(); break;
+        case 8: vm_wait<8>(); break;
+        case 9: vm_wait<9>(); break;
+        case 10: vm_wait<10>(); break;
+        case 11: vm_wait<11>(); break;
+        case 12: vm_wait<12>(); break;
+        case 13: vm_wait<13>(); break;
+        case 14: vm_wait<14>(); break;
+        case 15: vm_wait<15>(); break;
+        case 16: vm_wait<16>(); break;
+        case 17: vm_wait<17>(); break;
+        case 18: vm_wait<18>(); break;
+        case 19: vm_wait<19>(); break;
+        case 20: vm_wait<20>(); break;
+        case 21: vm_wait<21>(); break;
+        case 22: vm_wait<22>(); break;
+        case 23: vm_wait<23>(); break;
+        case 24: vm_wait<24>(); break;
+        default: vm_wait<0>(); break;
     }
-}
-
-__device__ __forceinline__ void mx_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
-
-__device__ __forceinline__ uint32_t fdiv(uint32_t x, FastDiv d) {
-    return (uint32_t)(((uint64_t)__umulhi(x, d.m) + x) >> d.s);
-}
-
-template <typename T> struct Mfma32;
-template <> struct Mfma32<__bf16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                       0, 0);
-    }
-};
-template <> struct Mfma32<_Float16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                      0);
-    }
-};
-
-__device__ __forceinline__ uint4 lds_rd(unsigned addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(3))) const uint4* lp;
-    return *reinterpret_cast<lp>((size_t)addr);
-#else
-    (void)addr;
-    return uint4{};
-#endif
 }
 
 }  // namespace
@@ -127,29 +80,6 @@ __device__ __forceinline__ uint4 lds_rd(unsigned addr) {
 // and rounds again (nets/nn.py:49, 135-136), stores 16-B chunks. Only `nc8` chunks
 // (couts [8*c8, 8*c8+8) < Cout) are stored; loads are unconditional (callers clamp
 // the addresses), so no load is ever left unconsumed.
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-template <typename T> struct Pk2;
-template <> struct Pk2<__bf16> {
-    typedef __attribute__((ext_vector_type(2))) __bf16 v2;
-};
-template <> struct Pk2<_Float16> {
-    typedef __attribute__((ext_vector_type(2))) _Float16 v2;
-};
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    typedef typename Pk2<T>::v2 v2;
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, v2));
-}
-template <typename T>
-__device__ __forceinline__ float lo16(unsigned u) {
-    const unsigned short s = (unsigned short)(u & 0xffffu);
-    return (float)__builtin_bit_cast(T, s);
-}
-template <typename T>
-__device__ __forceinline__ float hi16(unsigned u) {
-    const unsigned short s = (unsigned short)(u >> 16);
-    return (float)__builtin_bit_cast(T, s);
-}
 template <typename T, int NA, bool SILU, bool RES>
 __device__ __forceinline__ void mx_epi(const f32x16 (&acc)[NA], const float* bv, T* outp, const T* resp, int nc8) {
 #pragma unroll
@@ -302,7 +232,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void conv_mx(const MxArgs p) {
 #pragma unroll
     for (int i = 0; i < MX_MAXB; ++i) {
         const uint32_t q = (uint32_t)((i * NW + wv) * 64 + lane);
-        const uint32_t rs = fdiv(q, p.d_pcc);
+        const uint32_t rs = fast_div(q, p.d_pcc);
         const uint32_t rem = q - rs * (uint32_t)(p.PC * CPS);
         const uint32_t lc = rem / CPS, cpos = rem & (CPS - 1);
         const uint32_t f = ((lc >> p.sw_sh) + rs * p.sw_mr) & (CPS - 1);
@@ -355,12 +285,12 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void conv_mx(const MxArgs p) {
     int fill_seg = -1;
     int f_n = 0, f_h0 = 0, f_w0 = 0, f_sl = 0;
     auto decompose = [&](int tk, int& n, int& hh0, int& ww0, int& sl) {
-        const uint32_t a = fdiv((uint32_t)tk, p.d_nsl);
+        const uint32_t a = fast_div((uint32_t)tk, p.d_nsl);
         sl = tk - (int)a * p.nslices;
-        const uint32_t b = fdiv(a, p.d_ntw);
+        const uint32_t b = fast_div(a, p.d_ntw);
         const int tw = (int)(a - b * p.ntw);
         if constexpr (KS == 3) {
-            const uint32_t c = fdiv(b, p.d_nth);
+            const uint32_t c = fast_div(b, p.d_nth);
             const int th = (int)(b - c * p.nth);
             n = (int)c;
             hh0 = th * p.TH;
@@ -398,9 +328,9 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void conv_mx(const MxArgs p) {
                 if (!gen1) {
                     sptr[i] = ok ? base + (long long)f_w0 * ldc * 2 + (seg ? slot_off1[i] : slot_off0[i]) : nullptr;
                 } else {
-                    const uint32_t n = fdiv((uint32_t)m, p.d_howo);
+                    const uint32_t n = fast_div((uint32_t)m, p.d_howo);
                     const uint32_t rr = (uint32_t)m - n * (uint32_t)(p.Ho * p.Wo);
-                    const uint32_t ho = fdiv(rr, p.d_wo);
+                    const uint32_t ho = fast_div(rr, p.d_wo);
                     const uint32_t wo = rr - ho * (uint32_t)p.Wo;
                     const long long pix = ((long long)n * hs + (ho >> up)) * ws + (wo >> up);
                     sptr[i] = ok ? base + pix * ldc * 2 + c * 16 : nullptr;
@@ -421,7 +351,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void conv_mx(const MxArgs p) {
             const char* wsrc = p.w + ((long long)f_sl * p.nst + st) * p.wstage + (long long)(wv * 64 + lane) * 16;
 #pragma unroll
             for (int i = 0; i < AINS; ++i)
-                mx_glds(wsrc + (long long)i * NT * 16, sbase + (unsigned)((i * NW + wv) * 1024));
+                glds16(wsrc + (long long)i * NT * 16, sbase + (unsigned)((i * NW + wv) * 1024));
         }
         // patch
         const int ch0 = st * NCB * 16;
@@ -436,7 +366,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void conv_mx(const MxArgs p) {
                 if (i < nbi) {
                     const int c = (slot_geo[i] >> 22) & 15;
                     const bool ok = sptr[i] != nullptr && c < clim;
-                    mx_glds(ok ? (const void*)(sptr[i] + coff) : (const void*)p.zero, bb + (unsigned)((i * NW + wv) * 1024));
+                    glds16(ok ? (const void*)(sptr[i] + coff) : (const void*)p.zero, bb + (unsigned)((i * NW + wv) * 1024));
                 }
             }
         }
@@ -505,7 +435,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void conv_mx(const MxArgs p) {
         const T* res = reinterpret_cast<const T*>(p.res);
         T* out = reinterpret_cast<T*>(p.out);
         if (co_fits) {
-            mx_barrier();
+            lds_barrier_sched();
             char* E = reinterpret_cast<char*>(sm4) + ((g & 1) * stage_ch) * 16 + wv * 2048 * NA;
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
@@ -555,7 +485,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void conv_mx(const MxArgs p) {
         const bool more = g + 1 < nstages;
         if (more) issue(g + 1, (g + 1) & 1);
         mx_vmwait(more ? per_stage : 0);
-        mx_barrier();
+        lds_barrier_sched();
         if (MX_TRACE && g == 0) t_first = __builtin_amdgcn_s_memrealtime();
         const int st = g - (g / p.nst) * p.nst;
         if (st == 0) {
@@ -568,7 +498,7 @@ __global__ __launch_bounds__(64 * WN * WM, 2) void conv_mx(const MxArgs p) {
         }
         if (!(MX_DBG(4))) compute((g & 1) * stage_ch);
         if (st == p.nst - 1 && !(MX_DBG(8))) epilogue(t_lo + g / p.nst, g);
-        mx_barrier();
+        lds_barrier_sched();
     }
     if (MX_TRACE && threadIdx.x == 0) {
         unsigned long long* tr = MX_TRACE + blockIdx.x * 4;
@@ -623,10 +553,10 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_mxr(const MxArgs p) {
         const char* wsrc = p.w + (long long)sl * p.wstage;
         if (!(MX_DBG(1024)))
             for (int q = wv * 64; q < wch; q += 64 * NW)   // wch: a multiple of 64 chunks
-                mx_glds(wsrc + (long long)(q + lane) * 16, lds0 + (unsigned)q * 16);
+                glds16(wsrc + (long long)(q + lane) * 16, lds0 + (unsigned)q * 16);
         if (threadIdx.x < BN / 4)
             sm4[bias_ch + threadIdx.x] = *reinterpret_cast<const uint4*>(p.bias + sl * BN + threadIdx.x * 4);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vm_wait<0>();
         __syncthreads();
     }
     if (t_lo >= t_hi) return;
@@ -639,7 +569,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_mxr(const MxArgs p) {
 #pragma unroll
     for (int i = 0; i < NBI; ++i) {
         const uint32_t q = (uint32_t)(i * 64 + lane);
-        const uint32_t rs = fdiv(q, p.d_pcc);
+        const uint32_t rs = fast_div(q, p.d_pcc);
         const uint32_t rem = q - rs * (uint32_t)(p.PC * CPS);
         const uint32_t lc = rem / CPS, cpos = rem & (CPS - 1);
         const uint32_t f = ((lc >> p.sw_sh) + rs * p.sw_mr) & (CPS - 1);
@@ -692,9 +622,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_mxr(const MxArgs p) {
     int f_n = 0, f_h0 = 0, f_w0 = 0;
     auto tile_pos = [&](int tk, int& n, int& hh0, int& ww0) {
         if constexpr (KS == 3) {
-            const uint32_t b = fdiv((uint32_t)tk, p.d_ntw);
+            const uint32_t b = fast_div((uint32_t)tk, p.d_ntw);
             const int tw = tk - (int)b * p.ntw;
-            const uint32_t c = fdiv(b, p.d_nth);
+            const uint32_t c = fast_div(b, p.d_nth);
             n = (int)c;
             hh0 = ((int)b - (int)c * p.nth) * p.TH;
             ww0 = tw * p.TW;
@@ -729,9 +659,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_mxr(const MxArgs p) {
                 if (!gen1) {
                     sptr[i] = ok ? base + (long long)f_w0 * ldc * 2 + (seg ? slot_off1[i] : slot_off0[i]) : nullptr;
                 } else {
-                    const uint32_t n = fdiv((uint32_t)m, p.d_howo);
+                    const uint32_t n = fast_div((uint32_t)m, p.d_howo);
                     const uint32_t rr = (uint32_t)m - n * (uint32_t)(p.Ho * p.Wo);
-                    const uint32_t ho = fdiv(rr, p.d_wo);
+                    const uint32_t ho = fast_div(rr, p.d_wo);
                     const uint32_t wo = rr - ho * (uint32_t)p.Wo;
                     const long long pix = ((long long)n * hs + (ho >> up)) * ws + (wo >> up);
                     sptr[i] = ok ? base + pix * ldc * 2 + c * 16 : nullptr;
@@ -756,7 +686,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_mxr(const MxArgs p) {
         for (int i = 0; i < NBI; ++i) {
             const int c = (slot_geo[i] >> 22) & 15;
             const bool ok = sptr[i] != nullptr && c < clim && !MX_DBG(2);
-            mx_glds(ok ? (const void*)(sptr[i] + coff) : (const void*)p.zero, bb + (unsigned)(i * 1024));
+            glds16(ok ? (const void*)(sptr[i] + coff) : (const void*)p.zero, bb + (unsigned)(i * 1024));
         }
     };
 
@@ -855,9 +785,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_mxr(const MxArgs p) {
         const bool more = g + 1 < nstages;
         if (NBUF == 2 && more) {
             issue(g + 1);
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NBI) : "memory");
+            vm_wait<NBI>();
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            vm_wait<0>();
         }
         const int st = g - (g / p.nst) * p.nst;
         if (st == 0) {

@@ -13,7 +13,7 @@
 //     output tiles (TH x TW pixels of one image, all couts of its slice); wave (cg, pg)
 //     owns cout group cg (32 couts) and MB 32-pixel B tiles of pixel group pg;
 //   * a slot holds a tile's whole input patch (every input channel, full 128-B pixel lines
-//     for Cin = 64), filled by LDS-DMA (global_load_lds_dwordx4) by all waves; the slots
+//     for Cin = 64), filled by LDS-DMA (glds16 in mfma32.h) by all waves; the slots
 //     of the next NS-1 tiles are in flight while a tile is multiplied;
 //   * per tile: counted vmcnt (the wave's own DMA of this tile landed; later DMAs and the
 //     previous tiles' stores stay in flight) -> one barrier -> issue the DMA of tile
@@ -26,7 +26,7 @@
 //     pixel (out-of-image pixels get an offset past the buffer's range, which the
 //     hardware drops), so the vmcnt arithmetic is exact.
 #include "conv_mx.h"
-#include "dtypes.h"
+#include "mfma32.h"
 
 #include <algorithm>
 #include <cstring>
@@ -38,10 +38,8 @@
 
 namespace yh {
 
-typedef __attribute__((ext_vector_type(16))) float rw_f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int rw_u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int rw_u32x2;
-typedef __attribute__((ext_vector_type(2))) float rw_f32x2;
 
 RwGeo rw_geo(int S, int cin, int ncg, int npg, int mb, int tw, bool res, int nkc) {
     RwGeo g;
@@ -79,27 +77,6 @@ namespace {
 constexpr unsigned RW_OOB = 0x7ffffff0u;         // buffer offset past every valid byte: dropped
 constexpr int RW_NUM_RECORDS = 0x7ffffff0;
 
-__device__ __forceinline__ void rw_glds(const void* src, unsigned lds_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds_addr) : "memory");
-#else
-    (void)src; (void)lds_addr;
-#endif
-}
-
-template <int N>
-__device__ __forceinline__ void rw_vmwait() {
-    static_assert(N >= 0 && N <= 63, "vmcnt is 6 bits");
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-}
-
-__device__ __forceinline__ void rw_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
-
 // LDS column of patch column pcol (and back): stride 2 stores a row's even columns first
 template <int S, int PC>
 __host__ __device__ constexpr int rw_lcol(int pcol) {
@@ -109,36 +86,6 @@ template <int S, int PC>
 __host__ __device__ constexpr int rw_gcol(int lcol) {
     return S == 2 ? (lcol < (PC + 1) / 2 ? 2 * lcol : 2 * (lcol - (PC + 1) / 2) + 1) : lcol;
 }
-
-__device__ __forceinline__ uint32_t rw_fdiv(uint32_t x, FastDiv d) {
-    return (uint32_t)(((uint64_t)__umulhi(x, d.m) + x) >> d.s);
-}
-
-template <typename T> struct RwMfma;
-template <> struct RwMfma<__bf16> {
-    static __device__ __forceinline__ rw_f32x16 step(const uint4& a, const uint4& b, const rw_f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                       0, 0);
-    }
-};
-template <> struct RwMfma<_Float16> {
-    static __device__ __forceinline__ rw_f32x16 step(const uint4& a, const uint4& b, const rw_f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                      0);
-    }
-};
-
-template <typename T> struct RwPk2;
-template <> struct RwPk2<__bf16> { typedef __attribute__((ext_vector_type(2))) __bf16 v2; };
-template <> struct RwPk2<_Float16> { typedef __attribute__((ext_vector_type(2))) _Float16 v2; };
-template <typename T>
-__device__ __forceinline__ unsigned rw_pack2(float a, float b) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(rw_f32x2{a, b}, typename RwPk2<T>::v2));
-}
-template <typename T>
-__device__ __forceinline__ float rw_lo(unsigned u) { return (float)__builtin_bit_cast(T, (unsigned short)(u & 0xffffu)); }
-template <typename T>
-__device__ __forceinline__ float rw_hi(unsigned u) { return (float)__builtin_bit_cast(T, (unsigned short)(u >> 16)); }
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rw_rsrc(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, RW_NUM_RECORDS, 0x00020000);
@@ -239,9 +186,9 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
 
     auto tile_pos = [&](int it, int& n, int& ty0, int& tx0) {
         const int t = lw + it * wps;
-        const uint32_t b = rw_fdiv((uint32_t)t, p.d_ntw);
+        const uint32_t b = fast_div((uint32_t)t, p.d_ntw);
         tx0 = (t - (int)b * p.ntw) * TW;
-        const uint32_t c = rw_fdiv(b, p.d_nth);
+        const uint32_t c = fast_div(b, p.d_nth);
         ty0 = ((int)b - (int)c * p.nth) * TH;
         n = (int)c;
     };
@@ -259,7 +206,7 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
                 const int g = fgeo[i];
                 const int gy = gy0 + (g & 255), gx = gx0 + ((g >> 8) & 255);
                 const bool ok = g >= 0 && (unsigned)gy < (unsigned)p.Hi && (unsigned)gx < (unsigned)p.Wi;
-                rw_glds(ok ? (const void*)(base + foff[i]) : (const void*)p.zero, sb + (unsigned)(i * NW * 1024));
+                glds16(ok ? (const void*)(base + foff[i]) : (const void*)p.zero, sb + (unsigned)(i * NW * 1024));
             }
             if constexpr (RES) {
                 const int cbase = (sl * NCG) * 64;   // byte offset of the slice's couts
@@ -270,12 +217,12 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
                     const int oy = ty0 + px / TW, ox = tx0 + px % TW;
                     const bool ok = g >= 0 && oy < p.Ho && ox < p.Wo;
                     const char* src = p.res + (((long long)n * p.Ho + oy) * p.Wo + ox) * p.ldr * 2 + cbase + c * 16;
-                    rw_glds(ok ? (const void*)src : (const void*)p.zero, sb + (unsigned)((NBI + i) * NW * 1024));
+                    glds16(ok ? (const void*)src : (const void*)p.zero, sb + (unsigned)((NBI + i) * NW * 1024));
                 }
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < NBI + NBR; ++i) rw_glds(p.zero, sb + (unsigned)(i * NW * 1024));
+            for (int i = 0; i < NBI + NBR; ++i) glds16(p.zero, sb + (unsigned)(i * NW * 1024));
         }
     };
 
@@ -301,14 +248,14 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
         const int rot = (int)(blockIdx.x % NQ);
         for (int q0 = wv; q0 < NQ; q0 += NW) {
             const int q = q0 + rot < NQ ? q0 + rot : q0 + rot - NQ;
-            rw_glds(wimg + ((long long)q * 64 + lane) * 16, lds0 + (unsigned)(WOFF + q * 1024));
+            glds16(wimg + ((long long)q * 64 + lane) * 16, lds0 + (unsigned)(WOFF + q * 1024));
         }
-        rw_vmwait<0>();
-        rw_barrier();
+        vm_wait<0>();
+        lds_barrier_sched();
         const char* wl = reinterpret_cast<const char*>(sm4) + WOFF + ((cg * NKT + kc * NKS) * 64 + lane) * 16;
 #pragma unroll
         for (int s = 0; s < NKS; ++s) wf[s] = *reinterpret_cast<const uint4*>(wl + s * 1024);
-        rw_barrier();   // every wave holds its fragments: the rest of the ring may be filled
+        lds_barrier_sched();   // every wave holds its fragments: the rest of the ring may be filled
         for (int k = EARLY; k < NS - 1; ++k) issue(k, k);
     } else {
         for (int k = 0; k < NS - 1; ++k) issue(k, k);
@@ -324,15 +271,15 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
     // where its vmcnt(0) would drain the patch ring every iteration)
 #pragma unroll
     for (int s = 0; s < NKS; ++s) asm volatile("" :: "v"(wf[s].x), "v"(wf[s].y), "v"(wf[s].z), "v"(wf[s].w));
-    rw_vmwait<0>();
-    rw_barrier();
+    vm_wait<0>();
+    lds_barrier_sched();
     const unsigned long long t_setup = RW_TRACE ? __builtin_amdgcn_s_memrealtime() : 0ull;
     unsigned long long t_first = 0ull;
 
     const __amdgpu_buffer_rsrc_t ro = rw_rsrc(p.out);
     const bool silu_act = p.act == ACT_SILU;
 
-    rw_f32x16 acc[MB];
+    f32x16 acc[MB];
     // ---- epilogue (chunk-0 waves): bias, activation, one rounding (the conv output), the
     //      residual added in fp32 and rounded again (nets/nn.py:49). The wave's 32 pixels x
     //      32 couts go through its private LDS staging tile (lane (r32, h) writes its 16
@@ -361,7 +308,7 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
                         x0 = silu<T>(x0);
                         x1 = silu<T>(x1);
                     }
-                    w[e >> 1] = rw_pack2<T>(x0, x1);
+                    w[e >> 1] = pack2<T>(x0, x1);
                 }
                 const int q = 2 * h + c;
                 *reinterpret_cast<uint4*>(E + (r32 * 4 + (q ^ ((r32 >> 1) & 3))) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -382,7 +329,7 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
                     const unsigned rv[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        w[q] = rw_pack2<T>(rw_lo<T>(w[q]) + rw_lo<T>(rv[q]), rw_hi<T>(w[q]) + rw_hi<T>(rv[q]));
+                        w[q] = pack2<T>(lo16<T>(w[q]) + lo16<T>(rv[q]), hi16<T>(w[q]) + hi16<T>(rv[q]));
                 }
                 const unsigned oo = ok ? (unsigned)(m * p.ldo * 2) + (unsigned)(co0 + 8 * qr) * 2u : RW_OOB;
                 const unsigned od = RW_DBG(8) ? RW_OOB : oo;
@@ -425,7 +372,7 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
                 x1 = silu_act ? silu<T>(x1) : x1;
                 x2 = silu_act ? silu<T>(x2) : x2;
                 x3 = silu_act ? silu<T>(x3) : x3;
-                unsigned w[2] = {rw_pack2<T>(x0, x1), rw_pack2<T>(x2, x3)};
+                unsigned w[2] = {pack2<T>(x0, x1), pack2<T>(x2, x3)};
                 const int px = (pg * MB + j) * 32 + pp;
                 const int oy = ty0 + px / TW, ox = tx0 + px % TW;
                 const bool ok = oy < p.Ho && ox < p.Wo;
@@ -437,7 +384,7 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
                     const unsigned rv[2] = {rr.x, rr.y};
 #pragma unroll
                     for (int q = 0; q < 2; ++q)
-                        w[q] = rw_pack2<T>(rw_lo<T>(w[q]) + rw_lo<T>(rv[q]), rw_hi<T>(w[q]) + rw_hi<T>(rv[q]));
+                        w[q] = pack2<T>(lo16<T>(w[q]) + lo16<T>(rv[q]), hi16<T>(w[q]) + hi16<T>(rv[q]));
                 }
                 const unsigned oo = ok ? (unsigned)(m * p.ldo * 2) + (unsigned)(co0 + 4 * c4) * 2u : RW_OOB;
                 const unsigned od = RW_DBG(8) ? RW_OOB : oo;
@@ -459,8 +406,8 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
     for (int it = 0; it < n_it; ++it) {
         if (it > 0) {
             const unsigned long long tw0 = (RW_TRACE && RW_DBG(64)) ? __builtin_amdgcn_s_memrealtime() : 0ull;
-            rw_vmwait<CNT0>();
-            rw_barrier();   // tile it complete in its slot; slot (it - 1) % NS read by every wave
+            vm_wait<CNT0>();
+            lds_barrier_sched();   // tile it complete in its slot; slot (it - 1) % NS read by every wave
             if (RW_TRACE && RW_DBG(64)) t_wait += __builtin_amdgcn_s_memrealtime() - tw0;
             if (RW_TRACE && it == 1) t_first = __builtin_amdgcn_s_memrealtime();
         }
@@ -496,7 +443,7 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
                 if (s + PF < NKS) load(s + PF, (s + PF) % RING);
                 if (RW_DBG(4)) continue;
 #pragma unroll
-                for (int j = 0; j < MB; ++j) acc[j] = RwMfma<T>::step(wf[s], bf[s % RING][j], acc[j]);
+                for (int j = 0; j < MB; ++j) acc[j] = Mfma32<T>::step(wf[s], bf[s % RING][j], acc[j]);
                 if (s + PF < NKS) __builtin_amdgcn_sched_group_barrier(0x100, MB, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, MB, 0);
             }
@@ -506,7 +453,7 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
         // ---- K chunks: every chunk wave's partial tile to LDS (lane (r32, h) holds couts
         //      16 h .. 16 h + 15 of pixel r32: 4 swizzled 16-B chunks), then the shared epilogue
         if constexpr (NKC > 1) {
-            if constexpr (DEFER) rw_barrier();   // every wave's epilogue reads of tile it - 1 are done
+            if constexpr (DEFER) lds_barrier_sched();   // every wave's epilogue reads of tile it - 1 are done
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
                 float* t = red_tile(kc, j) + r32 * 32;
@@ -516,7 +463,7 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
                         make_float4(acc[j][4 * q], acc[j][4 * q + 1], acc[j][4 * q + 2], acc[j][4 * q + 3]);
             }
             if constexpr (!DEFER) {
-                rw_barrier();
+                lds_barrier_sched();
                 epilogue_split(it);
             }
         } else {
@@ -524,7 +471,7 @@ __global__ __launch_bounds__(64 * NCG * NKC * NPG, (NCG * NKC * NPG >= 8 || NCG 
         }
     }
     if constexpr (DEFER) {
-        rw_barrier();   // the last tile's partials
+        lds_barrier_sched();   // the last tile's partials
         epilogue_split(n_it - 1);
     }
     if (RW_TRACE && threadIdx.x == 0) {

@@ -16,28 +16,11 @@
 // accumulator, + bias, activation, one rounding). The first pointwise output is zeroed
 // outside the image: it is the second depthwise conv's zero padding.
 #include "common.h"
-#include "dtypes.h"
+#include "mfma32.h"
 
 namespace yh {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <typename T> struct HMfma;
-template <> struct HMfma<__bf16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                       0, 0);
-    }
-};
-template <> struct HMfma<_Float16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                      0);
-    }
-};
 
 constexpr int NWV = HEAD_CLS_THREADS / 64;
 constexpr bool HC_UNITS = NWV >= 8;
@@ -46,21 +29,6 @@ constexpr bool HC_UNITS = NWV >= 8;
 __device__ __forceinline__ float hx_exp(float x) { return __expf(x); }
 __device__ __forceinline__ float hx_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
-// LDS-DMA: the wave's 64 lanes each copy 16 B from their own global address into LDS at
-// lds_addr + 16 * lane (M0 holds the wave-uniform base; restored after the copy)
-__device__ __forceinline__ void hc_glds(const void* src, unsigned lds_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds_addr) : "memory");
-#else
-    (void)src; (void)lds_addr;
-#endif
-}
-
-// Workgroup barrier for LDS hand-offs only: __syncthreads() also waits for every global
-// load in flight (vmcnt(0)), which would drain the weight loads issued ahead of a phase.
-__device__ __forceinline__ void hc_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 #ifdef YH_HC_TRACE
 // experiments only (-DYH_HC_TRACE builds; the shipped library has none of this): per-workgroup
 // phase stamps, read back by yh_debug_hc_trace. Slots: 0 / 8 s_memrealtime at entry / exit,
@@ -70,7 +38,7 @@ constexpr int HC_TR = 10, HC_TR_WG = 8192;
 __device__ unsigned long long hc_trace_buf[HC_TR_WG * HC_TR];
 #define HC_STAMP(k, rt)                                                                                      \
     do {                                                                                                     \
-        hc_barrier();                                                                                        \
+        lds_barrier();                                                                                       \
         if (threadIdx.x == 0 && blockIdx.x < HC_TR_WG)                                                       \
             hc_trace_buf[(size_t)blockIdx.x * HC_TR + (k)] =                                                 \
                 (rt) ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();                     \
@@ -139,7 +107,7 @@ __device__ __forceinline__ void hc_dw(const T* src, int SW, int ss, T* dst, int 
         bb = *reinterpret_cast<const float4*>(b + c0);
         wg = g;
     };
-    hc_barrier();   // src (and the parameters in LDS) complete
+    lds_barrier();   // src (and the parameters in LDS) complete
     // channel group fastest: the lanes of a wave read consecutive 8-B groups of one or two pixels
     // (with the column fastest, lanes 16 apart hit one bank at the 144-B pixel stride: 37 % of
     // head_cls's LDS cycles were bank conflicts, profiles/r06_sq_all_ops_c2.txt)
@@ -222,7 +190,7 @@ __device__ __forceinline__ void hc_pw_run(const T* src, int ss, int NPX, const T
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l32 = lane & 31, h = lane >> 5;
     const int na = (M + 31) >> 5, nb = (NPX + 31) >> 5;
-    hc_barrier();   // src complete
+    lds_barrier();   // src complete
     for (int bi = wv; bi < nb; bi += NWV) {
         const int px = bi * 32 + l32;
         const int pxc = px < NPX ? px : NPX - 1;
@@ -245,10 +213,10 @@ __device__ __forceinline__ void hc_pw_run(const T* src, int ss, int NPX, const T
             for (int e = 0; e < 16; ++e) acc[e] = 0.f;
             if (a < NAP) {
 #pragma unroll
-                for (int kb = 0; kb < NK; ++kb) acc = HMfma<T>::step(A.f[a < NAP ? a : 0][kb], bf[kb], acc);
+                for (int kb = 0; kb < NK; ++kb) acc = Mfma32<T>::step(A.f[a < NAP ? a : 0][kb], bf[kb], acc);
             } else {
 #pragma unroll
-                for (int kb = 0; kb < NK; ++kb) acc = HMfma<T>::step(lf[a & 1][kb], bf[kb], acc);
+                for (int kb = 0; kb < NK; ++kb) acc = Mfma32<T>::step(lf[a & 1][kb], bf[kb], acc);
             }
             if (px < NPX) {
                 // register i of lane (l32, h): cout a*32 + (i & 3) + 8 (i >> 2) + 4 h, pixel px
@@ -304,7 +272,7 @@ __device__ __forceinline__ void hc_pw_units(const T* src, int ss, int NPX, const
     };
     int a_cur = u0 < u1 ? hc_q(u0, dnb) : 0;
     if (u0 < u1) load_a(a_cur, 0, 0);
-    hc_barrier();   // src complete
+    lds_barrier();   // src complete
     for (int u = u0; u < u1; ++u) {
         const int a = hc_q(u, dnb), bi = u - a * nb;
         const int px = bi * 32 + l32;
@@ -323,7 +291,7 @@ __device__ __forceinline__ void hc_pw_units(const T* src, int ss, int NPX, const
                 load_b(brow, hh + 1, (hh + 1) & 1);
             }
 #pragma unroll
-            for (int kb = 0; kb < KP; ++kb) acc = HMfma<T>::step(af[hh & 1][kb], bf[hh & 1][kb], acc);
+            for (int kb = 0; kb < KP; ++kb) acc = Mfma32<T>::step(af[hh & 1][kb], bf[hh & 1][kb], acc);
         }
         if (px < NPX) {
 #pragma unroll
@@ -384,7 +352,7 @@ __device__ __forceinline__ void hc_body(const HeadClsArgs& A, int li, char* hsm)
                              : q < e4 ? V.pw1b + 4 * (q - e3)
                              : q < e5 ? V.pw2b + 4 * (q - e4)
                              : q < e6 ? V.pw3b + 4 * (q - e5) : reinterpret_cast<const float*>(A.zero);
-            hc_glds(src, lds0 + (unsigned)L.prm + (unsigned)i0 * 16);
+            glds16(src, lds0 + (unsigned)L.prm + (unsigned)i0 * 16);
         }
     }
 #ifdef YH_HC_TRACE
@@ -421,18 +389,18 @@ __device__ __forceinline__ void hc_body(const HeadClsArgs& A, int li, char* hsm)
             const int gh = h0 - 2 + r, gw = w0 - 2 + cc;
             const bool ok = q < xtotal && c < cpp && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W;
             const void* src = ok ? (const void*)(x + (((long long)n * H + gh) * W + gw) * V.ldx + cl + c * 8) : A.zero;
-            hc_glds(src, lds0 + base + (unsigned)i0 * 16);
+            glds16(src, lds0 + base + (unsigned)i0 * 16);
         }
     };
     issue_x(0, 0);
     for (int cl = 0, k = 0; cl < C0; cl += ck, ++k) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMAs (and earlier loads) landed
+        vm_wait<0>();   // this wave's DMAs (and earlier loads) landed
         if (cl == 0) HC_STAMP(2, false);
         const unsigned cur = (k & 1) ? (unsigned)L.x2 : 0u;
         // the other buffer's last reader (chunk k - 1's depthwise conv) ended at the barrier below
         if (cl + ck < C0) issue_x(cl + ck, (k & 1) ? 0u : (unsigned)L.x2);
         hc_dw<T>(reinterpret_cast<const T*>(hsm + cur), XW, L.SX, R2, MH, MW, L.SD, cl, ck, PW1, C0, PB1);
-        if (cl + ck < C0) hc_barrier();   // chunk k's buffer is re-filled with chunk k + 2
+        if (cl + ck < C0) lds_barrier();   // chunk k's buffer is re-filled with chunk k + 2
     }
     HC_STAMP(3, false);
     // 3. pw1: D1 (R2) -> P1 (R1), zero outside the image (dw2's zero padding)
@@ -571,7 +539,7 @@ __device__ __forceinline__ void bd_body(const BoxDflArgs& A, int li) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
-            for (int kb = 0; kb < NK; ++kb) acc = HMfma<T>::step(af[a][kb], bf[t][kb], acc);
+            for (int kb = 0; kb < NK; ++kb) acc = Mfma32<T>::step(af[a][kb], bf[t][kb], acc);
             // register i: cout 32h + 16a + i = bin i of side 2h + a; the conv's rounding first
             float v[16];
 #pragma unroll

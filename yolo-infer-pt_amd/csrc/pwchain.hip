@@ -17,50 +17,20 @@
 // Bit-identical to the per-layer conv_mx launches: each stage walks K as one 32x32x16 MFMA step
 // per 16-channel block in ascending order (conv_mx.h), from a zero fp32 accumulator.
 #include "common.h"
-#include "dtypes.h"
+#include "mfma32.h"
 
 namespace yh {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <typename T> struct PMfma;
-template <> struct PMfma<__bf16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                       0, 0);
-    }
-};
-template <> struct PMfma<_Float16> {
-    static __device__ __forceinline__ f32x16 step(const uint4& a, const uint4& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                      0);
-    }
-};
-
 constexpr int PNW = PWC_THREADS / 64;
 
-__device__ __forceinline__ void pc_glds(const void* src, unsigned lds_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds_addr) : "memory");
-#else
-    (void)src; (void)lds_addr;
-#endif
-}
-__device__ __forceinline__ void pc_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-typedef __attribute__((address_space(3))) const uint4* pc_lp4;
 typedef __attribute__((address_space(3))) const uint2* pc_lp2;
 typedef __attribute__((address_space(3))) uint2* pc_sp2;
 #if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ uint4 pc_rd(unsigned addr) { return *reinterpret_cast<pc_lp4>((size_t)addr); }
 __device__ __forceinline__ uint2 pc_rd2(unsigned addr) { return *reinterpret_cast<pc_lp2>((size_t)addr); }
 __device__ __forceinline__ void pc_wr2(unsigned addr, uint2 v) { *reinterpret_cast<pc_sp2>((size_t)addr) = v; }
 #else
-__device__ __forceinline__ uint4 pc_rd(unsigned) { return uint4{}; }
 __device__ __forceinline__ uint2 pc_rd2(unsigned) { return uint2{}; }
 __device__ __forceinline__ void pc_wr2(unsigned, uint2) {}
 #endif
@@ -152,7 +122,7 @@ __global__ __launch_bounds__(PWC_THREADS) void pw_chain(const PwChainArgs A) {
             const bool ok = q < total && c < L.nchunk && px < np;
             const void* src = ok ? (const void*)(reinterpret_cast<const char*>(L.g) + ((m0 + px) * L.ldg + c * 8) * 2)
                                  : A.zero;
-            pc_glds(src, lds0 + (unsigned)L.lds + (unsigned)i0 * 16);
+            glds16(src, lds0 + (unsigned)L.lds + (unsigned)i0 * 16);
         }
     }
     PWC_STAMP(25, false);
@@ -166,14 +136,14 @@ __global__ __launch_bounds__(PWC_THREADS) void pw_chain(const PwChainArgs A) {
         for (int s = 0; s < A.nst; ++s) {
             const int nq = (A.st[s].N * A.st[s].wld * 2) >> 10;   // whole KB (rows are 128-B multiples)
             const char* w = reinterpret_cast<const char*>(A.st[s].w);
-            for (int q = (gi + G - q0 % G) % G + wv * G; q < nq; q += PNW * G) pc_glds(w + ((size_t)q << 10) + lane * 16, sink);
+            for (int q = (gi + G - q0 % G) % G + wv * G; q < nq; q += PNW * G) glds16(w + ((size_t)q << 10) + lane * 16, sink);
             q0 += nq;
         }
     }
     PWC_STAMP(26, false);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     PWC_STAMP(27, false);
-    pc_barrier();
+    lds_barrier();
     PWC_STAMP(1, false);
     if (ps < A.nst) load_a(ps, pu, ppc, ring[1]);
 
@@ -227,20 +197,20 @@ __global__ __launch_bounds__(PWC_THREADS) void pw_chain(const PwChainArgs A) {
                     uint4 x0[8], x1[8];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        x0[i] = pc_rd(b0 + i * 32);
-                        x1[i] = pc_rd(b1 + i * 32);
+                        x0[i] = lds_rd16(b0 + i * 32);
+                        x1[i] = lds_rd16(b1 + i * 32);
                     }
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        acc0 = PMfma<T>::step(f[i], x0[i], acc0);
-                        acc1 = PMfma<T>::step(f[i], x1[i], acc1);
+                        acc0 = Mfma32<T>::step(f[i], x0[i], acc0);
+                        acc1 = Mfma32<T>::step(f[i], x1[i], acc1);
                     }
                 } else {
                     uint4 x0[8];
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) x0[i] = pc_rd(b0 + i * 32);
+                    for (int i = 0; i < 8; ++i) x0[i] = lds_rd16(b0 + i * 32);
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) acc0 = PMfma<T>::step(f[i], x0[i], acc0);
+                    for (int i = 0; i < 8; ++i) acc0 = Mfma32<T>::step(f[i], x0[i], acc0);
                 }
             }
             // register i of lane (l32, h): cout a * 32 + (i & 3) + 8 (i >> 2) + 4 h, pixel j * 32 + l32
@@ -283,7 +253,7 @@ __global__ __launch_bounds__(PWC_THREADS) void pw_chain(const PwChainArgs A) {
             if (u == wv) PWC_STAMP(2 + 5 * s + 2, false);
         }
         PWC_STAMP(2 + 5 * s + 3, false);   // wave 0's units done
-        pc_barrier();   // this stage's LDS outputs are complete for the next stage
+        lds_barrier();   // this stage's LDS outputs are complete for the next stage
         PWC_STAMP(2 + 5 * s + 4, false);
     }
     PWC_STAMP(31, true);
