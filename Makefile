@@ -16,7 +16,7 @@ NET := engine net_build net_weights net_forward net_launch net_debug
 # handle-free host code compiled as HIP
 HOSTHIP := post_abi nms_host
 # kernels; the NOFMA ones promise bit-exact arithmetic against host code: no FMA contraction
-KERNELS := conv misc conv_mx conv_rw head c3k2 c3k pwchain cls
+KERNELS := conv sppf attn decode conv_mx conv_rw head c3k2 c3k pwchain cls
 KERNELS_NOFMA := preprocess nms match merge track
 # HIP-free translation units: plain C++, no device pass, no FMA contraction
 HOSTCXX := match_host merge_host track_host
@@ -47,6 +47,8 @@ $(call objs,$(HOSTCXX)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/%.h $(SRC)/box_math.
 	$(HIPCC) -x c++ -O3 -fPIC -std=c++17 -Iinclude -I$(SRC) -ffp-contract=off -c $< -o $@
 
 # headers only some units of a group include
+# the decode's value arithmetic, shared by its kernels and the fused head's
+$(call objs,decode head): $(SRC)/head_math.h
 # each shares its arithmetic with its host twin through box_math.h and the twin's header
 $(call objs,match merge track): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
 # reports its argument errors through host_util.h's guarded(); its host functions use the pool

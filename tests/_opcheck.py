@@ -253,7 +253,7 @@ def attention_op(ins, d, params, dtype, heads):
     """OP_ATTN (Attention nets/nn.py:97-123 up to the projection): per head
     o = V softmax(Q^T K * dk^-0.5)^T, rounded, + pe(v) (the positional DWConv 3x3, BN folded),
     rounded. The device keeps scores and softmax sums in fp32, rounds each softmax weight to
-    the dtype before the P.V MFMA (misc.hip psa_attention_*), and rescales online per block of
+    the dtype before the P.V MFMA (attn.hip psa_attention_*), and rescales online per block of
     16 keys; its departure from the exact o is bounded by
         (u16 + 2 eps + (4T + 8) u) (sum_j p_j |v_j| / D + |o|) + ds_max sum_j p_j |v_j - o| / D
     (+ T 2^-25 max|v| / D for fp16 subnormal weights), eps = (max_j |s_j - m| + 8) u the exp

@@ -153,7 +153,7 @@ def test_head_cls_wide_level_equals_per_layer_launches(gpu, dtype, batch, h, w):
 @pytest.mark.parametrize("variant,dtype,batch,size", [("n", torch.bfloat16, 4, 640), ("s", torch.float16, 2, 320),
                                                       ("x", torch.bfloat16, 1, 1280), ("n", torch.float16, 2, 224)])
 def test_attention_lds_kernel_equals_per_wave_kernel(gpu, variant, dtype, batch, size):
-    """misc.hip psa_attention_lds (K / V staged in LDS once per workgroup, chunks of 256 keys)
+    """attn.hip psa_attention_lds (K / V staged in LDS once per workgroup, chunks of 256 keys)
     runs psa_attention_mfma's per-16-key-block arithmetic in the same order: bit-identical, also
     over several chunks (x at 1280: 1600 tokens) and with a partial last block (224: 49 tokens).
     YH_ATTN_LDS, like every switch, is read at handle creation: each engine keeps its own kernel."""
@@ -172,7 +172,7 @@ def test_attention_lds_kernel_equals_per_wave_kernel(gpu, variant, dtype, batch,
 @pytest.mark.parametrize("variant,dtype,batch,size", [("n", torch.bfloat16, 4, 640), ("s", torch.float16, 2, 320),
                                                       ("n", torch.float16, 2, 224), ("m", torch.bfloat16, 2, 480)])
 def test_attention_full_kernel_equals_chunked_kernel_and_pe_add(gpu, variant, dtype, batch, size):
-    """misc.hip psa_attention_full (one workgroup per (image, head), the whole K / V in LDS, the
+    """attn.hip psa_attention_full (one workgroup per (image, head), the whole K / V in LDS, the
     positional term added in the epilogue) is bit-identical to the chunked kernel followed by
     pe_add (YH_ATTN_FULL=0), including partial key blocks (224: 49 tokens) and several heads
     (m: 4 heads at 480 -> 225 tokens). Both workgroup shapes of the full kernel: these small
@@ -193,7 +193,7 @@ def test_attention_full_kernel_equals_chunked_kernel_and_pe_add(gpu, variant, dt
 @pytest.mark.parametrize("variant,dtype,batch,size", [("n", torch.bfloat16, 4, 640), ("s", torch.float16, 2, 320),
                                                       ("x", torch.bfloat16, 1, 1280), ("n", torch.float16, 2, 224)])
 def test_sppf_kernel_equals_three_maxpools(gpu, variant, dtype, batch, size):
-    """misc.hip sppf_fused (CPW 8-channel chunks of one image per workgroup: 1 or 2 by default,
+    """sppf.hip sppf_fused (CPW 8-channel chunks of one image per workgroup: 1 or 2 by default,
     halved until the planes fit the LDS) with the default and 1, 2, 4 and 8 chunks (YH_SPPF_CPW;
     8 fits at 20x20, 40x40 falls back to 2) is bit-identical to three maxpool5 launches
     (YH_SPPF_FUSED=0).

@@ -12,8 +12,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [("n", "bf16", 4, 640), ("s", "fp16", 2, 320), ("n", "fp16", 2, 224), ("m", "bf16", 2, 480),
-         ("n", "fp32", 2, 224), ("x", "bf16", 1, 256)]
-SETTINGS = [{}, {"YH_FUSE": "0"}, {"YH_C3K": "0"}, {"YH_PWCHAIN": "0"}, {"YH_CSP_TAIL": "1"}]
+         ("n", "fp32", 2, 224), ("x", "bf16", 1, 256),
+         ("n", "fp32", 1, 256)]   # 1344 anchors, a multiple of 8: head_decode<float, true> (224: 1029, ROWS = false)
+SETTINGS = [{}, {"YH_FUSE": "0"}, {"YH_C3K": "0"}, {"YH_PWCHAIN": "0"}, {"YH_CSP_TAIL": "1"},
+            # the attention kernels one by one (chunked, per wave, 16-wave full), the three max-pools
+            {"YH_ATTN_FULL": "0"}, {"YH_ATTN_FULL": "0", "YH_ATTN_LDS": "0"},
+            {"YH_ATTN_FULL": "1", "YH_ATTN_NW": "16", "YH_ATTN_QS": "1"}, {"YH_SPPF_FUSED": "0"}]
 DTYPES = {"bf16": "bfloat16", "fp16": "float16", "fp32": "float32"}
 
 

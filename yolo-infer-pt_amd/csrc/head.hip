@@ -16,6 +16,7 @@
 // accumulator, + bias, activation, one rounding). The first pointwise output is zeroed
 // outside the image: it is the second depthwise conv's zero padding.
 #include "common.h"
+#include "head_math.h"
 #include "mfma32.h"
 
 namespace yh {
@@ -24,10 +25,6 @@ namespace {
 
 constexpr int NWV = HEAD_CLS_THREADS / 64;
 constexpr bool HC_UNITS = NWV >= 8;
-
-// the decode's 16-bit exp and division (misc.hip ex<T> / dv<T>): same instructions, same bits
-__device__ __forceinline__ float hx_exp(float x) { return __expf(x); }
-__device__ __forceinline__ float hx_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
 #ifdef YH_HC_TRACE
 // experiments only (-DYH_HC_TRACE builds; the shipped library has none of this): per-workgroup
@@ -452,7 +449,7 @@ __device__ __forceinline__ void hc_body(const HeadClsArgs& A, int li, char* hsm)
                 const gptr<T> col = yio + ((long long)n * (4 + A.nc) + 4 + co) * A.A + V.aoff + gh * W + gw;
                 const T* o = reinterpret_cast<const T*>(&v);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) col[(long long)e * A.A] = fromf<T>(hx_div(1.0f, 1.0f + hx_exp(-tof(o[e]))));
+                for (int e = 0; e < 4; ++e) col[(long long)e * A.A] = fromf<T>(sigmoid<T>(tof(o[e])));
             }
         });
     else
@@ -544,29 +541,21 @@ __device__ __forceinline__ void bd_body(const BoxDflArgs& A, int li) {
             float v[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = tof(fromf<T>(acc[i] + bs[a][i]));
-            float mx = v[0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) mx = fmaxf(mx, v[i]);
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { v[i] = hx_exp(v[i] - mx); sum += v[i]; }
-            float d = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) d = fmaf((float)i, hx_div(v[i], sum), d);
-            dist[a] = d;
+            dist[a] = dfl16<T>(v);
         }
+        // the other half's two sides complete (left, top, right, bottom)
         const float o0 = xor32_swap(dist[0]), o1 = xor32_swap(dist[1]);
-        const float dl = h ? o0 : dist[0], dt = h ? o1 : dist[1];
-        const float dr = h ? dist[0] : o0, db = h ? dist[1] : o1;
+        const float d[4] = {h ? o0 : dist[0], h ? o1 : dist[1], h ? dist[0] : o0, h ? dist[1] : o1};
         const long long m = tt * 32 + l32;
         if (m < M) {
             const int n = (int)(m / HW), loc = (int)(m - (long long)n * HW);
             const int gy = loc / V.W, gx = loc - gy * V.W;
-            const float ax = (float)gx + 0.5f, ay = (float)gy + 0.5f, st = V.stride;
-            const float x1 = ax - dl, y1 = ay - dt;
-            const float x2 = ax + dr, y2 = ay + db;
-            const float r0 = h ? (x2 - x1) * st : (x1 + x2) / 2.0f * st;
-            const float r1 = h ? (y2 - y1) * st : (y1 + y2) / 2.0f * st;
+            const float st = V.stride;
+            float e[4];
+            box_edges(gx, gy, d, e);
+            // half 0 writes (cx, cy), half 1 (w, h)
+            const float r0 = h ? box_extent(e[0], e[2], st) : box_centre(e[0], e[2], st);
+            const float r1 = h ? box_extent(e[1], e[3], st) : box_centre(e[1], e[3], st);
             const gptr<T> col = yb + ((long long)n * (4 + A.nc) + 2 * h) * A.A + V.aoff + loc;
             col[0] = fromf<T>(r0);
             col[A.A] = fromf<T>(r1);
