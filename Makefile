@@ -17,7 +17,7 @@ NET := engine net_build net_weights net_forward net_launch net_debug
 HOSTHIP := post_abi nms_host
 # kernels; the NOFMA ones promise bit-exact arithmetic against host code: no FMA contraction
 KERNELS := conv sppf attn decode conv_mx conv_rw head c3k2 c3k pwchain cls
-KERNELS_NOFMA := preprocess nms match merge track
+KERNELS_NOFMA := preprocess nms match merge track reid
 # HIP-free translation units: plain C++, no device pass, no FMA contraction
 HOSTCXX := match_host merge_host track_host
 
@@ -51,6 +51,8 @@ $(call objs,$(HOSTCXX)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/%.h $(SRC)/box_math.
 $(call objs,decode head): $(SRC)/head_math.h
 # each shares its arithmetic with its host twin through box_math.h and the twin's header
 $(call objs,match merge track): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
+# the appearance kernels share the tracker's header: the twins live in track_host.cpp
+$(OBJDIR)/reid.o: $(SRC)/track_host.h $(SRC)/box_math.h
 # reports its argument errors through host_util.h's guarded(); its host functions use the pool
 $(OBJDIR)/preprocess.o: $(SRC)/host_util.h $(SRC)/host_parallel.h
 

@@ -37,6 +37,12 @@
  *                       nets/nn.py YOLOCls - Ultralytics' YOLO11-cls: DarkNet without the SPPF, C2PSA,
  *                       then Classify (1x1 conv to 1280 + BN + SiLU, global average pool, linear, softmax)
  *   yh_classify         YOLOCls.forward / YOLOCls.features in eval mode on a batch of crops
+ *   yh_embed_quantize,
+ *   yh_embed_similarity no reference counterpart: unit int8 features and their exact int32 cosine
+ *                       matrix on the int8 MFMA, for gallery search and for the tracker
+ *   yh_track_reid       no reference counterpart: yh_track with an appearance term in the first
+ *                       association and a per-slot int8 feature gallery in the state
+ *   yh_embed_quantize_host, yh_embed_similarity_host, yh_track_reid_host   the same in host memory
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -364,6 +370,111 @@ int yh_track(const float* dets, const int* counts, int batch, int max_det, const
 int yh_track_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
                   void* state, int streams, int max_tracks, const yh_track_params* p, int max_out,
                   float* out, int* ids, int* det_index, int* out_counts, int threads);
+
+/* Appearance features for re-identification (no reference counterpart: the rules below are the
+ * specification; tests/_reid_cases.py restates them in numpy). A feature is any (rows, dim) f32
+ * embedding - yh_classify's, or a trained re-ID head's; dim % 64 == 0 and 64 <= dim <=
+ * YH_REID_MAX_DIM. Every sum below is an integer sum, so no order needs fixing and the device
+ * and the host compute the same bytes.
+ *
+ * yh_embed_quantize: e (rows, dim) f32 -> q (rows, dim) int8, the unit vector of each row scaled
+ * to length 127. Per row, in fp64 with one rounding per operation and no FMA:
+ *   1. m = max |e_i|. If m == 0 or any element is not finite, q = 0 ("no feature").
+ *   2. p_i = (int)rint((double)e_i * (16384.0 / (double)m)).
+ *   3. S = sum p_i^2 (int64).
+ *   4. q_i = (int)rint((double)p_i * (127.0 / sqrt((double)S))).
+ * count: NULL, or (1) int32 (device memory for yh_embed_quantize): rows at or beyond
+ * min(max(*count, 0), rows) are written as zero and their e is never read. Every byte of q is
+ * written.
+ *
+ * yh_embed_similarity: out[b] = A[b] . B[b]^T in exact int32, for a batch.
+ *   a:       int8 blocks of (ra, dim), row-major, block k at a + k * a_block_stride bytes, nblocks
+ *            of them
+ *   a_index: NULL, or (batch) int32: batch row b reads block a_index[b] (NULL: block b). An index
+ *            outside [0, nblocks) gives a zero block and touches nothing else (stream_ids' rule)
+ *   b:       (batch, rb, dim) int8
+ *   out:     (batch, ra, rb) int32; every element is written
+ * Any int8 value is legal, -128 included. The device kernel is the gfx950 int8 MFMA
+ * (v_mfma_i32_32x32x32_i8); it loads 16 bytes at a time, so on the device a, b and
+ * a_block_stride must be multiples of 16 bytes.
+ *
+ * Both are asynchronous on `stream`, allocate nothing and never synchronise; the *_host twins
+ * split the rows over `threads` (<= 0: every hardware thread) and are synchronous.
+ * YH_EINVAL (message in yh_last_error()), nothing launched: a bad dim, a negative size, a NULL
+ * required pointer (none is required when there is nothing to write), a_block_stride smaller
+ * than ra * dim, a misaligned device operand. */
+#define YH_REID_MAX_DIM 2048
+int yh_embed_quantize(const float* e, int rows, int dim, const int* count, int8_t* q, void* stream);
+int yh_embed_quantize_host(const float* e, int rows, int dim, const int* count, int8_t* q, int threads);
+int yh_embed_similarity(const int8_t* a, size_t a_block_stride, int nblocks, const int* a_index, const int8_t* b,
+                        int batch, int ra, int rb, int dim, int32_t* out, void* stream);
+int yh_embed_similarity_host(const int8_t* a, size_t a_block_stride, int nblocks, const int* a_index, const int8_t* b,
+                             int batch, int ra, int rb, int dim, int32_t* out, int threads);
+
+/* yh_track with an appearance term in its first association (no reference counterpart; BoT-SORT's
+ * and DeepSORT's idea under this tracker's greedy walk). Arguments, rules, outputs and errors are
+ * yh_track's, plus:
+ *
+ *   embed:        (capacity, dim) f32 features, or NULL (no row has a feature)
+ *   feat_counts:  (batch) int32 or NULL (NULL: the clamped counts)
+ *   embed_total:  (1) int32 or NULL; ignored when embed is NULL
+ *   rp:           cos_min, iou_min (BoT-SORT: 0.5 / 0.5; iou_min = 0 re-identifies anywhere in
+ *                 the frame)
+ *   workspace:    caller-owned, yh_track_reid_workspace_bytes(batch, max_det, max_tracks, dim)
+ *                 bytes, 16-byte aligned on the device; its contents mean nothing between calls
+ *
+ * Features of rows. With c_b = min(max(counts[b], 0), max_det), row r of batch row b has a feature
+ * iff r < n_b = min(max(feat_counts[b], 0), c_b), and its slot s = n_0 + ... + n_(b-1) + r is
+ * below capacity and, when embed_total is given, below *embed_total. This is yh_crop_rois'
+ * compaction: crops cut with counts = feat_counts, yh_classify's embedding of them and the crops'
+ * total plug in as they lie. (The sum runs over all batch rows, whatever their stream_ids.) The
+ * row's quantised feature q is yh_embed_quantize's of embed[s]; every other row has q = 0.
+ *
+ * State: yh_track_reid_state_bytes(streams, max_tracks, dim) bytes; per stream the words of
+ * yh_track's state, unchanged, then a gallery (max_tracks, dim) int8, one row g_t per slot.
+ * All-zero is the empty state and a zero gallery row means "no feature". No pointers, the same
+ * layout on host and device. The yh_track part evolves exactly as yh_track's would under the
+ * same matches.
+ *
+ * Association 1 (status 2 or 3 against the high rows). For slot t and row d: dot = g_t . q_d
+ * (int32); cosv = (float)dot / 16129.0f; app = 0.5f + 0.5f * cosv (fp32, one rounding per
+ * operation, no FMA); inter and iou as in step 3, iou counting as 0 when inter == 0. The pair is
+ * eligible iff g_t and q_d are both non-zero, cosv >= cos_min and iou >= iou_min. It is a
+ * candidate iff the class rule holds and (inter != 0 and iou >= iou_first, or it is eligible).
+ * Its sort value is the larger of iou and app when eligible, else iou. The walk is step 3's: value
+ * descending, then slot, then row; greedy, both sides unmatched. Associations 2 and 3, predict,
+ * update, births and output are yh_track's.
+ *
+ * Gallery update, after step 5: a slot matched in this frame (any association) or born in it,
+ * whose row has a feature, takes g = q if g was zero or the slot was born; else, with t_i =
+ * 7 g_i + q_i and S = sum t_i^2 (int64), g_i = (int)rint((double)t_i * (127.0 / sqrt((double)S)))
+ * (all zero if S == 0). A birth whose row has no feature zeroes its gallery row. Nothing else
+ * writes a gallery row; a freed slot keeps its bytes.
+ *
+ * With embed NULL, or no row having a feature, out, ids, det_index, out_counts and the yh_track
+ * part of the state are byte for byte yh_track's.
+ *
+ * yh_track_reid launches on `stream`: the quantisation into the workspace, yh_embed_similarity's
+ * kernel of the galleries (read where they lie in the state, through stream_ids) against it, the
+ * track kernel, which reads the similarities, and the gallery update behind it. Asynchronous,
+ * allocates nothing, never synchronises, no atomics. yh_track_reid_host: the same bytes.
+ * YH_EINVAL as yh_track, and: a bad dim, cos_min or iou_min not finite, a NULL rp or workspace,
+ * a workspace smaller than required, a negative capacity. */
+typedef struct {
+    float cos_min, iou_min;
+} yh_reid_params;
+size_t yh_track_reid_state_bytes(int streams, int max_tracks, int dim);
+size_t yh_track_reid_workspace_bytes(int batch, int max_det, int max_tracks, int dim);
+int yh_track_reid(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+                  void* state, int streams, int max_tracks, const yh_track_params* p, int max_out,
+                  float* out, int* ids, int* det_index, int* out_counts, const float* embed, int capacity,
+                  int dim, const int* feat_counts, const int* embed_total, const yh_reid_params* rp,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int yh_track_reid_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+                       void* state, int streams, int max_tracks, const yh_track_params* p, int max_out,
+                       float* out, int* ids, int* det_index, int* out_counts, const float* embed, int capacity,
+                       int dim, const int* feat_counts, const int* embed_total, const yh_reid_params* rp,
+                       void* workspace, size_t workspace_bytes, int threads);
 
 /* Letterbox geometry of one image for a square canvas of `size` (dataset.py:95-103,
  * 292-313): resized height / width (int(h * r), int(w * r) with r = size / max(h, w);

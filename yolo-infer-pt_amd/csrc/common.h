@@ -52,6 +52,16 @@ inline int lds_optin(const void* kernel, int bytes) {
     return 0;
 }
 
+// the sum of a 64-bit integer over the 64 lanes of a wave, in every lane (reid.hip, track.hip)
+__device__ inline long long wave_sum(long long v) {
+    for (int m = 32; m > 0; m >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(unsigned long long)v, m);
+        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)((unsigned long long)v >> 32), m);
+        v += (long long)(((unsigned long long)hi << 32) | lo);
+    }
+    return v;
+}
+
 // ACT_SILU_F64: SiLU of (K sum + bias) evaluated in fp64 and rounded once to fp32; only the fp32
 // handle's classifier head conv (conv_gemm's EXACT instances), whose output is held to one ulp
 enum Act { ACT_ID = 0, ACT_SILU = 1, ACT_SILU_F64 = 2 };
@@ -424,5 +434,30 @@ int launch_merge(const float* dets, const int* counts, int tiles, int max_det, c
 int launch_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
                  int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
                  int* det_index, int* out_counts, hipStream_t s);
+// the same with the appearance term (yh_track_reid): the state carries the galleries, the
+// workspace the rows' features, their flags and the similarities (csrc/track_host.h's layout)
+struct TrackReid {
+    const int8_t* q;    // (batch, max_det, dim)
+    const int* flags;   // (batch, max_det)
+    const int* sim;     // (batch, max_tracks, max_det)
+    const int* sim_t;   // (batch, max_det, max_tracks): the same numbers, transposed
+    const int* gnz;     // (batch, max_tracks): the slot's gallery row is non-zero; NULL without features
+    int* code;          // (batch, max_tracks): the gallery's work, for launch_gallery_update
+    int dim;
+    float cos_min, iou_min;
+};
+int launch_track_reid(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                      int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
+                      int* det_index, int* out_counts, const TrackReid& rd, hipStream_t s);
+// reid.hip: yh_embed_quantize, the quantise-and-scatter of yh_track_reid, yh_embed_similarity
+int launch_embed_quantize(const float* e, int rows, int dim, const int* count, int8_t* q, hipStream_t s);
+int launch_embed_scatter(const float* embed, int capacity, int dim, const int* counts, const int* feat_counts,
+                         const int* embed_total, int batch, int max_det, int8_t* q, int* flags, hipStream_t s);
+int launch_embed_similarity(const int8_t* a, size_t a_block_stride, int nblocks, const int* a_index, const int8_t* b,
+                            int batch, int ra, int rb, int dim, int32_t* out, int* a_nonzero, int32_t* out_t,
+                            hipStream_t s);
+int launch_gallery_update(void* state, size_t stream_bytes, size_t gallery_offset, const int* stream_ids, int batch,
+                          int max_tracks, int max_det, int dim, const int8_t* q, const int* flags, const int* code,
+                          hipStream_t s);
 
 }  // namespace yh

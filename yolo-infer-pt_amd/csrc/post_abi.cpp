@@ -1,5 +1,6 @@
 // C ABI of the stages after the forward, none of which needs a handle: yh_nms (with its
-// workspace layout), yh_match, yh_merge, yh_track and their *_host twins.
+// workspace layout), yh_match, yh_merge, yh_track, yh_embed_quantize, yh_embed_similarity,
+// yh_track_reid and their *_host twins.
 #include <algorithm>
 
 #include "common.h"
@@ -163,6 +164,112 @@ int yh_track_host(const float* dets, const int* counts, int batch, int max_det, 
                                det_index, out_counts));
         yh_track_host_run(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
                           det_index, out_counts, threads);
+    });
+}
+
+int yh_embed_quantize(const float* e, int rows, int dim, const int* count, int8_t* q, void* stream) {
+    return guarded([&] {
+        checked(yh_embed_quantize_check(e, rows, dim, q));
+        const int rc = yh::launch_embed_quantize(e, rows, dim, count, q, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("embed_quantize launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_embed_quantize_host(const float* e, int rows, int dim, const int* count, int8_t* q, int threads) {
+    return guarded([&] {
+        checked(yh_embed_quantize_check(e, rows, dim, q));
+        yh_embed_quantize_host_run(e, rows, dim, count, q, threads);
+    });
+}
+
+int yh_embed_similarity(const int8_t* a, size_t a_block_stride, int nblocks, const int* a_index, const int8_t* b,
+                        int batch, int ra, int rb, int dim, int32_t* out, void* stream) {
+    return guarded([&] {
+        checked(yh_embed_similarity_check(a, a_block_stride, nblocks, b, batch, ra, rb, dim, out));
+        yh::require(((uintptr_t)a | (uintptr_t)b | a_block_stride) % 16 == 0,
+                    "a, b and a_block_stride must be multiples of 16 bytes on the device");
+        const int rc = yh::launch_embed_similarity(a, a_block_stride, nblocks, a_index, b, batch, ra, rb, dim, out,
+                                                   nullptr, nullptr, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("embed_similarity launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_embed_similarity_host(const int8_t* a, size_t a_block_stride, int nblocks, const int* a_index, const int8_t* b,
+                             int batch, int ra, int rb, int dim, int32_t* out, int threads) {
+    return guarded([&] {
+        checked(yh_embed_similarity_check(a, a_block_stride, nblocks, b, batch, ra, rb, dim, out));
+        yh_embed_similarity_host_run(a, a_block_stride, nblocks, a_index, b, batch, ra, rb, dim, out, threads);
+    });
+}
+
+size_t yh_track_reid_state_bytes(int streams, int max_tracks, int dim) {
+    if (streams < 0 || max_tracks < 1 || yh_reid_dim_check(dim)) return 0;
+    return (size_t)streams * yh_track_reid_stream_bytes(max_tracks, dim);
+}
+
+size_t yh_track_reid_workspace_bytes(int batch, int max_det, int max_tracks, int dim) {
+    if (batch < 0 || max_det < 0 || max_tracks < 1 || yh_reid_dim_check(dim)) return 0;
+    return yh_reid_ws_bytes(batch, max_det, max_tracks, dim);
+}
+
+int yh_track_reid(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                  int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
+                  int* det_index, int* out_counts, const float* embed, int capacity, int dim, const int* feat_counts,
+                  const int* embed_total, const yh_reid_params* rp, void* workspace, size_t workspace_bytes,
+                  void* stream) {
+    return guarded([&] {
+        checked(yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
+                               det_index, out_counts));
+        checked(yh_track_reid_check(batch, max_det, max_tracks, capacity, dim, rp, workspace, workspace_bytes));
+        yh::require(((uintptr_t)workspace | (uintptr_t)state) % 16 == 0,
+                    "state and workspace must be 16-byte aligned on the device");
+        if (batch == 0) return;
+        char* ws = static_cast<char*>(workspace);
+        yh::TrackReid rd{};
+        rd.q = reinterpret_cast<const int8_t*>(ws);
+        rd.flags = reinterpret_cast<const int*>(ws + yh_reid_ws_flags(batch, max_det, dim));
+        rd.sim = reinterpret_cast<const int*>(ws + yh_reid_ws_sim(batch, max_det, dim));
+        rd.sim_t = reinterpret_cast<const int*>(ws + yh_reid_ws_sim_t(batch, max_det, max_tracks, dim));
+        int* gnz = reinterpret_cast<int*>(ws + yh_reid_ws_gnz(batch, max_det, max_tracks, dim));
+        const bool features = embed && streams > 0 && max_det > 0;
+        rd.gnz = features ? gnz : nullptr;
+        rd.code = reinterpret_cast<int*>(ws + yh_reid_ws_code(batch, max_det, max_tracks, dim));
+        rd.dim = dim;
+        rd.cos_min = rp->cos_min;
+        rd.iou_min = rp->iou_min;
+        hipStream_t s = (hipStream_t)stream;
+        int rc = yh::launch_embed_scatter(embed, capacity, dim, counts, feat_counts, embed_total, batch, max_det,
+                                          const_cast<int8_t*>(rd.q), const_cast<int*>(rd.flags), s);
+        // the galleries are read where they lie: block stream_ids[b] of `streams`, behind the words
+        // of yh_track's state. Without features no pair reads a similarity.
+        const size_t gallery_offset = yh_track_stream_words(max_tracks) * 4;
+        const size_t stream_bytes = yh_track_reid_stream_bytes(max_tracks, dim);
+        if (rc == 0 && features)
+            rc = yh::launch_embed_similarity(static_cast<const int8_t*>(state) + gallery_offset, stream_bytes, streams,
+                                             stream_ids, rd.q, batch, max_tracks, max_det, dim,
+                                             const_cast<int*>(rd.sim), gnz, const_cast<int*>(rd.sim_t), s);
+        if (rc == 0)
+            rc = yh::launch_track_reid(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, *p, max_out,
+                                       out, ids, det_index, out_counts, rd, s);
+        if (rc == 0)
+            rc = yh::launch_gallery_update(state, stream_bytes, gallery_offset, stream_ids, batch, max_tracks, max_det,
+                                           dim, rd.q, rd.flags, rd.code, s);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("track_reid launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_track_reid_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                       int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
+                       int* det_index, int* out_counts, const float* embed, int capacity, int dim,
+                       const int* feat_counts, const int* embed_total, const yh_reid_params* rp, void* workspace,
+                       size_t workspace_bytes, int threads) {
+    return guarded([&] {
+        checked(yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
+                               det_index, out_counts));
+        checked(yh_track_reid_check(batch, max_det, max_tracks, capacity, dim, rp, workspace, workspace_bytes));
+        const yh_track_reid_args ra{embed, capacity, dim, feat_counts, embed_total, *rp, workspace};
+        yh_track_host_run(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
+                          det_index, out_counts, threads, &ra);
     });
 }
 

@@ -33,6 +33,14 @@
 // launch. In the scans all groups of a wave read the same list entries (broadcasts) and a group's
 // lanes consecutive ones.
 // Built with -ffp-contract=off: every formula must round exactly as in the host twin.
+//
+// yh_track_reid is the same kernel, instantiated with APP: its first association takes a pair's
+// candidacy and sort value from yh_trk_pair_reid, with the dot products the similarity launch in
+// front of it (csrc/reid.hip) left in the workspace, as sim (T, D) and as its transpose, so that a
+// slot's walk over the rows and a row's walk over the slots both read neighbouring entries, four
+// of them in flight per lane. Which slots and rows have a feature comes from the workspace too (a
+// word more per slot and per row in LDS). The galleries are not touched here: the kernel leaves
+// each slot's row of this frame in the workspace for the gallery launch behind it.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -49,10 +57,13 @@ constexpr int TRACK_T = 1024;                 // threads per workgroup (16 waves
 constexpr int TRACK_WAVES = TRACK_T / 64;
 static_assert(YH_TRACK_MAX_TRACKS <= TRACK_T && YH_TRACK_MAX_DET <= TRACK_T, "a thread owns one slot and one row");
 
-constexpr size_t track_lds(int T, int D) { return ((size_t)9 * T + (size_t)7 * D + 2 * TRACK_WAVES + 4) * 4; }
+// app: the appearance instance (yh_track_reid) keeps a word more per slot and per row
+constexpr size_t track_lds(int T, int D, bool app = false) {
+    return ((size_t)(app ? 10 : 9) * T + (size_t)(app ? 8 : 7) * D + 2 * TRACK_WAVES + 4) * 4;
+}
 // above the 64 KiB a workgroup gets by default at the caps: launch_track requests the size with the
 // attribute csrc/merge.hip uses (up to 160 KiB per workgroup on gfx950)
-static_assert(track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET) <= 160 * 1024, "LDS plan");
+static_assert(track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET, true) <= 160 * 1024, "LDS plan");
 
 struct Lds {
     float *sx1, *sy1, *sx2, *sy2, *scls;   // [T] slot box and class
@@ -61,7 +72,22 @@ struct Lds {
     int *mslot, *rlist;                    // [D] matched slot, live list
     int* wsum;                             // [2][TRACK_WAVES] prefix-sum wave totals
     int* ctl;                              // [0] last round that matched, [1] f, [2] ids handed out, [3] rows
+    int *gnz, *qfl;                        // appearance only: [T] the gallery row is non-zero, [D] the row's flags
 };
+
+// One pair of an association: a candidate, and with which sort value? APP: the first association
+// of yh_track_reid; dot is the pair's entry of the similarity matrix (whatever the memory holds
+// where a side has no feature: it is not used then).
+template <bool APP>
+__device__ inline bool pair_value(const Lds& L, const TrackReid& rd, int dot, int t, int d, const yh_track_box& tb,
+                                  const yh_track_box& db, float thr, float& val) {
+    if constexpr (APP) {
+        const bool feat = L.gnz[t] && (L.qfl[d] & 2);
+        return yh_trk_pair_reid(tb, db, thr, feat, dot, rd.cos_min, rd.iou_min, val);
+    } else {
+        return yh_trk_pair(tb, db, thr, val);
+    }
+}
 
 // exclusive ranks of two flags over the workgroup (thread order) and their totals; the totals
 // are read from LDS after a barrier: workgroup-uniform
@@ -114,9 +140,16 @@ __device__ inline int group_size(int n) {
 }
 
 // assoc(T, D, thr) of the specification. slive / rlive: this thread's slot / row takes part (false
-// for a thread without one). round: the workgroup's running round number (uniform).
+// for a thread without one). round: the workgroup's running round number (uniform). APP: pairs by
+// pair_value<true> (sim (T, D): this batch row's similarities, sim_t (D, T): their transpose, so
+// that the walk along a row of either scan reads neighbouring entries).
+template <bool APP>
 __device__ void assoc(const Lds& L, bool slive, bool rlive, float thr, int class_aware, int tid, int lane,
-                      int wave, int& round) {
+                      int wave, int& round, const TrackReid& rd, const int* __restrict__ sim,
+                      const int* __restrict__ sim_t, int T, int D) {
+    // APP: a lane takes U pairs at a time, so that their U similarities, which come from global
+    // memory, are in flight together; the plain instance walks pair by pair as before
+    constexpr int U = 4;
     if (slive) L.sact[tid] = 1;         // cleared by the row that takes the slot
     for (;;) {
         // the lists of the slots and rows still live: as pairs retire, more lanes share a scan
@@ -136,14 +169,27 @@ __device__ void assoc(const Lds& L, bool slive, bool rlive, float thr, int class
             if (t >= 0) {
                 const yh_track_box tb{L.sx1[t], L.sy1[t], L.sx2[t], L.sy2[t]};
                 const float tc = L.scls[t];
-                for (int j = g; j < nr; j += gs) {
-                    const int d = L.rlist[j];
-                    if (class_aware && !(tc == L.rcls[d])) continue;
+                auto consider = [&](int d, int dot) {
+                    if (class_aware && !(tc == L.rcls[d])) return;
                     const yh_track_box db{L.rx1[d], L.ry1[d], L.rx2[d], L.ry2[d]};
                     float iou;
-                    if (!yh_trk_pair(tb, db, thr, iou)) continue;
+                    if (!pair_value<APP>(L, rd, dot, t, d, tb, db, thr, iou)) return;
                     const unsigned long long key = pair_key(iou, d);
                     if (key > bk) bk = key;
+                };
+                if constexpr (APP) {   // row t of sim: a group's lanes read neighbouring entries
+                    for (int j0 = g; j0 < nr; j0 += gs * U) {
+                        int dd[U], dot[U];
+#pragma unroll
+                        for (int u = 0; u < U; ++u) dd[u] = j0 + u * gs < nr ? L.rlist[j0 + u * gs] : -1;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) dot[u] = dd[u] >= 0 ? sim[(size_t)t * D + dd[u]] : 0;
+#pragma unroll
+                        for (int u = 0; u < U; ++u)
+                            if (dd[u] >= 0) consider(dd[u], dot[u]);
+                    }
+                } else {
+                    for (int j = g; j < nr; j += gs) consider(L.rlist[j], 0);
                 }
             }
             bk = group_max(bk, gs);
@@ -158,14 +204,27 @@ __device__ void assoc(const Lds& L, bool slive, bool rlive, float thr, int class
             if (d >= 0) {
                 const yh_track_box db{L.rx1[d], L.ry1[d], L.rx2[d], L.ry2[d]};
                 const float dc = L.rcls[d];
-                for (int j = g; j < ns; j += gr) {
-                    const int t = L.slist[j];
-                    if (class_aware && !(L.scls[t] == dc)) continue;
+                auto consider = [&](int t, int dot) {
+                    if (class_aware && !(L.scls[t] == dc)) return;
                     const yh_track_box tb{L.sx1[t], L.sy1[t], L.sx2[t], L.sy2[t]};
                     float iou;
-                    if (!yh_trk_pair(tb, db, thr, iou)) continue;
+                    if (!pair_value<APP>(L, rd, dot, t, d, tb, db, thr, iou)) return;
                     const unsigned long long key = pair_key(iou, t);
                     if (key > bk) bk = key;
+                };
+                if constexpr (APP) {   // row d of the transpose: neighbouring entries again
+                    for (int j0 = g; j0 < ns; j0 += gr * U) {
+                        int tt[U], dot[U];
+#pragma unroll
+                        for (int u = 0; u < U; ++u) tt[u] = j0 + u * gr < ns ? L.slist[j0 + u * gr] : -1;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) dot[u] = tt[u] >= 0 ? sim_t[(size_t)d * T + tt[u]] : 0;
+#pragma unroll
+                        for (int u = 0; u < U; ++u)
+                            if (tt[u] >= 0) consider(tt[u], dot[u]);
+                    }
+                } else {
+                    for (int j = g; j < ns; j += gr) consider(L.slist[j], 0);
                 }
             }
             bk = group_max(bk, gr);
@@ -191,12 +250,16 @@ __device__ void assoc(const Lds& L, bool slive, bool rlive, float thr, int class
     }
 }
 
+// APP: yh_track_reid. A stream's state is then stream_bytes long, its gallery behind the words
+// of yh_track's state; rd is not read otherwise.
+template <bool APP>
 __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict__ dets, const int* __restrict__ counts,
                                                         int D, const int* __restrict__ stream_ids,
-                                                        uint32_t* __restrict__ state, int streams, int T,
-                                                        yh_track_params p, int max_out, float* __restrict__ out,
-                                                        int* __restrict__ ids, int* __restrict__ det_index,
-                                                        int* __restrict__ out_counts) {
+                                                        char* __restrict__ state, size_t stream_bytes, int streams,
+                                                        int T, yh_track_params p, int max_out,
+                                                        float* __restrict__ out, int* __restrict__ ids,
+                                                        int* __restrict__ det_index, int* __restrict__ out_counts,
+                                                        TrackReid rd) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Lds L;
     {
@@ -218,7 +281,9 @@ __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict_
         L.mslot = reinterpret_cast<int*>(at); at += D;
         L.rlist = reinterpret_cast<int*>(at); at += D;
         L.wsum = reinterpret_cast<int*>(at); at += 2 * TRACK_WAVES;
-        L.ctl = reinterpret_cast<int*>(at);
+        L.ctl = reinterpret_cast<int*>(at); at += 4;
+        L.gnz = reinterpret_cast<int*>(at); at += T;   // beyond the request unless APP: never touched then
+        L.qfl = reinterpret_cast<int*>(at);
     }
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
@@ -235,9 +300,13 @@ __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict_
             odet[i] = 0;
         }
         if (tid == 0) out_counts[b] = 0;
+        if constexpr (APP)
+            for (int i = tid; i < T; i += TRACK_T) rd.code[(size_t)b * T + i] = -1;   // no gallery to update
         return;
     }
-    uint32_t* w = state + (size_t)s * yh_track_stream_words(T);
+    uint32_t* w = reinterpret_cast<uint32_t*>(state + (size_t)s * stream_bytes);
+    const int* sim = APP ? rd.sim + (size_t)b * T * D : nullptr;
+    const int* sim_t = APP ? rd.sim_t + (size_t)b * T * D : nullptr;
     uint32_t* fld = w + YH_TRACK_HDR + tid;            // field i of this thread's slot: fld[i * T]
     if (tid == 0) {
         int n = counts[b];
@@ -301,11 +370,20 @@ __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict_
         L.rcls[tid] = rcl;
         L.mslot[tid] = -1;
     }
+    if constexpr (APP) {
+        // the rows' flags, and which slots hold a feature (found by the similarity launch, which
+        // read every gallery row; without features nothing asks)
+        if (tid < D) L.qfl[tid] = has_row ? rd.flags[(size_t)b * D + tid] : 0;
+        if (has_slot) L.gnz[tid] = rd.gnz ? rd.gnz[(size_t)b * T + tid] : 0;
+    }
     // phase 2 (the first barrier of each association's prefix sum orders the writes above)
     int round = 0;
-    assoc(L, st0 == 2 || st0 == 3, band == 2, p.iou_first, p.class_aware, tid, lane, wave, round);
-    assoc(L, st0 == 2 && L.mrow[tid] < 0, band == 1, p.iou_second, p.class_aware, tid, lane, wave, round);
-    assoc(L, st0 == 1, band == 2 && L.mslot[tid] < 0, p.iou_tentative, p.class_aware, tid, lane, wave, round);
+    assoc<APP>(L, st0 == 2 || st0 == 3, band == 2, p.iou_first, p.class_aware, tid, lane, wave, round, rd, sim, sim_t, T,
+               D);
+    assoc<false>(L, st0 == 2 && L.mrow[tid] < 0, band == 1, p.iou_second, p.class_aware, tid, lane, wave, round, rd,
+                 sim, sim_t, T, D);
+    assoc<false>(L, st0 == 1, band == 2 && L.mslot[tid] < 0, p.iou_tentative, p.class_aware, tid, lane, wave, round, rd,
+                 sim, sim_t, T, D);
 
     // phase 3: step 4 ...
     int st = st0;
@@ -344,6 +422,15 @@ __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict_
         if (f == 1) {                  // only these births are output: the others are tentative
             myrow = d;
             L.mslot[d] = tid;
+        }
+    }
+    if constexpr (APP) {
+        // the gallery's work of this slot, for the launch behind this one: its row of this frame,
+        // born slots tagged
+        if (has_slot) {
+            int code = st0 != 0 ? L.mrow[tid] : -1;
+            if (born) code = L.rlist[kf] | (1 << 30);
+            rd.code[(size_t)b * T + tid] = code;
         }
     }
     // phase 4: step 6
@@ -398,17 +485,34 @@ __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict_
 
 }  // namespace
 
-int launch_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
-                 int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
-                 int* det_index, int* out_counts, hipStream_t s) {
+template <bool APP>
+int launch(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+           size_t stream_bytes, int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
+           int* det_index, int* out_counts, const TrackReid& rd, hipStream_t s) {
     // arguments were checked by yh_track (yh_track_check): 1 <= max_tracks <= YH_TRACK_MAX_TRACKS,
     // 0 <= max_det <= YH_TRACK_MAX_DET
     if (batch <= 0) return 0;
-    if (int rc = lds_optin(reinterpret_cast<const void*>(track_kernel), (int)track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET))) return rc;
-    hipLaunchKernelGGL(track_kernel, dim3(batch), dim3(TRACK_T), track_lds(max_tracks, max_det), s, dets, counts, max_det,
-                       stream_ids, static_cast<uint32_t*>(state), streams, max_tracks, p, max_out, out, ids, det_index,
-                       out_counts);
+    if (int rc = lds_optin(reinterpret_cast<const void*>(track_kernel<APP>),
+                           (int)track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET, APP)))
+        return rc;
+    hipLaunchKernelGGL(track_kernel<APP>, dim3(batch), dim3(TRACK_T), track_lds(max_tracks, max_det, APP), s, dets, counts,
+                       max_det, stream_ids, static_cast<char*>(state), stream_bytes, streams, max_tracks, p, max_out, out,
+                       ids, det_index, out_counts, rd);
     return (int)hipGetLastError();
+}
+
+int launch_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                 int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
+                 int* det_index, int* out_counts, hipStream_t s) {
+    return launch<false>(dets, counts, batch, max_det, stream_ids, state, yh_track_stream_words(max_tracks) * 4, streams,
+                         max_tracks, p, max_out, out, ids, det_index, out_counts, TrackReid{}, s);
+}
+
+int launch_track_reid(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                      int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
+                      int* det_index, int* out_counts, const TrackReid& rd, hipStream_t s) {
+    return launch<true>(dets, counts, batch, max_det, stream_ids, state, yh_track_reid_stream_bytes(max_tracks, rd.dim),
+                        streams, max_tracks, p, max_out, out, ids, det_index, out_counts, rd, s);
 }
 
 }  // namespace yh

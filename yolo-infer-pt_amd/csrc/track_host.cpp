@@ -10,6 +10,7 @@
 // is preceded by no pair that shares a side with it, so the walk takes it; removing it and
 // repeating is the walk.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -19,7 +20,7 @@
 namespace {
 
 struct Pair {
-    uint32_t ord;   // yh::float_order(iou)
+    uint32_t ord;   // yh::float_order(sort value)
     int t, d;
 };
 
@@ -35,8 +36,9 @@ struct Frame {
 
 yh_track_box row_box(const float* d) { return yh_track_box{d[0], d[1], d[2], d[3]}; }
 
-template <class FS, class FR>
-void assoc(Frame& fr, FS slot_live, FR row_live, float thr, int class_aware) {
+// pair(t, d, val): is (slot t, row d) a candidate, and with which sort value?
+template <class FS, class FR, class FP>
+void assoc(Frame& fr, FS slot_live, FR row_live, int class_aware, FP pair) {
     std::vector<Pair> pairs;
     const int T = (int)fr.status.size();
     for (int t = 0; t < T; ++t) {
@@ -45,9 +47,9 @@ void assoc(Frame& fr, FS slot_live, FR row_live, float thr, int class_aware) {
             if (!row_live(d)) continue;
             const float* r = fr.dets + 6 * (size_t)d;
             if (class_aware && !(fr.tcls[t] == r[5])) continue;
-            float iou;
-            if (!yh_trk_pair(fr.tbox[t], row_box(r), thr, iou)) continue;
-            pairs.push_back({yh::float_order(iou), t, d});
+            float val;
+            if (!pair(t, d, val)) continue;
+            pairs.push_back({yh::float_order(val), t, d});
         }
     }
     std::sort(pairs.begin(), pairs.end(), [](const Pair& p, const Pair& q) {
@@ -82,9 +84,50 @@ void store_kal(uint32_t* w, int T, int t, const yh_track_kal& k) {
     }
 }
 
-// one frame of one stream; w: the stream's state words
+// The appearance side of one frame of one stream (yh_track_reid): the rows' quantised features
+// and flags in the workspace, the stream's gallery.
+struct Reid {
+    const int8_t* q;      // (max_det, dim)
+    const int* flags;     // (max_det): bit 0 the row has a feature, bit 1 its q is non-zero
+    int8_t* gallery;      // (T, dim)
+    int dim;
+    yh_reid_params rp;
+};
+
+bool nonzero(const int8_t* v, int dim) {
+    for (int i = 0; i < dim; ++i)
+        if (v[i]) return true;
+    return false;
+}
+
+// the gallery update of slot t with row d (born: the slot was born in this frame)
+void gallery_update(const Reid& r, int t, int d, bool born) {
+    int8_t* g = r.gallery + (size_t)t * r.dim;
+    if (!(r.flags[d] & 1)) {
+        if (born) std::memset(g, 0, r.dim);
+        return;
+    }
+    const int8_t* q = r.q + (size_t)d * r.dim;
+    if (born || !nonzero(g, r.dim)) {
+        std::memcpy(g, q, r.dim);
+        return;
+    }
+    int64_t S = 0;
+    for (int i = 0; i < r.dim; ++i) {
+        const int v = 7 * (int)g[i] + (int)q[i];
+        S += (int64_t)v * v;
+    }
+    if (S == 0) {
+        std::memset(g, 0, r.dim);
+        return;
+    }
+    const double scale = yh_reid_scale(S);
+    for (int i = 0; i < r.dim; ++i) g[i] = (int8_t)yh_reid_round(7 * (int)g[i] + (int)q[i], scale);
+}
+
+// one frame of one stream; w: the stream's state words; reid: NULL for yh_track
 void track_stream(const float* dets, int count, int max_det, uint32_t* w, int T, const yh_track_params& p,
-                  int max_out, float* out, int* ids, int* det_index, int* out_count) {
+                  int max_out, float* out, int* ids, int* det_index, int* out_count, const Reid* reid) {
     std::fill(out, out + (size_t)max_out * 6, 0.0f);
     std::fill(ids, ids + max_out, 0);
     std::fill(det_index, det_index + max_out, 0);
@@ -116,10 +159,38 @@ void track_stream(const float* dets, int count, int max_det, uint32_t* w, int T,
     auto high = [&](int d) { return score(d) >= p.track_high; };
     auto low = [&](int d) { return score(d) >= p.track_low && score(d) < p.track_high; };
     // step 3
-    assoc(fr, [&](int t) { return fr.status[t] == 2 || fr.status[t] == 3; }, high, p.iou_first, p.class_aware);
-    assoc(fr, [&](int t) { return fr.status[t] == 2 && fr.mrow[t] < 0; }, low, p.iou_second, p.class_aware);
+    auto by_iou = [&](float thr) {
+        return [&fr, dets, thr](int t, int d, float& val) {
+            return yh_trk_pair(fr.tbox[t], row_box(dets + 6 * (size_t)d), thr, val);
+        };
+    };
+    auto first = [&](int t) { return fr.status[t] == 2 || fr.status[t] == 3; };
+    if (reid) {
+        std::vector<char> gnz(T, 0);
+        for (int t = 0; t < T; ++t) gnz[t] = first(t) && nonzero(reid->gallery + (size_t)t * reid->dim, reid->dim);
+        assoc(fr, first, high, p.class_aware, [&](int t, int d, float& val) {
+            const bool feat = gnz[t] && (reid->flags[d] & 2);
+            int dot = 0;
+            if (feat) {
+                const int8_t* g = reid->gallery + (size_t)t * reid->dim;
+                const int8_t* q = reid->q + (size_t)d * reid->dim;
+                for (int i = 0; i < reid->dim; ++i) dot += (int)g[i] * (int)q[i];
+            }
+            return yh_trk_pair_reid(fr.tbox[t], row_box(dets + 6 * (size_t)d), p.iou_first, feat, dot,
+                                    reid->rp.cos_min, reid->rp.iou_min, val);
+        });
+    } else {
+        assoc(fr, first, high, p.class_aware, by_iou(p.iou_first));
+    }
+    assoc(fr, [&](int t) { return fr.status[t] == 2 && fr.mrow[t] < 0; }, low, p.class_aware, by_iou(p.iou_second));
     assoc(fr, [&](int t) { return fr.status[t] == 1; }, [&](int d) { return high(d) && fr.mslot[d] < 0; },
-          p.iou_tentative, p.class_aware);
+          p.class_aware, by_iou(p.iou_tentative));
+    std::vector<int> grow;   // the gallery's work: slot -> its row of this frame, born ones tagged
+    if (reid) {
+        grow.assign(T, -1);
+        for (int t = 0; t < T; ++t)
+            if (st[t] != 0 && fr.mrow[t] >= 0) grow[t] = fr.mrow[t];
+    }
     // step 4
     for (int t = 0; t < T; ++t) {
         if (st[t] == 0) continue;
@@ -154,7 +225,11 @@ void track_stream(const float* dets, int count, int max_det, uint32_t* w, int T,
             fr.mrow[t] = d;
             fr.mslot[d] = t;
         }
+        if (reid) grow[t] = d | (1 << 30);
     }
+    if (reid)
+        for (int s = 0; s < T; ++s)
+            if (grow[s] >= 0) gallery_update(*reid, s, grow[s] & ~(1 << 30), (grow[s] >> 30) != 0);
     // step 6
     int k = 0;
     for (int d = 0; d < fr.n && k < max_out; ++d) {
@@ -193,10 +268,119 @@ const char* yh_track_check(const void* dets, const void* counts, int batch, int 
     return nullptr;
 }
 
+const char* yh_reid_dim_check(int dim) {
+    if (dim < 64 || dim > YH_REID_MAX_DIM || dim % 64) return "dim must be a multiple of 64 in [64, " YH_STR(YH_REID_MAX_DIM) "]";
+    return nullptr;
+}
+
+const char* yh_track_reid_check(int batch, int max_det, int max_tracks, int capacity, int dim, const yh_reid_params* rp,
+                                const void* workspace, size_t workspace_bytes) {
+    if (const char* bad = yh_reid_dim_check(dim)) return bad;
+    if (capacity < 0) return "capacity must be >= 0";
+    if (!rp) return "null reid params";
+    if (!std::isfinite(rp->cos_min) || !std::isfinite(rp->iou_min)) return "cos_min / iou_min must be finite";
+    if (batch > 0 && !workspace) return "null workspace";
+    if (batch > 0 && workspace_bytes < yh_reid_ws_bytes(batch, max_det, max_tracks, dim)) return "reid workspace too small";
+    return nullptr;
+}
+
+const char* yh_embed_quantize_check(const void* e, int rows, int dim, const void* q) {
+    if (const char* bad = yh_reid_dim_check(dim)) return bad;
+    if (rows < 0) return "rows must be >= 0";
+    if (rows > 0 && (!e || !q)) return "null e / q";
+    return nullptr;
+}
+
+const char* yh_embed_similarity_check(const void* a, size_t a_block_stride, int nblocks, const void* b, int batch,
+                                      int ra, int rb, int dim, const void* out) {
+    if (const char* bad = yh_reid_dim_check(dim)) return bad;
+    if (batch < 0 || ra < 0 || rb < 0 || nblocks < 0) return "batch, ra, rb and nblocks must be >= 0";
+    if (a_block_stride < (size_t)ra * dim) return "a_block_stride is smaller than a block (ra * dim)";
+    if (batch > 0 && ra > 0 && rb > 0 && !out) return "null out";
+    if (batch > 0 && ra > 0 && rb > 0 && !b) return "null b";
+    if (batch > 0 && ra > 0 && rb > 0 && nblocks > 0 && !a) return "null a";
+    return nullptr;
+}
+
+void yh_embed_quantize_row(const float* e, int dim, int8_t* q) {
+    std::memset(q, 0, dim);
+    if (!e) return;
+    float m = 0.0f;
+    for (int i = 0; i < dim; ++i) {
+        if (!std::isfinite(e[i])) return;
+        const float a = std::fabs(e[i]);
+        if (a > m) m = a;
+    }
+    if (m == 0.0f) return;
+    const double r = 16384.0 / (double)m;
+    std::vector<int> pv(dim);
+    int64_t S = 0;
+    for (int i = 0; i < dim; ++i) {
+        pv[i] = (int)rint((double)e[i] * r);
+        S += (int64_t)pv[i] * pv[i];
+    }
+    const double scale = yh_reid_scale(S);   // S >= 16384^2: the largest element
+    for (int i = 0; i < dim; ++i) q[i] = (int8_t)yh_reid_round(pv[i], scale);
+}
+
+int yh_embed_quantize_host_run(const float* e, int rows, int dim, const int* count, int8_t* q, int threads) {
+    const int n = count ? std::min(std::max(*count, 0), rows) : rows;
+    yh::parallel_strided(rows, threads, [&](int r) {
+        yh_embed_quantize_row(r < n ? e + (size_t)r * dim : nullptr, dim, q + (size_t)r * dim);
+    });
+    return 0;
+}
+
+int yh_embed_similarity_host_run(const int8_t* a, size_t a_block_stride, int nblocks, const int* a_index,
+                                 const int8_t* b, int batch, int ra, int rb, int dim, int32_t* out, int threads) {
+    yh::parallel_strided(batch * ra, threads, [&](int job) {
+        const int bz = job / ra, m = job % ra;
+        const int k = a_index ? a_index[bz] : bz;
+        int32_t* o = out + ((size_t)bz * ra + m) * rb;
+        if (k < 0 || k >= nblocks) {
+            std::fill(o, o + rb, 0);
+            return;
+        }
+        const int8_t* ar = a + (size_t)k * a_block_stride + (size_t)m * dim;
+        for (int n = 0; n < rb; ++n) {
+            const int8_t* br = b + ((size_t)bz * rb + n) * dim;
+            int32_t acc = 0;
+            for (int i = 0; i < dim; ++i) acc += (int32_t)ar[i] * (int32_t)br[i];
+            o[n] = acc;
+        }
+    });
+    return 0;
+}
+
 int yh_track_host_run(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
                       void* state, int streams, int max_tracks, const yh_track_params* p, int max_out, float* out,
-                      int* ids, int* det_index, int* out_counts, int threads) {
+                      int* ids, int* det_index, int* out_counts, int threads, const yh_track_reid_args* ra) {
     const size_t words = yh_track_stream_words(max_tracks);
+    const size_t stride = ra ? yh_track_reid_stream_bytes(max_tracks, ra->dim) : words * 4;
+    int8_t* wq = nullptr;
+    int* wflags = nullptr;
+    if (ra && batch > 0) {
+        // the rows' features: yh_crop_rois' compaction, then the quantisation into the workspace
+        wq = static_cast<int8_t*>(ra->workspace);
+        wflags = reinterpret_cast<int*>(static_cast<char*>(ra->workspace) + yh_reid_ws_flags(batch, max_det, ra->dim));
+        long long limit = ra->embed ? ra->capacity : 0;
+        if (ra->embed && ra->embed_total) limit = std::min<long long>(limit, *ra->embed_total);
+        std::vector<long long> base(batch + 1, 0);
+        std::vector<int> nf(batch);
+        for (int b = 0; b < batch; ++b) {
+            const int c = std::min(std::max(counts[b], 0), max_det);
+            nf[b] = ra->feat_counts ? std::min(std::max(ra->feat_counts[b], 0), c) : c;
+            base[b + 1] = base[b] + nf[b];
+        }
+        yh::parallel_strided(batch * max_det, threads, [&](int job) {
+            const int b = job / max_det, r = job % max_det;
+            const long long s = base[b] + r;
+            const bool has = r < nf[b] && s < limit;
+            int8_t* q = wq + (size_t)job * ra->dim;
+            yh_embed_quantize_row(has ? ra->embed + (size_t)s * ra->dim : nullptr, ra->dim, q);
+            wflags[job] = has ? 1 | (nonzero(q, ra->dim) ? 2 : 0) : 0;
+        });
+    }
     auto run = [&](int b) {
         const int s = stream_ids ? stream_ids[b] : b;
         float* o = out + (size_t)b * max_out * 6;
@@ -209,9 +393,17 @@ int yh_track_host_run(const float* dets, const int* counts, int batch, int max_d
             out_counts[b] = 0;
             return;
         }
-        track_stream(dets + (size_t)b * max_det * 6, counts[b], max_det,
-                     static_cast<uint32_t*>(state) + (size_t)s * words, max_tracks, *p, max_out, o, oi, od,
-                     out_counts + b);
+        char* w = static_cast<char*>(state) + (size_t)s * stride;
+        Reid reid{};
+        if (ra) {
+            reid.q = wq + (size_t)b * max_det * ra->dim;
+            reid.flags = wflags + (size_t)b * max_det;
+            reid.gallery = reinterpret_cast<int8_t*>(w + words * 4);
+            reid.dim = ra->dim;
+            reid.rp = ra->rp;
+        }
+        track_stream(dets + (size_t)b * max_det * 6, counts[b], max_det, reinterpret_cast<uint32_t*>(w), max_tracks,
+                     *p, max_out, o, oi, od, out_counts + b, ra ? &reid : nullptr);
     };
     yh::parallel_strided(batch, threads, run);
     return 0;

@@ -6,6 +6,7 @@
 #ifndef YH_TRACK_HOST_H
 #define YH_TRACK_HOST_H
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -131,7 +132,78 @@ YH_HD bool yh_trk_pair(const yh_track_box& t, const yh_track_box& d, float thr, 
     return iou >= thr;
 }
 
+// The appearance term of yh_track_reid's first association, in place of yh_trk_pair: is the pair
+// a candidate, and with which sort value? feat: the slot's gallery row and the row's quantised
+// feature are both non-zero; dot: their int32 product (read only when feat).
+YH_HD bool yh_trk_pair_reid(const yh_track_box& t, const yh_track_box& d, float thr, bool feat, int dot,
+                            float cos_min, float iou_min, float& val) {
+    const float inter = yh::intersection(t.x1, t.y1, t.x2, t.y2, d.x1, d.y1, d.x2, d.y2);
+    float iou = 0.0f;
+    if (inter != 0.0f) {
+        const float at = (t.x2 - t.x1) * (t.y2 - t.y1);
+        const float ad = (d.x2 - d.x1) * (d.y2 - d.y1);
+        iou = inter / ((at + ad) - inter);
+    }
+    val = iou;
+    bool eligible = false;
+    if (feat) {
+        const float cosv = (float)dot / 16129.0f;
+        const float app = 0.5f + 0.5f * cosv;
+        eligible = cosv >= cos_min && iou >= iou_min;
+        if (eligible && app > iou) val = app;
+    }
+    return (inter != 0.0f && iou >= thr) || eligible;
+}
+
+// An integer vector of squared length S scaled to length 127: the factor, and an element
+// (yh_embed_quantize's step 4 and the gallery update). fp64, one rounding per operation.
+YH_HD double yh_reid_scale(int64_t S) { return 127.0 / sqrt((double)S); }
+YH_HD int yh_reid_round(int v, double scale) { return (int)rint((double)v * scale); }
+
+// yh_track_reid's state: per stream yh_track's words, then the gallery (max_tracks, dim) int8
+YH_HD size_t yh_track_reid_stream_bytes(int max_tracks, int dim) {
+    return yh_track_stream_words(max_tracks) * 4 + (size_t)max_tracks * (size_t)dim;
+}
+
+// yh_track_reid's workspace: q (batch, max_det, dim) int8, flags (batch, max_det) int32 (bit 0:
+// the row has a feature, bit 1: its q is non-zero), and for the device only sim (batch, max_tracks,
+// max_det) int32 and its transpose sim_t, gnz (batch, max_tracks) int32 (the slot's gallery row is non-zero) and code
+// (batch, max_tracks) int32 (the gallery update's work); sections 256-byte aligned
+YH_HD size_t yh_reid_al(size_t v) { return (v + 255) & ~(size_t)255; }
+YH_HD size_t yh_reid_ws_flags(int batch, int max_det, int dim) { return yh_reid_al((size_t)batch * max_det * dim); }
+YH_HD size_t yh_reid_ws_sim(int batch, int max_det, int dim) {
+    return yh_reid_al(yh_reid_ws_flags(batch, max_det, dim) + (size_t)batch * max_det * 4);
+}
+YH_HD size_t yh_reid_ws_sim_t(int batch, int max_det, int max_tracks, int dim) {
+    return yh_reid_al(yh_reid_ws_sim(batch, max_det, dim) + (size_t)batch * max_tracks * max_det * 4);
+}
+YH_HD size_t yh_reid_ws_gnz(int batch, int max_det, int max_tracks, int dim) {
+    return yh_reid_al(yh_reid_ws_sim_t(batch, max_det, max_tracks, dim) + (size_t)batch * max_tracks * max_det * 4);
+}
+YH_HD size_t yh_reid_ws_code(int batch, int max_det, int max_tracks, int dim) {
+    return yh_reid_al(yh_reid_ws_gnz(batch, max_det, max_tracks, dim) + (size_t)batch * max_tracks * 4);
+}
+YH_HD size_t yh_reid_ws_bytes(int batch, int max_det, int max_tracks, int dim) {
+    return yh_reid_al(yh_reid_ws_code(batch, max_det, max_tracks, dim) + (size_t)batch * max_tracks * 4);
+}
+
+// The appearance arguments of yh_track_reid as the host loop takes them (NULL: plain yh_track)
+struct yh_track_reid_args {
+    const float* embed;
+    int capacity, dim;
+    const int* feat_counts;
+    const int* embed_total;
+    yh_reid_params rp;
+    void* workspace;
+};
+
 // NULL when the arguments are acceptable, else the message for yh_last_error() (YH_EINVAL).
+const char* yh_reid_dim_check(int dim);
+const char* yh_track_reid_check(int batch, int max_det, int max_tracks, int capacity, int dim, const yh_reid_params* rp,
+                                const void* workspace, size_t workspace_bytes);
+const char* yh_embed_quantize_check(const void* e, int rows, int dim, const void* q);
+const char* yh_embed_similarity_check(const void* a, size_t a_block_stride, int nblocks, const void* b, int batch,
+                                      int ra, int rb, int dim, const void* out);
 const char* yh_track_check(const void* dets, const void* counts, int batch, int max_det, const void* state,
                            int streams, int max_tracks, const yh_track_params* p, int max_out, const void* out,
                            const void* ids, const void* det_index, const void* out_counts);
@@ -140,6 +212,13 @@ const char* yh_track_check(const void* dets, const void* counts, int batch, int 
 // `threads` (<= 0: every hardware thread).
 int yh_track_host_run(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
                       void* state, int streams, int max_tracks, const yh_track_params* p, int max_out, float* out,
-                      int* ids, int* det_index, int* out_counts, int threads);
+                      int* ids, int* det_index, int* out_counts, int threads,
+                      const yh_track_reid_args* reid = nullptr);
+
+// The host twins of yh_embed_quantize / yh_embed_similarity; arguments already checked.
+void yh_embed_quantize_row(const float* e, int dim, int8_t* q);   // one row; e NULL: zeros
+int yh_embed_quantize_host_run(const float* e, int rows, int dim, const int* count, int8_t* q, int threads);
+int yh_embed_similarity_host_run(const int8_t* a, size_t a_block_stride, int nblocks, const int* a_index,
+                                 const int8_t* b, int batch, int ra, int rb, int dim, int32_t* out, int threads);
 
 #endif

@@ -8,7 +8,8 @@ from BGR or `NV12` video frames on a square or rectangular canvas (`letterbox_fr
 `rect_canvas`; yolo_hip.preprocess), and `crop_rois` cuts one fixed-size crop per detection from
 those frames for a second-stage model (`Crops`);
 `Tracker` (yolo_hip.track) gives the detections of video streams identities across frames
-(`track`, `track_state`, `Tracks`); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
+(`track`, `track_state`, `Tracks`), with re-identification by appearance when it is given
+embeddings (`track_reid`, `embed_quantize`, `embed_similarity`); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
 those crops (`Classified`: class, confidence and embedding per detection). The drop-in module API lives in `nets.nn` / `utils.util`.
 """
 from .variants import VARIANTS, Variant, lookup  # noqa: F401
@@ -34,7 +35,7 @@ def __getattr__(name):
     if name in ("Classifier", "Classified"):
         from . import classify
         return getattr(classify, name)
-    if name in ("Tracker", "Tracks", "track", "track_state"):
+    if name in ("Tracker", "Tracks", "track", "track_state", "track_reid", "embed_quantize", "embed_similarity"):
         # the function shares its name with its module, and importing the module binds the name
         # here: the module is callable as the function (yolo_hip/track.py, at its end)
         import importlib

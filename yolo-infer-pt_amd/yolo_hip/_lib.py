@@ -92,6 +92,20 @@ _PROTOS = {
                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_track_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "yh_embed_quantize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "yh_embed_quantize_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]),
+    "yh_embed_similarity": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                    c_void_p]),
+    "yh_embed_similarity_host": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                         c_void_p, c_int]),
+    "yh_track_reid_state_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "yh_track_reid_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "yh_track_reid": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "yh_track_reid_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_int]),
     "yh_letterbox_geometry": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_letterbox": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "yh_letterbox_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),

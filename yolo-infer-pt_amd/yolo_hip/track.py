@@ -8,6 +8,8 @@ lies - no copy to the host, no synchronisation:
   track        yh_track / yh_track_host: one frame of every stream of a batch (functional)
   track_state  the zeroed state tensor of `streams` streams
   Tracks       (dets, ids, det_index, counts) of one call
+  track_reid   yh_track_reid: `track` with an appearance term (int8 features, cosine by int8 MFMA)
+  embed_quantize, embed_similarity   its two primitives, usable alone for gallery search
   Tracker      the state, the thresholds and the buffers of a set of streams; `update` for a
                caller's loop, `post` as the in-stream hook of a DetectPipeline
 
@@ -27,6 +29,7 @@ import torch
 
 MAX_TRACKS = 1024   # YH_TRACK_MAX_TRACKS
 MAX_DET = 1024      # YH_TRACK_MAX_DET
+REID_MAX_DIM = 2048  # YH_REID_MAX_DIM
 _HDR, _FIELDS = 4, 24   # state words per stream: _HDR + _FIELDS * max_tracks (csrc/track_host.h)
 
 
@@ -45,14 +48,32 @@ def params(track_high=0.25, track_low=0.1, track_new=0.25, iou_first=0.2, iou_se
                        1 if class_aware else 0)
 
 
-def track_state(streams, max_tracks=256, device="cpu"):
+class ReidParams(ctypes.Structure):
+    """yh_reid_params"""
+    _fields_ = [("cos_min", ctypes.c_float), ("iou_min", ctypes.c_float)]
+
+
+def _check_dim(dim):
+    dim = int(dim)
+    if dim % 64 or not 64 <= dim <= REID_MAX_DIM:
+        raise ValueError(f"yolo_hip.track: the feature length must be a multiple of 64 in [64, {REID_MAX_DIM}], got {dim}")
+    return dim
+
+
+def _reid_words(max_tracks, dim):
+    return _HDR + _FIELDS * max_tracks + max_tracks * dim // 4
+
+
+def track_state(streams, max_tracks=256, device="cpu", reid_dim=None):
     """The empty state of `streams` streams: (streams, 4 + 24 * max_tracks) int32 zeros. The words are
     opaque, hold no addresses and mean the same on host and device: .cpu() / .to(device) / a file
-    carry a state over in the middle of a sequence."""
+    carry a state over in the middle of a sequence. reid_dim: the state of `track_reid` for features
+    of that length: each stream's words are followed by its gallery, max_tracks * reid_dim int8."""
     streams, max_tracks = int(streams), int(max_tracks)
     if streams < 0 or not 1 <= max_tracks <= MAX_TRACKS:
         raise ValueError(f"yolo_hip.track: streams must be >= 0 and max_tracks in [1, {MAX_TRACKS}]")
-    return torch.zeros((streams, _HDR + _FIELDS * max_tracks), dtype=torch.int32, device=device)
+    words = _HDR + _FIELDS * max_tracks if reid_dim is None else _reid_words(max_tracks, _check_dim(reid_dim))
+    return torch.zeros((streams, words), dtype=torch.int32, device=device)
 
 
 class Tracks(NamedTuple):
@@ -85,6 +106,36 @@ def _check(name, t, shape, dtype, device):
         raise ValueError(f"yolo_hip.track: {name} must be contiguous")
 
 
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _frame_args(dets, counts, state, stream_ids, max_out, out):
+    """The checks `track` and `track_reid` share -> (device, B, max_det, max_out, Tracks to write)."""
+    if not isinstance(dets, torch.Tensor) or dets.dim() != 3:
+        raise ValueError("yolo_hip.track: dets must be a (B, max_det, 6) tensor")
+    dev = dets.device
+    B, md = dets.shape[0], dets.shape[1]
+    _check("dets", dets, (B, md, 6), torch.float32, dev)
+    _check("counts", counts, (B,), torch.int32, dev)
+    _check("state", state, (None, None), torch.int32, dev)
+    if stream_ids is not None:
+        _check("stream_ids", stream_ids, (B,), torch.int32, dev)
+    max_out = md if max_out is None else int(max_out)
+    if out is None:
+        o = Tracks(torch.empty((B, max(max_out, 0), 6), dtype=torch.float32, device=dev),
+                   torch.empty((B, max(max_out, 0)), dtype=torch.int32, device=dev),
+                   torch.empty((B, max(max_out, 0)), dtype=torch.int32, device=dev),
+                   torch.empty((B,), dtype=torch.int32, device=dev))
+    else:
+        o = Tracks(*out)
+        _check("out dets", o.dets, (B, max_out, 6), torch.float32, dev)
+        _check("out ids", o.ids, (B, max_out), torch.int32, dev)
+        _check("out det_index", o.det_index, (B, max_out), torch.int32, dev)
+        _check("out counts", o.counts, (B,), torch.int32, dev)
+    return dev, B, md, max_out, o
+
+
 def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, threads=0):
     """One frame of every stream of a batch, in one launch.
 
@@ -100,36 +151,13 @@ def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, 
     the host twin (yh_track_host, `threads` <= 0: every hardware thread); both give the same bytes,
     state included. Frames of one stream must be submitted in order on one stream."""
     from ._lib import check, lib
-    if not isinstance(dets, torch.Tensor) or dets.dim() != 3:
-        raise ValueError("yolo_hip.track: dets must be a (B, max_det, 6) tensor")
-    dev = dets.device
-    B, md = dets.shape[0], dets.shape[1]
-    _check("dets", dets, (B, md, 6), torch.float32, dev)
-    _check("counts", counts, (B,), torch.int32, dev)
-    _check("state", state, (None, None), torch.int32, dev)
+    dev, B, md, max_out, o = _frame_args(dets, counts, state, stream_ids, max_out, out)
     S, words = state.shape
     if words < _HDR + _FIELDS or (words - _HDR) % _FIELDS:
         raise ValueError(f"yolo_hip.track: state has {words} words per stream, expected 4 + 24 * max_tracks")
     mt = (words - _HDR) // _FIELDS
-    if stream_ids is not None:
-        _check("stream_ids", stream_ids, (B,), torch.int32, dev)
-    max_out = md if max_out is None else int(max_out)
-    if out is None:
-        o = Tracks(torch.empty((B, max(max_out, 0), 6), dtype=torch.float32, device=dev),
-                   torch.empty((B, max(max_out, 0)), dtype=torch.int32, device=dev),
-                   torch.empty((B, max(max_out, 0)), dtype=torch.int32, device=dev),
-                   torch.empty((B,), dtype=torch.int32, device=dev))
-    else:
-        o = Tracks(*out)
-        _check("out dets", o.dets, (B, max_out, 6), torch.float32, dev)
-        _check("out ids", o.ids, (B, max_out), torch.int32, dev)
-        _check("out det_index", o.det_index, (B, max_out), torch.int32, dev)
-        _check("out counts", o.counts, (B,), torch.int32, dev)
     p = params() if p is None else p
-
-    def ptr(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
+    ptr = _ptr
     L = lib()
     if mt <= MAX_TRACKS and L.yh_track_state_bytes(S, mt) != state.numel() * 4:
         raise RuntimeError("yolo_hip.track: the library's state size differs from track_state's")
@@ -143,6 +171,149 @@ def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, 
     else:
         raise ValueError(f"yolo_hip.track: unsupported device {dev}")
     return o
+
+
+def reid_workspace(batch, max_det, max_tracks, dim, device="cpu"):
+    """The scratch buffer of `track_reid` for these sizes (uint8; its contents mean nothing between
+    calls)."""
+    from ._lib import lib
+    n = lib().yh_track_reid_workspace_bytes(int(batch), int(max_det), int(max_tracks), _check_dim(dim))
+    return torch.empty((n,), dtype=torch.uint8, device=device)
+
+
+def track_reid(dets, counts, state, embed=None, feat_counts=None, embed_total=None, dim=None, reid_cos=0.5,
+               reid_iou=0.5, p=None, stream_ids=None, max_out=None, out=None, workspace=None, threads=0):
+    """`track` with an appearance term in its first association (yh_track_reid): a track and a
+    high-score row may also pair when their features agree (cosine >= reid_cos) and they overlap
+    at least reid_iou, and such a pair is walked at the larger of its IoU and (1 + cosine) / 2.
+    reid_iou = 0 re-identifies a lost track anywhere in the frame. BoT-SORT's values are the
+    defaults.
+
+    state: `track_state(..., reid_dim=dim)`; it also carries one int8 feature per track.
+    embed (capacity, dim) f32 or None: the features of the rows, compacted as `crop_rois` compacts
+    its crops: row r of batch row b has a feature iff r < n_b = clamp(feat_counts[b], 0, counts[b])
+    (feat_counts None: the counts), at embed[n_0 + ... + n_(b-1) + r], as long as that index is
+    below capacity and below embed_total[0] when given - `Classified.embed` of `Crops` cut with
+    counts=feat_counts, and `Crops.total`, plug in as they lie. dim: the feature length when embed
+    is None. workspace: a `reid_workspace` to reuse (None: allocated per call).
+    Without features the result and the tracks are exactly `track`'s.
+
+    cuda tensors run the HIP kernels (quantise, the int8 MFMA similarity, the track kernel) on
+    the current stream, CPU tensors the host twin; both give the same bytes, state included."""
+    from ._lib import check, lib
+    dev, B, md, max_out, o = _frame_args(dets, counts, state, stream_ids, max_out, out)
+    if embed is not None:
+        if not isinstance(embed, torch.Tensor) or embed.dim() != 2:
+            raise ValueError("yolo_hip.track: embed must be a (capacity, dim) tensor")
+        if dim is not None and int(dim) != embed.shape[1]:
+            raise ValueError(f"yolo_hip.track: embed has {embed.shape[1]} columns, dim is {dim}")
+        dim = embed.shape[1]
+        _check("embed", embed, (None, dim), torch.float32, dev)
+    elif dim is None:
+        raise ValueError("yolo_hip.track: without embed, dim must be given")
+    dim = _check_dim(dim)
+    if feat_counts is not None:
+        _check("feat_counts", feat_counts, (B,), torch.int32, dev)
+    if embed_total is not None:
+        _check("embed_total", embed_total, (1,), torch.int32, dev)
+    S, words = state.shape
+    per = _FIELDS + dim // 4
+    if words < _HDR + per or (words - _HDR) % per:
+        raise ValueError(f"yolo_hip.track: state has {words} words per stream, expected 4 + (24 + dim / 4) * max_tracks")
+    mt = (words - _HDR) // per
+    L = lib()
+    if mt <= MAX_TRACKS and L.yh_track_reid_state_bytes(S, mt, dim) != state.numel() * 4:
+        raise RuntimeError("yolo_hip.track: the library's state size differs from track_state's")
+    need = L.yh_track_reid_workspace_bytes(B, md, mt, dim)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    else:
+        _check("workspace", workspace, (None,), torch.uint8, dev)
+    p = params() if p is None else p
+    rp = ReidParams(float(reid_cos), float(reid_iou))
+    args = (_ptr(dets), _ptr(counts), B, md, _ptr(stream_ids), _ptr(state), S, mt, ctypes.byref(p), max_out,
+            _ptr(o.dets), _ptr(o.ids), _ptr(o.det_index), _ptr(o.counts), _ptr(embed),
+            0 if embed is None else embed.shape[0], dim, _ptr(feat_counts), _ptr(embed_total), ctypes.byref(rp),
+            _ptr(workspace), workspace.numel())
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            check(L.yh_track_reid(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track_reid")
+    elif dev.type == "cpu":
+        check(L.yh_track_reid_host(*args, int(threads)), "track_reid_host")
+    else:
+        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+    return o
+
+
+def embed_quantize(e, count=None, out=None, threads=0):
+    """Unit int8 features (yh_embed_quantize): e (rows, dim) f32 -> (rows, dim) int8, each row scaled
+    to length 127; a row of zeros, or with an element that is not finite, gives zeros ("no
+    feature"). count (1,) i32 or None: rows at or beyond it give zeros. dim % 64 == 0, 64 <= dim <=
+    2048. cuda tensors run the kernel on the current stream, CPU tensors the host twin: the same
+    bytes."""
+    from ._lib import check, lib
+    if not isinstance(e, torch.Tensor) or e.dim() != 2:
+        raise ValueError("yolo_hip.track: e must be a (rows, dim) tensor")
+    dev = e.device
+    rows, dim = e.shape
+    _check("e", e, (rows, dim), torch.float32, dev)
+    _check_dim(dim)
+    if count is not None:
+        _check("count", count, (1,), torch.int32, dev)
+    if out is None:
+        out = torch.empty((rows, dim), dtype=torch.int8, device=dev)
+    else:
+        _check("out", out, (rows, dim), torch.int8, dev)
+    L = lib()
+    args = (_ptr(e), rows, dim, _ptr(count), _ptr(out))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            check(L.yh_embed_quantize(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  "embed_quantize")
+    elif dev.type == "cpu":
+        check(L.yh_embed_quantize_host(*args, int(threads)), "embed_quantize_host")
+    else:
+        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+    return out
+
+
+def embed_similarity(a, b, a_index=None, out=None, threads=0):
+    """Exact int32 products of int8 features (yh_embed_similarity): out[i] = A[i] @ b[i].T.
+    a (nblocks, ra, dim) int8, whose blocks may be strided (a.stride(0) >= ra * dim, the rest
+    contiguous); b (B, rb, dim) int8; a_index (B,) i32 or None: batch row i reads block
+    a_index[i] (None: block i), a block out of range counts as zeros. -> (B, ra, rb) int32. Two
+    `embed_quantize` rows give 16129 times their cosine. cuda tensors run the int8 MFMA kernel on
+    the current stream, CPU tensors the host twin: the same numbers."""
+    from ._lib import check, lib
+    if not isinstance(a, torch.Tensor) or a.dim() != 3 or not isinstance(b, torch.Tensor) or b.dim() != 3:
+        raise ValueError("yolo_hip.track: a must be (nblocks, ra, dim) and b (B, rb, dim)")
+    dev = a.device
+    nblocks, ra, dim = a.shape
+    B, rb = b.shape[0], b.shape[1]
+    _check_dim(dim)
+    _check("b", b, (B, rb, dim), torch.int8, dev)
+    if a.dtype != torch.int8 or a.device != dev:
+        raise TypeError("yolo_hip.track: a must be int8 on b's device")
+    if ra > 0 and nblocks > 0 and (a.stride(2) != 1 or a.stride(1) != dim or (nblocks > 1 and a.stride(0) < ra * dim)):
+        raise ValueError("yolo_hip.track: the blocks of a must be contiguous and must not overlap")
+    stride = a.stride(0) if nblocks > 1 else ra * dim
+    if a_index is not None:
+        _check("a_index", a_index, (B,), torch.int32, dev)
+    if out is None:
+        out = torch.empty((B, ra, rb), dtype=torch.int32, device=dev)
+    else:
+        _check("out", out, (B, ra, rb), torch.int32, dev)
+    L = lib()
+    args = (_ptr(a), stride, nblocks, _ptr(a_index), _ptr(b), B, ra, rb, dim, _ptr(out))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            check(L.yh_embed_similarity(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  "embed_similarity")
+    elif dev.type == "cpu":
+        check(L.yh_embed_similarity_host(*args, int(threads)), "embed_similarity_host")
+    else:
+        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+    return out
 
 
 class Tracker:
@@ -168,11 +339,18 @@ class Tracker:
     clears that). A Tracker is constructed and reset on the current stream; submit() orders the
     pipeline's work after it.
 
+    Re-identification. With reid_dim (the feature length) the tracker is `track_reid`'s: update()
+    also takes embed, feat_counts and embed_total (see `track_reid`; reid_cos and reid_iou are its
+    thresholds), the state carries a feature per track, and the tracker owns the workspace, sized
+    at the first call and again when the batch shape grows. `feature_counts` says which rows to cut
+    and embed. Without reid_dim a Tracker is the plain IoU tracker and takes no embeddings.
+
     Nothing here reads a device value on the host. Outputs are allocated per call on the stream
     the call runs on (DetectPipeline marks its `extra` for the caller's stream)."""
 
     def __init__(self, streams, device, max_tracks=256, max_out=None, track_high=0.25, track_low=0.1, track_new=0.25,
-                 iou_first=0.2, iou_second=0.5, iou_tentative=0.3, max_age=30, class_aware=True):
+                 iou_first=0.2, iou_second=0.5, iou_tentative=0.3, max_age=30, class_aware=True, reid_dim=None,
+                 reid_cos=0.5, reid_iou=0.5):
         self.device = torch.device(device)
         self.max_tracks = int(max_tracks)
         self.max_out = None if max_out is None else int(max_out)
@@ -182,7 +360,10 @@ class Tracker:
             raise ValueError("yolo_hip.Tracker: max_age must be >= 0")
         self.params = params(track_high, track_low, track_new, iou_first, iou_second, iou_tentative, max_age,
                              class_aware)
-        self.state = track_state(streams, self.max_tracks, self.device)
+        self.reid_dim = None if reid_dim is None else _check_dim(reid_dim)
+        self.reid_cos, self.reid_iou = float(reid_cos), float(reid_iou)
+        self._workspace = None
+        self.state = track_state(streams, self.max_tracks, self.device, self.reid_dim)
         self._post_stream = None
 
     @property
@@ -193,12 +374,27 @@ class Tracker:
         if streams is None or int(streams) == self.streams:
             self.state.zero_()
         else:
-            self.state = track_state(streams, self.max_tracks, self.device)
+            self.state = track_state(streams, self.max_tracks, self.device, self.reid_dim)
         self._post_stream = None
 
-    def update(self, dets, counts=None, stream_ids=None, threads=0):
+    def feature_counts(self, dets, counts):
+        """(B,) int32: per batch row the number of leading rows with score >= track_high, clamped to
+        the counts - the rows the first association and the births look at, hence the only rows whose
+        feature is ever read. Cut and embed these (`crop_rois(..., counts=feature_counts)`) and
+        pass the result to update() as feat_counts. Counting the leading rows is valid because
+        `nms` (yh_nms) and `merge` (yh_merge) emit the rows of a frame by descending score, so the
+        rows at or above the threshold are a prefix. Torch ops on the device; nothing is read on
+        the host."""
+        md = dets.shape[1]
+        live = torch.arange(md, device=dets.device).unsqueeze(0) < counts.clamp(0, md).unsqueeze(1)
+        high = (dets[:, :, 4] >= self.params.track_high) & live      # NaN padding compares false
+        return torch.cumprod(high.to(torch.int32), dim=1).sum(dim=1).to(torch.int32)
+
+    def update(self, dets, counts=None, stream_ids=None, threads=0, embed=None, feat_counts=None, embed_total=None):
         if counts is None:                       # a Detections
             dets, counts = dets.dets, dets.counts
+        if self.reid_dim is None and (embed is not None or feat_counts is not None or embed_total is not None):
+            raise ValueError("yolo_hip.Tracker: embeddings need a Tracker made with reid_dim")
         if stream_ids is not None and not isinstance(stream_ids, torch.Tensor):
             host = [int(v) for v in stream_ids]
             if len(set(host)) != len(host):
@@ -208,8 +404,16 @@ class Tracker:
             stream_ids = torch.tensor(host, dtype=torch.int32).to(self.device, non_blocking=True)
         elif stream_ids is None and isinstance(dets, torch.Tensor) and dets.dim() == 3 and dets.shape[0] > self.streams:
             raise ValueError(f"yolo_hip.Tracker: a batch of {dets.shape[0]} rows for {self.streams} streams")
-        return track(dets, counts, self.state, self.params, stream_ids=stream_ids, max_out=self.max_out,
-                     threads=threads)
+        if self.reid_dim is None:
+            return track(dets, counts, self.state, self.params, stream_ids=stream_ids, max_out=self.max_out,
+                         threads=threads)
+        from ._lib import lib
+        need = lib().yh_track_reid_workspace_bytes(dets.shape[0], dets.shape[1], self.max_tracks, self.reid_dim)
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        return track_reid(dets, counts, self.state, embed=embed, feat_counts=feat_counts, embed_total=embed_total,
+                          dim=self.reid_dim, reid_cos=self.reid_cos, reid_iou=self.reid_iou, p=self.params,
+                          stream_ids=stream_ids, max_out=self.max_out, workspace=self._workspace, threads=threads)
 
     def post(self, dets, counts):
         if self.device.type == "cuda":
