@@ -59,6 +59,12 @@ def test_nms_workspace_bytes():
     mask = al(ents + 2 * 3 * 4096 * 16)
     assert lib.yh_nms_workspace_bytes(2, 80, 8400) == mask + 2 * 64 * 64 * 65 // 2 * 8
     assert lib.yh_nms_workspace_bytes(0, 80, 8400) == 0
+    # the values the library returned before nms.hip became the layout's one owner
+    assert lib.yh_nms_workspace_bytes(1, 80, 8400) == 1303040
+    assert lib.yh_nms_workspace_bytes(3, 80, 8400) == 3908096
+    assert lib.yh_nms_workspace_bytes(32, 80, 8400) == 41683200
+    for bad in ((-1, 80, 8400), (2, 0, 8400), (2, 80, -5)):
+        assert lib.yh_nms_workspace_bytes(*bad) == 0
 
 
 def test_nms_rejects_bad_arguments_without_touching_the_device():

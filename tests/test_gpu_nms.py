@@ -142,21 +142,46 @@ def test_negative_iou_threshold_vs_oracle(gpu, iou):
     _assert_same(_gpu_nms(torch.from_numpy(y), gpu, iou_threshold=iou), want)
 
 
-@pytest.mark.parametrize("scores", ["spread", "tied"])
+@pytest.mark.parametrize("scores", ["spread", "tied", "spread_then_tied"])
 def test_few_kept_long_continuation_vs_oracle(gpu, scores):
     """Boxes of each class piled on one spot: an image keeps about one box per class of 67 k
     candidates, so NMS runs later batches until max_nms candidates are processed (the C5
     pattern). 'spread': scores over many bins (the fast path's compact list); 'tied': one score
-    for every pair (a single bin past 4096 keys: the radix-select path and its list)."""
-    rng = np.random.default_rng(21)
-    B, A, nc = 2, 8400, 8
+    for every pair (a single bin past 4096 keys: the radix-select path and its list).
+
+    'spread_then_tied': a fast later batch followed by the switch to the radix path. Of 8400
+    pairs per image 1500 have scores spread over 101 bins (at most 32 per bin) and 6900 share one
+    score: a first batch of about 970 keys, one fast later batch of the about 530 spread keys
+    left, then the tied bin (past 4096 keys) in two radix batches. Anchors 7, 107, .., 1007 are
+    small boxes apart from the pile and from each other, so tied entries are kept (in tie order)
+    and both the later batches' results and the max_nms cut inside the tied bin show in the
+    output: the oracle keeps [96, 96], [40, 40] and [59, 62] rows per image for the three
+    settings, of which 74 / 78, 18 / 22 and 37 / 44 carry the tied score."""
+    if scores == "spread_then_tied":
+        rng = np.random.default_rng(23)
+        B, A, nc = 2, 1050, 8   # A: not a multiple of 8
+    else:
+        rng = np.random.default_rng(21)
+        B, A, nc = 2, 8400, 8
     y = np.empty((B, 4 + nc, A), np.float32)
     y[:, 0:2] = 320.0 + rng.uniform(-2, 2, size=(B, 2, A))
     y[:, 2:4] = 100.0 + rng.uniform(-2, 2, size=(B, 2, A))
+    kws = (dict(), dict(max_nms=50000, max_det=5))
     if scores == "spread":
         y[:, 4:] = rng.uniform(0.01, 0.99, size=(B, nc, A)).astype(np.float32)
-    else:
+    elif scores == "tied":
         y[:, 4:] = 0.5
-    for kw in (dict(), dict(max_nms=50000, max_det=5)):
+    else:
+        k = np.arange(11)
+        lone = 7 + 100 * k
+        y[:, 0, lone] = 10.0 + 6.0 * k
+        y[:, 1, lone] = 600.0
+        y[:, 2:4, lone] = 4.0
+        y[:, 4:] = 0.25
+        for b in range(B):
+            idx = rng.permutation(nc * A)[:1500]
+            y[b, 4:].reshape(-1)[idx] = rng.uniform(0.6, 0.99, 1500)
+        kws = (dict(max_det=300, max_nms=30000), dict(max_det=40, max_nms=30000), dict(max_det=300, max_nms=5000))
+    for kw in kws:
         want = onms.non_max_suppression(y, 0.001, 0.65, kw.get("max_det", 300), kw.get("max_nms", 30000))
         _assert_same(_gpu_nms(torch.from_numpy(y), gpu, **kw), want)

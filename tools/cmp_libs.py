@@ -1,5 +1,6 @@
-"""Two builds of the library on the same inputs: forward outputs bit for bit, and the host's view of
-the net (conv list, every op's description, label, class, bytes, flops and kernel, the launch units).
+"""Two builds of the library on the same inputs: forward outputs bit for bit, the NMS of each (kept
+rows and counts, bit for bit), and the host's view of the net (conv list, every op's description,
+label, class, bytes, flops and kernel, the launch units).
 usage: python tools/cmp_libs.py <libA> <libB> [i,j,..]   ('' = the in-tree library; i,j,..: indices
 into SETTINGS, default all)
 
@@ -46,7 +47,7 @@ def child(out):
     sys.path.insert(0, os.path.join(ROOT, "yolo-infer-pt_amd"))
     import torch
     from yolo_hip import synth
-    from yolo_hip.engine import Engine
+    from yolo_hip.engine import Engine, nms
     from nets import nn
     res = {}
     for v, dt, b, sz in CASES:
@@ -60,8 +61,13 @@ def child(out):
         eng.load_module(model)
         x = synth.synth_scenes(b, sz, sz, seed=34).to(dev, dtype)
         y = eng.forward(x)
+        dets, counts = nms(y)
         torch.cuda.synchronize()
-        res[f"{v}_{dt}_{b}_{sz}"] = {"y": y.cpu(), "listing": listing(eng, b, sz, sz)}
+        dets = dets.cpu()
+        for i, c in enumerate(counts.tolist()):
+            dets[i, c:] = 0   # rows past the count are not written
+        res[f"{v}_{dt}_{b}_{sz}"] = {"y": y.cpu(), "dets": dets, "counts": counts.cpu(),
+                                     "listing": listing(eng, b, sz, sz)}
     torch.save(res, out)
 
 
@@ -90,9 +96,11 @@ def main():
             a, b = outs[0][key], outs[1][key]
             same = torch.equal(a["y"], b["y"])
             diff = [f for f in a["listing"] if a["listing"][f] != b["listing"][f]]
-            bad += (not same) + bool(diff)
+            same_nms = torch.equal(a["counts"], b["counts"]) and torch.equal(a["dets"], b["dets"])
+            bad += (not same) + bool(diff) + (not same_nms)
             la = a["listing"]
             print(" ", key, "bit-identical" if same else f"DIFFER max {(a['y'].float() - b['y'].float()).abs().max().item()}",
+                  "|", f"nms {a['counts'].tolist()} kept:", "bit-identical" if same_nms else "DIFFER",
                   "|", f"{len(la['convs'])} convs, {len(la['ops'])} ops, {len(la['units'])} units:",
                   "listings equal" if not diff else f"LISTINGS DIFFER in {diff}", flush=True)
     sys.exit(1 if bad else 0)

@@ -52,10 +52,10 @@ def main():
     torch.cuda.synchronize()
     lib().yh_debug_nms_trace(None)
     t = tr.cpu()
-    # marks: 0-3 nms_prep (start, start, gathered keys loaded, sorted + decoded), 4-6 nms_finish
-    # (start, first batch resolved, end); 3 -> 4 is nms_mask plus the launch gaps
-    ph = ["-", "load batch", "sort+decode", "mask(+gaps)", "resolve", "outputs+rest"]
-    d = (t[:, 1:7] - t[:, 0:6]).double() * 10.0  # 100 MHz ticks -> ns
+    # the slots are csrc/nms.hip's TraceSlot table; marks 0, 2, 3 are nms_prep's, 4-6 nms_finish's
+    ph = ["load batch", "sort+decode", "mask(+gaps)", "resolve", "outputs+rest"]
+    marks = t[:, [0, 2, 3, 4, 5, 6]]
+    d = (marks[:, 1:] - marks[:, :-1]).double() * 10.0  # 100 MHz ticks -> ns
     print("per-image phase us (mean / max):")
     for i, name in enumerate(ph):
         print(f"  {name:16s} {d[:, i].mean().item() / 1e3:8.2f} {d[:, i].max().item() / 1e3:8.2f}")

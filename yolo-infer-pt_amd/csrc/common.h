@@ -177,14 +177,18 @@ struct DecodeArgs {
 };
 
 // NMS (utils/util.py:123-169)
+constexpr int NMS_MAX_DET = 1024;    // most rows an image keeps (the kept set lives in LDS)
+constexpr int NMS_PAIR_BITS = 26;    // anchors * classes < 2^26 (the pair index in a sort key's low bits)
 struct NmsArgs {
     const void* y; int B, A, nc;
     float conf;          // threshold, already rounded to the input dtype
     float iou;           // largest float <= iou threshold (so ovr > iou  <=>  ovr > thr)
     float max_wh;
     int max_det, max_nms;
+    // counts, hist, state, gkeys, ents and mask are the workspace (nms_workspace_bytes), filled
+    // by nms_workspace_bind: nms.hip owns the layout
     int* counts;               // [B] candidate counts (zeroed by nms_zero)
-    unsigned* hist;            // [B][2048] coarse score-bin histogram (zeroed by the launcher)
+    unsigned* hist;            // [B][2048] coarse score-bin histogram (zeroed by nms_zero)
     int bin_base;              // (fp32 bits >> 16) of the lowest bin
     float* dets; int* ndet;
     // first-batch scratch of the split greedy (nms.hip): per image a state record, the
@@ -194,10 +198,12 @@ struct NmsArgs {
     float* ents;                // [B][3][4096][4]: offset box, plain box, (area, score, class, -)
     unsigned long long* mask;   // [B][64 * 64 * 65 / 2] words
 #ifdef YH_ABLATION
-    unsigned long long* trace;  // diagnostic builds only: [B][16] phase timestamps (s_memrealtime)
-    int dbg;                    // diagnostic builds only: ablation bits (YH_NMS_DBG, nms.hip)
+    unsigned long long* trace;  // diagnostic builds only: [B][16] phase timestamps (nms.hip TraceSlot)
 #endif
 };
+// bytes of the workspace for a batch of B images; the six workspace pointers of a (a.B set) into base
+size_t nms_workspace_bytes(int B);
+void nms_workspace_bind(NmsArgs& a, void* base);
 
 // Fused cls branch of the detect head (nets/nn.py:244-252), one launch for all levels:
 //   DWConv 3x3 + SiLU -> Conv 1x1 + SiLU -> DWConv 3x3 + SiLU -> Conv 1x1 + SiLU

@@ -1,5 +1,4 @@
-// C ABI of the stages after the forward, none of which needs a handle: yh_nms (with its
-// workspace layout), yh_match, yh_merge, yh_track, yh_embed_quantize, yh_embed_similarity,
+// C ABI of the stages after the forward, none of which needs a handle: yh_nms, yh_match, yh_merge, yh_track, yh_embed_quantize, yh_embed_similarity,
 // yh_track_reid and their *_host twins.
 #include <algorithm>
 
@@ -12,33 +11,23 @@
 using yh::Fail;
 using yh::guarded;
 
-// NMS workspace: [counts B x i32][hist B x 2048 u32][state][gkeys][ents][mask], the split greedy's
-// first-batch scratch (yh::NmsArgs::state / gkeys / ents / mask), 256-byte aligned sections (no
-// per-candidate key list: the keys are made from the scores where they are needed, nms.hip
-// for_pairs)
 namespace {
-constexpr size_t NMS_STATE_B = 64, NMS_GK_B = 4096 * 8, NMS_ENTS_B = 3 * 4096 * 16, NMS_MASK_B = 64 * 64 * 65 / 2 * 8;
-size_t nms_al(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t nms_off_hist(int B) { return nms_al((size_t)B * 4); }
-size_t nms_off_state(int B) { return nms_al(nms_off_hist(B) + (size_t)B * 2048 * 4); }
-size_t nms_off_gk(int B) { return nms_al(nms_off_state(B) + (size_t)B * NMS_STATE_B); }
-size_t nms_off_ents(int B) { return nms_al(nms_off_gk(B) + (size_t)B * NMS_GK_B); }
-size_t nms_off_mask(int B) { return nms_al(nms_off_ents(B) + (size_t)B * NMS_ENTS_B); }
 // the *_check functions return the complaint, or null
 void checked(const char* bad) { yh::require(!bad, bad ? bad : ""); }
 }  // namespace
 
 extern "C" {
 
+// the layout is nms.hip's (yh::nms_workspace_bytes / nms_workspace_bind)
 size_t yh_nms_workspace_bytes(int batch, int num_classes, int anchors) {
     if (batch <= 0 || num_classes <= 0 || anchors <= 0) return 0;
-    return nms_off_mask(batch) + (size_t)batch * NMS_MASK_B;
+    return yh::nms_workspace_bytes(batch);
 }
 
 #ifdef YH_ABLATION
 // Diagnostic builds only (make EXTRA=-DYH_ABLATION; not in the ABI header):
 // yh_debug_nms_trace(buf) makes later yh_nms calls record per-image phase timestamps
-// into the device buffer buf ([batch][16] u64, s_memrealtime ticks at 100 MHz).
+// into the device buffer buf ([batch][16] u64, the slots of nms.hip's TraceSlot).
 static unsigned long long* nms_trace = nullptr;
 int yh_debug_nms_trace(void* device_buf) {
     nms_trace = (unsigned long long*)device_buf;
@@ -53,10 +42,11 @@ int yh_nms(int dtype, const void* y, int batch, int num_classes, int anchors, fl
         yh::require(y && dets && counts && workspace, "null argument");
         yh::require(dtype == YH_F32 || dtype == YH_F16 || dtype == YH_BF16, "bad dtype");
         yh::require(batch > 0 && anchors > 0 && num_classes > 0, "bad shape");
-        yh::require(max_det > 0 && max_det <= 1024, "max_det must be in [1, 1024]");
+        static_assert(yh::NMS_MAX_DET == 1024 && yh::NMS_PAIR_BITS == 26, "the two messages below name these limits");
+        yh::require(max_det > 0 && max_det <= yh::NMS_MAX_DET, "max_det must be in [1, 1024]");
         yh::require(max_nms > 0, "max_nms must be positive");
         yh::require(conf_threshold >= 0.0f, "conf_threshold must be >= 0");
-        yh::require((long long)anchors * num_classes < (1ll << 26), "anchors * classes exceeds 2^26");
+        yh::require((long long)anchors * num_classes < (1ll << yh::NMS_PAIR_BITS), "anchors * classes exceeds 2^26");
         yh::require(workspace_bytes >= yh_nms_workspace_bytes(batch, num_classes, anchors), "NMS workspace too small");
         yh::NmsArgs a{};
         a.y = y; a.B = batch; a.A = anchors; a.nc = num_classes;
@@ -72,15 +62,8 @@ int yh_nms(int dtype, const void* y, int batch, int num_classes, int anchors, fl
         a.max_nms = max_nms;
 #ifdef YH_ABLATION
         a.trace = nms_trace;
-        a.dbg = getenv("YH_NMS_DBG") ? atoi(getenv("YH_NMS_DBG")) : 0;
 #endif
-        char* ws = (char*)workspace;
-        a.counts = (int*)ws;
-        a.hist = (unsigned*)(ws + nms_off_hist(batch));
-        a.state = (unsigned long long*)(ws + nms_off_state(batch));
-        a.gkeys = (unsigned long long*)(ws + nms_off_gk(batch));
-        a.ents = (float*)(ws + nms_off_ents(batch));
-        a.mask = (unsigned long long*)(ws + nms_off_mask(batch));
+        yh::nms_workspace_bind(a, workspace);
         {   // lowest bin at the threshold (or 2047 bins below 1.0 for tiny thresholds)
             uint32_t cb;
             std::memcpy(&cb, &a.conf, 4);
