@@ -43,6 +43,10 @@
  *   yh_track_reid       no reference counterpart: yh_track with an appearance term in the first
  *                       association and a per-slot int8 feature gallery in the state
  *   yh_embed_quantize_host, yh_embed_similarity_host, yh_track_reid_host   the same in host memory
+ *   yh_gallery_search,
+ *   yh_gallery_enrol    no reference counterpart: the k best rows of a large int8 gallery per query
+ *                       on the int8 MFMA (identities across streams and time), and appending to it
+ *   yh_gallery_search_host, yh_gallery_enrol_host   the same in host memory
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -475,6 +479,77 @@ int yh_track_reid_host(const float* dets, const int* counts, int batch, int max_
                        float* out, int* ids, int* det_index, int* out_counts, const float* embed, int capacity,
                        int dim, const int* feat_counts, const int* embed_total, const yh_reid_params* rp,
                        void* workspace, size_t workspace_bytes, int threads);
+
+/* Identity search over a gallery of int8 features (no reference counterpart: the rules below are
+ * the specification; tests/_gallery_cases.py restates them in numpy). The gallery is a caller-owned
+ * database of yh_embed_quantize rows that outlives streams and tracks: yh_gallery_search returns
+ * the k best rows of each query without ever writing the (nq, n) score matrix, yh_gallery_enrol
+ * appends rows. dim follows the rule above (dim % 64 == 0, 64 <= dim <= YH_REID_MAX_DIM).
+ *
+ * yh_gallery_search
+ *   gallery:   (capacity, dim) int8, row-major; capacity <= YH_GALLERY_MAX_CAPACITY
+ *   labels:    (capacity) int32, or NULL
+ *   size:      (1) int32, or NULL
+ *   q:         (nq, dim) int8
+ *   nq_count:  (1) int32, or NULL
+ *   k:         1 .. YH_GALLERY_MAX_K
+ *   scores, index: (nq, k) int32
+ *   workspace: caller-owned, yh_gallery_workspace_bytes(capacity, nq, k, chunk_rows) bytes; its
+ *              contents mean nothing between calls
+ * n = clamp(*size, 0, capacity), or capacity when size is NULL. m = clamp(*nq_count, 0, nq), or nq
+ * when nq_count is NULL. Row g is a candidate of query i iff g < n and (labels == NULL or
+ * labels[g] >= 0). Its score is the exact int32 dot product of the two rows; any int8 value is
+ * legal, -128 included. The candidates of a query are ordered by score descending, then g
+ * ascending, and the first k are written: scores[i][j], index[i][j] = g. Positions beyond the
+ * number of candidates get score INT32_MIN and index -1. A query row i >= m, or one whose bytes
+ * are all zero ("no feature"), has no candidates. Every element of scores and index is written
+ * exactly once; nothing else is written outside the workspace. Rows at or beyond n never
+ * influence a result (the device does not read them).
+ *
+ * chunk_rows: 0, or a positive multiple of 64. The gallery is cut into chunks of that many rows
+ * (0: the library chooses, as a function of capacity and nq), each chunk is searched on its own
+ * and the chunks' lists are merged. The result does not depend on it; it exists so that a gallery
+ * of a few hundred rows exercises many chunks and the merge. The workspace holds k candidates of
+ * 8 bytes per chunk and query, rounded up to 256 bytes: it never grows with capacity x nq.
+ *
+ * yh_gallery_enrol appends query rows to the gallery without a read-back.
+ *   gallery, labels: as above, written; both required when capacity > 0
+ *   size:       (1) int32, read and written, required
+ *   take:       (nq) int32, or NULL (every row)
+ *   labels_in:  (nq) int32, or NULL
+ *   next_label: (1) int32, read and written; required when labels_in is NULL, untouched otherwise
+ *   rows_out:   (nq) int32
+ * With n = clamp(*size, 0, capacity) and m as above, the query rows are walked in ascending order.
+ * Row i is enrolled iff i < m, (take == NULL or take[i] != 0), q_i has a non-zero byte and n <
+ * capacity. Enrolling copies the dim bytes of q_i to gallery row n, sets labels[n] = labels_in ?
+ * labels_in[i] : (*next_label)++, writes rows_out[i] = n and increments n. Every other rows_out[i]
+ * is -1. At the end *size = n. q must not overlap the gallery.
+ *
+ * On the device both calls are asynchronous on `stream`, allocate nothing, never synchronise and
+ * use no atomics; every pointer is device memory, and gallery, q and workspace must be 16-byte
+ * aligned. The search is the gfx950 int8 MFMA (v_mfma_i32_32x32x32_i8) with the queries in LDS
+ * and the running k best of every query on chip, then a merge of the chunks; the enrolment is one
+ * launch (a workgroup prefix sum over the flags, then the copy). The *_host twins give the same
+ * bytes; the search splits the queries over `threads` (<= 0: every hardware thread).
+ * YH_EINVAL (message in yh_last_error()), nothing launched: a bad dim, k outside [1,
+ * YH_GALLERY_MAX_K], a negative size, a capacity above YH_GALLERY_MAX_CAPACITY, a chunk_rows that
+ * is negative or no multiple of 64, a workspace that is NULL or too small, a NULL required
+ * pointer (none is required when there is nothing to read or write), a misaligned device operand. */
+#define YH_GALLERY_MAX_K 32
+#define YH_GALLERY_MAX_CAPACITY 2147482624   /* 2^31 - 1024 */
+size_t yh_gallery_workspace_bytes(int capacity, int nq, int k, int chunk_rows);
+int yh_gallery_search(const int8_t* gallery, const int32_t* labels, const int32_t* size, int capacity, int dim,
+                      const int8_t* q, int nq, const int32_t* nq_count, int k, int chunk_rows, int32_t* scores,
+                      int32_t* index, void* workspace, size_t workspace_bytes, void* stream);
+int yh_gallery_search_host(const int8_t* gallery, const int32_t* labels, const int32_t* size, int capacity, int dim,
+                           const int8_t* q, int nq, const int32_t* nq_count, int k, int chunk_rows, int32_t* scores,
+                           int32_t* index, void* workspace, size_t workspace_bytes, int threads);
+int yh_gallery_enrol(int8_t* gallery, int32_t* labels, int32_t* size, int capacity, int dim, const int8_t* q, int nq,
+                     const int32_t* nq_count, const int32_t* take, const int32_t* labels_in, int32_t* next_label,
+                     int32_t* rows_out, void* stream);
+int yh_gallery_enrol_host(int8_t* gallery, int32_t* labels, int32_t* size, int capacity, int dim, const int8_t* q,
+                          int nq, const int32_t* nq_count, const int32_t* take, const int32_t* labels_in,
+                          int32_t* next_label, int32_t* rows_out, int threads);
 
 /* Letterbox geometry of one image for a square canvas of `size` (dataset.py:95-103,
  * 292-313): resized height / width (int(h * r), int(w * r) with r = size / max(h, w);

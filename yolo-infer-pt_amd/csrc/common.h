@@ -465,5 +465,13 @@ int launch_embed_similarity(const int8_t* a, size_t a_block_stride, int nblocks,
 int launch_gallery_update(void* state, size_t stream_bytes, size_t gallery_offset, const int* stream_ids, int batch,
                           int max_tracks, int max_det, int dim, const int8_t* q, const int* flags, const int* code,
                           hipStream_t s);
+// gallery.hip: yh_gallery_search (the chunks' k best into the workspace, then their merge) and
+// yh_gallery_enrol; the chunking and the workspace layout are csrc/gallery_host.h's
+int launch_gallery_search(const int8_t* gallery, const int* labels, const int* size, int capacity, int dim,
+                          const int8_t* q, int nq, const int* nq_count, int k, int chunk_rows, int32_t* scores,
+                          int32_t* index, void* workspace, hipStream_t s);
+int launch_gallery_enrol(int8_t* gallery, int* labels, int* size, int capacity, int dim, const int8_t* q, int nq,
+                         const int* nq_count, const int* take, const int* labels_in, int* next_label, int* rows_out,
+                         hipStream_t s);
 
 }  // namespace yh

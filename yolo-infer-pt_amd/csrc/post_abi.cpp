@@ -1,8 +1,9 @@
 // C ABI of the stages after the forward, none of which needs a handle: yh_nms, yh_match, yh_merge, yh_track, yh_embed_quantize, yh_embed_similarity,
-// yh_track_reid and their *_host twins.
+// yh_track_reid, yh_gallery_search, yh_gallery_enrol and their *_host twins.
 #include <algorithm>
 
 #include "common.h"
+#include "gallery_host.h"
 #include "host_util.h"
 #include "match_host.h"
 #include "merge_host.h"
@@ -253,6 +254,60 @@ int yh_track_reid_host(const float* dets, const int* counts, int batch, int max_
         const yh_track_reid_args ra{embed, capacity, dim, feat_counts, embed_total, *rp, workspace};
         yh_track_host_run(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
                           det_index, out_counts, threads, &ra);
+    });
+}
+
+size_t yh_gallery_workspace_bytes(int capacity, int nq, int k, int chunk_rows) {
+    if (capacity < 0 || capacity > YH_GALLERY_MAX_CAPACITY || nq < 0 || k < 1 || k > YH_GALLERY_MAX_K ||
+        chunk_rows < 0 || chunk_rows % 64)
+        return 0;
+    return yh_gal_ws_bytes(capacity, nq, k, chunk_rows);
+}
+
+int yh_gallery_search(const int8_t* gallery, const int32_t* labels, const int32_t* size, int capacity, int dim,
+                      const int8_t* q, int nq, const int32_t* nq_count, int k, int chunk_rows, int32_t* scores,
+                      int32_t* index, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        checked(yh_gallery_search_check(gallery, capacity, dim, q, nq, k, chunk_rows, scores, index, workspace,
+                                        workspace_bytes));
+        yh::require(((uintptr_t)gallery | (uintptr_t)q | (uintptr_t)workspace) % 16 == 0,
+                    "gallery, q and workspace must be 16-byte aligned on the device");
+        const int rc = yh::launch_gallery_search(gallery, labels, size, capacity, dim, q, nq, nq_count, k, chunk_rows,
+                                                 scores, index, workspace, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("gallery_search launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_gallery_search_host(const int8_t* gallery, const int32_t* labels, const int32_t* size, int capacity, int dim,
+                           const int8_t* q, int nq, const int32_t* nq_count, int k, int chunk_rows, int32_t* scores,
+                           int32_t* index, void* workspace, size_t workspace_bytes, int threads) {
+    return guarded([&] {
+        checked(yh_gallery_search_check(gallery, capacity, dim, q, nq, k, chunk_rows, scores, index, workspace,
+                                        workspace_bytes));
+        yh_gallery_search_host_run(gallery, labels, size, capacity, dim, q, nq, nq_count, k, scores, index, threads);
+    });
+}
+
+int yh_gallery_enrol(int8_t* gallery, int32_t* labels, int32_t* size, int capacity, int dim, const int8_t* q, int nq,
+                     const int32_t* nq_count, const int32_t* take, const int32_t* labels_in, int32_t* next_label,
+                     int32_t* rows_out, void* stream) {
+    return guarded([&] {
+        checked(yh_gallery_enrol_check(gallery, labels, size, capacity, dim, q, nq, labels_in, next_label, rows_out));
+        yh::require(((uintptr_t)gallery | (uintptr_t)q) % 16 == 0, "gallery and q must be 16-byte aligned on the device");
+        const int rc = yh::launch_gallery_enrol(gallery, labels, size, capacity, dim, q, nq, nq_count, take, labels_in,
+                                                next_label, rows_out, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("gallery_enrol launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_gallery_enrol_host(int8_t* gallery, int32_t* labels, int32_t* size, int capacity, int dim, const int8_t* q,
+                          int nq, const int32_t* nq_count, const int32_t* take, const int32_t* labels_in,
+                          int32_t* next_label, int32_t* rows_out, int threads) {
+    (void)threads;   // one walk: a row's place depends on every row before it
+    return guarded([&] {
+        checked(yh_gallery_enrol_check(gallery, labels, size, capacity, dim, q, nq, labels_in, next_label, rows_out));
+        yh_gallery_enrol_host_run(gallery, labels, size, capacity, dim, q, nq, nq_count, take, labels_in, next_label,
+                                  rows_out);
     });
 }
 

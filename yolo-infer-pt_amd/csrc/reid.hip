@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "mfma_i8.h"
 #include "track_host.h"
 #include "yolo_hip.h"
 
@@ -158,13 +159,6 @@ __global__ __launch_bounds__(QUANT_T) void scatter_kernel(const float* __restric
     if (tid == 0) flags[job] = has ? (nz ? 3 : 1) : 0;
 }
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ i32x4 load16(const int8_t* p, bool ok) {
-    return ok ? *reinterpret_cast<const i32x4*>(p) : i32x4{0, 0, 0, 0};
-}
-
 // the lane's 16 results of a 32 x 32 tile at (m0, n0) of out (ra, rb)
 __device__ __forceinline__ void store_tile(int32_t* __restrict__ out, const i32x16& c, int m0, int n0, int ra, int rb,
                                            int r, int h) {
@@ -172,7 +166,7 @@ __device__ __forceinline__ void store_tile(int32_t* __restrict__ out, const i32x
     if (n >= rb) return;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-        const int m = m0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        const int m = m0 + tile_row(reg, h);
         if (m < ra) out[(size_t)m * rb + n] = c[reg];
     }
 }
@@ -189,7 +183,7 @@ __device__ __forceinline__ void store_tile_t(int32_t* __restrict__ out_t, const 
     if (n >= rb) return;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {   // registers 4 g .. 4 g + 3 are the rows m .. m + 3
-        const int m = m0 + 8 * g + 4 * h;
+        const int m = m0 + tile_row(4 * g, h);
         int32_t* o = out_t + (size_t)n * ra + m;
         if (m + 3 < ra) {
             *reinterpret_cast<i32x4u*>(o) = i32x4u{c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]};

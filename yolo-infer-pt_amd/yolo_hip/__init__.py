@@ -10,7 +10,9 @@ those frames for a second-stage model (`Crops`);
 `Tracker` (yolo_hip.track) gives the detections of video streams identities across frames
 (`track`, `track_state`, `Tracks`), with re-identification by appearance when it is given
 embeddings (`track_reid`, `embed_quantize`, `embed_similarity`); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
-those crops (`Classified`: class, confidence and embedding per detection). The drop-in module API lives in `nets.nn` / `utils.util`.
+those crops (`Classified`: class, confidence and embedding per detection); `Gallery` (yolo_hip.gallery)
+turns those embeddings into identities across streams and time (`gallery_search`, `gallery_enrol`,
+`gallery_workspace`: the k best rows of a large int8 gallery per query on the int8 MFMA). The drop-in module API lives in `nets.nn` / `utils.util`.
 """
 from .variants import VARIANTS, Variant, lookup  # noqa: F401
 
@@ -41,4 +43,7 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module(".track", __name__)
         return mod if name == "track" else getattr(mod, name)
+    if name in ("Gallery", "gallery_search", "gallery_enrol", "gallery_workspace"):
+        from . import gallery
+        return getattr(gallery, name)
     raise AttributeError(name)

@@ -53,10 +53,10 @@ class ReidParams(ctypes.Structure):
     _fields_ = [("cos_min", ctypes.c_float), ("iou_min", ctypes.c_float)]
 
 
-def _check_dim(dim):
+def _check_dim(dim, who="yolo_hip.track"):
     dim = int(dim)
     if dim % 64 or not 64 <= dim <= REID_MAX_DIM:
-        raise ValueError(f"yolo_hip.track: the feature length must be a multiple of 64 in [64, {REID_MAX_DIM}], got {dim}")
+        raise ValueError(f"{who}: the feature length must be a multiple of 64 in [64, {REID_MAX_DIM}], got {dim}")
     return dim
 
 
@@ -92,18 +92,18 @@ class Tracks(NamedTuple):
         return [(self.dets[i, :k], self.ids[i, :k], self.det_index[i, :k]) for i, k in enumerate(self.counts.tolist())]
 
 
-def _check(name, t, shape, dtype, device):
+def _check(name, t, shape, dtype, device, who="yolo_hip.track"):
     if not isinstance(t, torch.Tensor):
-        raise TypeError(f"yolo_hip.track: {name} must be a tensor")
+        raise TypeError(f"{who}: {name} must be a tensor")
     if t.dtype != dtype:
-        raise TypeError(f"yolo_hip.track: {name} must be {dtype}, got {t.dtype}")
+        raise TypeError(f"{who}: {name} must be {dtype}, got {t.dtype}")
     if t.device != device:
-        raise ValueError(f"yolo_hip.track: {name} is on {t.device}, expected {device}")
+        raise ValueError(f"{who}: {name} is on {t.device}, expected {device}")
     if len(shape) != t.dim() or any(w is not None and w != g for w, g in zip(shape, t.shape)):
         want = tuple("*" if w is None else w for w in shape)
-        raise ValueError(f"yolo_hip.track: {name} has shape {tuple(t.shape)}, expected {want}")
+        raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected {want}")
     if not t.is_contiguous():
-        raise ValueError(f"yolo_hip.track: {name} must be contiguous")
+        raise ValueError(f"{who}: {name} must be contiguous")
 
 
 def _ptr(t):
