@@ -4,10 +4,14 @@ The drop-in's CPU device path (utils.util.non_max_suppression on a CPU tensor,
 main.py:20) runs this C++ implementation; the oracle is only the checker. Bar:
 bit-exact kept rows and counts, as for the device kernel (tests/test_gpu_nms.py).
 """
+import os
+import re
+
 import numpy as np
 import pytest
 import torch
 
+import _nms_cases as cases
 from _util import golden_name
 from conftest import load_golden
 from oracle import nms as onms
@@ -88,12 +92,42 @@ def test_thread_count_does_not_change_results():
 def test_negative_iou_threshold_vs_oracle(iou):
     """iou_threshold < 0: disjoint pairs (IoU 0) suppress too, across classes; zero-area boxes
     (NaN IoU) never do."""
-    rng = np.random.default_rng(11)
-    B, A, nc = 2, 900, 80
-    y = np.empty((B, 4 + nc, A), np.float32)
-    y[:, 0:2] = rng.uniform(0, 640, size=(B, 2, A))
-    y[:, 2:4] = rng.uniform(8, 60, size=(B, 2, A))
-    y[:, 2:4, ::50] = 0.0
-    y[:, 4:] = (1 / (1 + np.exp(-rng.normal(-5, 2.5, size=(B, nc, A))))).astype(np.float32)
+    y = cases.negative_iou()
     _assert_same(_host_nms(torch.from_numpy(y), iou_threshold=iou),
                  onms.non_max_suppression(y, 0.001, iou, 300, 30000))
+
+
+# ---------------------------------------------------------------- the case list (tests/_nms_cases.py)
+def test_selection_constants_match_the_kernel():
+    """The census restates five constants of csrc/nms.hip; they are read from its constexpr lines."""
+    src = open(os.path.join(os.path.dirname(__file__), "..", "yolo-infer-pt_amd", "csrc", "nms.hip")).read()
+    for name in ("FIRST_TARGET", "LATER_TARGET", "CAP", "NB_LDS", "NBINS"):
+        m = re.search(r"^constexpr int %s = (\d+);" % name, src, re.M)
+        assert m, f"no constexpr int {name} in nms.hip"
+        assert int(m.group(1)) == getattr(cases, name), name
+    assert cases.LDS_ENTRIES == 19 * 64
+
+
+@pytest.mark.parametrize("name", cases.ALL)
+def test_case_takes_the_paths_it_is_named_for(name):
+    got = set().union(*cases.labels(name))
+    assert not cases.LABELS[name] - got, f"{name}: missing {sorted(cases.LABELS[name] - got)} in {sorted(got)}"
+
+
+def test_case_list_covers_every_path():
+    got = set().union(*(lab for name in cases.ALL for lab in cases.labels(name)))
+    missing = sorted(cases.REQUIRED - got) + [p for p in cases.REQUIRED_PREFIXES if not any(g.startswith(p) for g in got)]
+    assert not missing, f"no case reaches {missing}"
+    # a radix batch boundary inside the score digits and one inside a fully tied bin
+    assert "radix_distinct_scores" in cases.labels("radix_first")[0]
+    assert "radix_distinct_scores" not in cases.labels("few_kept_tied")[0]
+    # and the first two radix batches of radix_first (4096 keys each) end inside runs of equal scores
+    y = cases.case("radix_first")[0]
+    s = np.sort(y[0, 4:][y[0, 4:] > np.float32(0.001)])[::-1]
+    assert s[4095] == s[4096] and s[8191] == s[8192] and s[4096] != s[8191]
+
+
+@pytest.mark.parametrize("name", cases.ALL)
+def test_case_list_vs_oracle(name):
+    _, kw, _ = cases.case(name)
+    cases.assert_same(_host_nms(cases.tensor(name), **kw), cases.want(name), name)

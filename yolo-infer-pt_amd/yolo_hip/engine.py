@@ -304,7 +304,7 @@ def nms(outputs, confidence_threshold=0.001, iou_threshold=0.65, max_det=300, ma
         out=None, workspace=None):
     """On-device batched NMS of a (B, 4 + nc, A) cuda tensor -> (dets (B, max_det, 6) f32, counts (B,) i32).
 
-    out=(dets, counts) and workspace (uint8, >= nms_workspace_bytes) may be given to reuse buffers
+    out=(dets, counts) and workspace (uint8, >= nms_workspace_bytes), all contiguous, may be given to reuse buffers
     (yolo_hip.pipeline's result ring); otherwise they come from the caching allocator."""
     if not outputs.is_cuda:
         raise ValueError("yolo_hip.nms needs a cuda tensor")
@@ -314,8 +314,10 @@ def nms(outputs, confidence_threshold=0.001, iou_threshold=0.65, max_det=300, ma
     dev = y.device
     need = lib().yh_nms_workspace_bytes(B, nc, A)
     if workspace is not None:
-        if workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != dev:
-            raise ValueError(f"yolo_hip.nms: workspace must be a uint8 tensor of >= {need} bytes on {dev}")
+        # yh_nms writes the workspace (and counts, below) as dense memory: a strided view is refused
+        if (workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous()
+                or workspace.numel() * workspace.element_size() < need):
+            raise ValueError(f"yolo_hip.nms: workspace must be a contiguous uint8 tensor of >= {need} bytes on {dev}")
         ws = workspace
     else:
         ws = torch.empty(int(need), dtype=torch.uint8, device=dev)  # caching allocator: stream-safe reuse
@@ -323,14 +325,14 @@ def nms(outputs, confidence_threshold=0.001, iou_threshold=0.65, max_det=300, ma
         dets, counts = out
         if (tuple(dets.shape) != (B, max_det, 6) or dets.dtype != torch.float32 or tuple(counts.shape) != (B,)
                 or counts.dtype != torch.int32 or dets.device != dev or counts.device != dev
-                or not dets.is_contiguous()):
-            raise ValueError("yolo_hip.nms: out must be (dets (B, max_det, 6) f32, counts (B,) i32) on the device")
+                or not dets.is_contiguous() or not counts.is_contiguous()):
+            raise ValueError("yolo_hip.nms: out must be contiguous (dets (B, max_det, 6) f32, counts (B,) i32) on the device")
     else:
         dets = torch.empty((B, max_det, 6), dtype=torch.float32, device=dev)
         counts = torch.empty((B,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         check(lib().yh_nms(dtype_code(y.dtype), c_void_p(y.data_ptr()), B, nc, A, ctypes.c_float(confidence_threshold),
                            c_double(iou_threshold), int(max_det), int(max_nms), ctypes.c_float(max_wh),
-                           c_void_p(ws.data_ptr()), c_size_t(ws.numel()), c_void_p(dets.data_ptr()),
+                           c_void_p(ws.data_ptr()), c_size_t(ws.numel() * ws.element_size()), c_void_p(dets.data_ptr()),
                            c_void_p(counts.data_ptr()), _stream_ptr(dev)), "nms")
     return dets, counts
