@@ -17,14 +17,15 @@ NET := engine net_build net_weights net_forward net_launch net_debug
 HOSTHIP := post_abi nms_host
 # kernels; the NOFMA ones promise bit-exact arithmetic against host code: no FMA contraction
 KERNELS := conv sppf attn decode conv_mx conv_rw head c3k2 c3k pwchain cls
-KERNELS_NOFMA := preprocess nms match merge track reid gallery
+KERNELS_NOFMA := preprocess nms match merge track reid gallery assign
 # HIP-free translation units: plain C++, no device pass, no FMA contraction
-HOSTCXX := match_host merge_host track_host gallery_host
+HOSTCXX := match_host merge_host track_host gallery_host assign_host
 
 objs = $(patsubst %,$(OBJDIR)/%.o,$(1))
 OBJS := $(call objs,$(NET) $(HOSTHIP) $(KERNELS) $(KERNELS_NOFMA) $(HOSTCXX))
 HOST_H := $(SRC)/host_util.h $(SRC)/host_parallel.h $(SRC)/box_math.h \
-          $(SRC)/match_host.h $(SRC)/merge_host.h $(SRC)/track_host.h $(SRC)/gallery_host.h
+          $(SRC)/match_host.h $(SRC)/merge_host.h $(SRC)/track_host.h $(SRC)/gallery_host.h \
+          $(SRC)/assign_host.h
 
 all: $(OUT)
 
@@ -58,6 +59,11 @@ $(OBJDIR)/reid.o: $(SRC)/track_host.h $(SRC)/box_math.h
 $(call objs,reid gallery): $(SRC)/mfma_i8.h
 $(OBJDIR)/gallery.o: $(SRC)/gallery_host.h $(SRC)/box_math.h
 $(OBJDIR)/gallery_host.o: $(SRC)/track_host.h
+# the assignment solver: the kernel and the tracker's optimal instances share assign.h, the host
+# twins of both share assign_host.h (which also holds the weight arithmetic of all four)
+$(call objs,assign track): $(SRC)/assign.h $(SRC)/assign_host.h
+$(OBJDIR)/assign.o: $(SRC)/box_math.h
+$(OBJDIR)/track_host.o: $(SRC)/assign_host.h
 # reports its argument errors through host_util.h's guarded(); its host functions use the pool
 $(OBJDIR)/preprocess.o: $(SRC)/host_util.h $(SRC)/host_parallel.h
 

@@ -47,6 +47,12 @@
  *   yh_gallery_enrol    no reference counterpart: the k best rows of a large int8 gallery per query
  *                       on the int8 MFMA (identities across streams and time), and appending to it
  *   yh_gallery_search_host, yh_gallery_enrol_host   the same in host memory
+ *   yh_assign           no reference counterpart: batched maximum-weight assignment by shortest
+ *                       augmenting paths, one workgroup per problem
+ *   yh_track2,
+ *   yh_track_reid2      yh_track / yh_track_reid with that assignment in place of the greedy walk
+ *                       of the associations, on request (ByteTrack's lapjv step)
+ *   yh_assign_host, yh_track2_host, yh_track_reid2_host   the same in host memory
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -339,7 +345,8 @@ int yh_merge_host(const float* dets, const int* counts, int tiles, int max_det,
  *   3. assoc(slots, rows, thr): the candidate pairs have equal class (f32 ==; not tested when
  *      class_aware is 0), an intersection != 0 and iou = inter / ((area_t + area_d) - inter)
  *      >= thr; they are walked by iou descending, then slot, then row ascending, and a pair is
- *      taken when both sides are unmatched (greedy, not ByteTrack's lapjv). Three calls:
+ *      taken when both sides are unmatched (greedy; yh_track2 can solve the assignment instead, as
+ *      ByteTrack's lapjv does). Three calls:
  *      (status 2 or 3, high, iou_first); (status 2 still unmatched, low, iou_second);
  *      (status 1, high still unmatched, iou_tentative).
  *   4. a matched slot is updated with z = (centre, size) of its row: r = sq(0.05, wh4 of the
@@ -479,6 +486,100 @@ int yh_track_reid_host(const float* dets, const int* counts, int batch, int max_
                        float* out, int* ids, int* det_index, int* out_counts, const float* embed, int capacity,
                        int dim, const int* feat_counts, const int* embed_total, const yh_reid_params* rp,
                        void* workspace, size_t workspace_bytes, int threads);
+
+/* Batched linear assignment (no reference counterpart: the rules below are the specification;
+ * tests/_assign_cases.py restates them in numpy). Problem p has T slots and D rows and a weight
+ * matrix weights[p] (T, D) int32: 0 forbids the pair, 1 .. YH_ASSIGN_MAX_WEIGHT is its weight. A
+ * weight below 0 is read as 0 and one above YH_ASSIGN_MAX_WEIGHT as YH_ASSIGN_MAX_WEIGHT, so no
+ * input can overflow the arithmetic below. t_counts / d_counts: NULL, or (problems) int32 (device
+ * memory for yh_assign): only the slots below nt = min(max(t_counts[p], 0), T) and the rows below
+ * nd = min(max(d_counts[p], 0), D) take part, and weights outside that corner are never read.
+ *
+ * Output: row_of_slot (problems, T) int32, the row matched to each slot or -1, and its inverse
+ * slot_of_row (problems, D). Every byte of both is written; entries at or beyond nt / nd are -1.
+ *
+ * Result: a matching over the allowed pairs of maximum total weight. That is not a matching of
+ * maximum size (a pair is left out when taking it would cost more weight elsewhere), and a pair
+ * of weight 0 is never output. Several matchings can share the maximum; which one is returned is
+ * fixed by the algorithm, which is therefore normative: successive shortest augmenting paths
+ * (Jonker-Volgenant / the Hungarian method with duals) in integers, with M = YH_ASSIGN_MAX_WEIGHT.
+ *   - The columns are the nd rows ("real" columns) and, per slot, one private column only that
+ *     slot can use, which stands for staying unmatched. cost(t, d) = M - w for an allowed pair,
+ *     cost(t, private t) = M; forbidden pairs do not exist. Duals u[t] = 0, v[d] = 0 at the start;
+ *     a private column's dual stays 0.
+ *   - For root = 0 .. nt - 1 in this order, a Dijkstra search over the columns: dist[d] = infinity,
+ *     no column scanned; the slot i = root enters the tree at base = 0. Repeat:
+ *       a. the private column of i gets the distance base + M - u[i]; the nearest private column
+ *          so far is kept, the lower slot on equal distances;
+ *       b. every unscanned real column d with w(i, d) > 0 is relaxed: cand = base + (M - w) - u[i]
+ *          - v[d]; if cand < dist[d] then dist[d] = cand and pred[d] = i;
+ *       c. the next column is the unscanned real column of smallest dist, the lowest index on
+ *          equal distances, unless the nearest private column is strictly nearer (a real column
+ *          comes before a private one) or no real column has been reached: then the path ends at
+ *          that private column, total = its distance;
+ *       d. the chosen real column d is scanned. If it is free the path ends there, total =
+ *          dist[d]. Otherwise its slot enters the tree: i = slot_of_row[d], base = dist[d].
+ *   - The duals are updated: u[root] += total; for every scanned column d other than the end,
+ *     with delta = total - dist[d]: u[slot_of_row[d]] += delta, v[d] -= delta.
+ *   - Then the path is flipped from its end back to the root along pred. A slot whose path ends
+ *     at its private column is unmatched.
+ * All arithmetic is int32 and exact: a path is never longer than M (the root's private column),
+ * so a dual moves by at most M per root, and with at most YH_ASSIGN_MAX_SIZE roots every dual and
+ * every distance stays below (YH_ASSIGN_MAX_SIZE + 2) * M < 2^27. Because every choice above is a
+ * minimum under a total order, the result does not depend on how the scan over the columns is
+ * parallelised.
+ *
+ * yh_assign: device pointers, one workgroup per problem, asynchronous on `stream`, allocates
+ * nothing, never synchronises, no atomics. yh_assign_host: the same bytes for host pointers,
+ * problems in parallel over `threads` (<= 0: all hardware threads), synchronous.
+ * YH_EINVAL (message in yh_last_error()): T or D above YH_ASSIGN_MAX_SIZE, a negative size, a NULL
+ * required pointer (none is required when there is nothing to read or write). */
+#define YH_ASSIGN_MAX_WEIGHT (1 << 16)
+#define YH_ASSIGN_MAX_SIZE 1024
+int yh_assign(const int32_t* weights, int problems, int T, int D, const int32_t* t_counts,
+              const int32_t* d_counts, int32_t* row_of_slot, int32_t* slot_of_row, void* stream);
+int yh_assign_host(const int32_t* weights, int problems, int T, int D, const int32_t* t_counts,
+                   const int32_t* d_counts, int32_t* row_of_slot, int32_t* slot_of_row, int threads);
+
+/* yh_track and yh_track_reid with a choice of how an association picks among its candidate pairs.
+ * Arguments, state, outputs and errors are those of yh_track / yh_track_reid, plus ap (mode; set the
+ * reserved words to 0). A sequence may change the mode from frame to frame: the state
+ * layout is the same.
+ *   YH_ASSIGN_GREEDY   byte for byte yh_track / yh_track_reid (which are these functions in this
+ *                      mode): the sorted walk of step 3.
+ *   YH_ASSIGN_OPTIMAL  in each of the three assoc calls of step 3 (and in yh_track_reid's
+ *                      association 1) the candidate pairs and their sort value val are unchanged
+ *                      (for yh_track val is the iou, for yh_track_reid's association 1 the larger
+ *                      of iou and app when eligible), but instead of the walk the matching is
+ *                      yh_assign's on the weights w = 1 + (int)(val * 65535.0f) (one fp32
+ *                      multiply, a truncation, clamped to [1, YH_ASSIGN_MAX_WEIGHT]) for candidate
+ *                      pairs and 0 for all others, over the association's slots and rows in
+ *                      ascending order. It maximises the sum of val over the gated pairs (lapjv
+ *                      with a cost limit maximises the sum of val - thr). Steps 1, 2, 4, 5, 6 and
+ *                      the gallery update are untouched.
+ * YH_EINVAL as the plain functions, and: a NULL ap, an unknown mode. */
+#define YH_ASSIGN_GREEDY 0
+#define YH_ASSIGN_OPTIMAL 1
+typedef struct {
+    int mode;
+    int reserved[3];
+} yh_assign_params;
+int yh_track2(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+              void* state, int streams, int max_tracks, const yh_track_params* p, int max_out,
+              float* out, int* ids, int* det_index, int* out_counts, const yh_assign_params* ap, void* stream);
+int yh_track2_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+                   void* state, int streams, int max_tracks, const yh_track_params* p, int max_out,
+                   float* out, int* ids, int* det_index, int* out_counts, const yh_assign_params* ap, int threads);
+int yh_track_reid2(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+                   void* state, int streams, int max_tracks, const yh_track_params* p, int max_out,
+                   float* out, int* ids, int* det_index, int* out_counts, const float* embed, int capacity,
+                   int dim, const int* feat_counts, const int* embed_total, const yh_reid_params* rp,
+                   void* workspace, size_t workspace_bytes, const yh_assign_params* ap, void* stream);
+int yh_track_reid2_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+                        void* state, int streams, int max_tracks, const yh_track_params* p, int max_out,
+                        float* out, int* ids, int* det_index, int* out_counts, const float* embed, int capacity,
+                        int dim, const int* feat_counts, const int* embed_total, const yh_reid_params* rp,
+                        void* workspace, size_t workspace_bytes, const yh_assign_params* ap, int threads);
 
 /* Identity search over a gallery of int8 features (no reference counterpart: the rules below are
  * the specification; tests/_gallery_cases.py restates them in numpy). The gallery is a caller-owned

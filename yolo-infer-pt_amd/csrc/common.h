@@ -436,10 +436,11 @@ int launch_match(const float* dets, const int* counts, int batch, int max_det, c
 int launch_merge(const float* dets, const int* counts, int tiles, int max_det, const float* tile_xf,
                  const int* tile_offsets, const float* image_wh, int images, int max_tiles, double iou_threshold,
                  int max_out, float* out, int* out_counts, hipStream_t s);
-// track.hip: one frame of every stream of a batch through its track table (yh_track); p by value
+// track.hip: one frame of every stream of a batch through its track table (yh_track); p by value;
+// optimal: the associations solve an assignment instead of walking greedily (yh_track2)
 int launch_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
                  int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
-                 int* det_index, int* out_counts, hipStream_t s);
+                 int* det_index, int* out_counts, bool optimal, hipStream_t s);
 // the same with the appearance term (yh_track_reid): the state carries the galleries, the
 // workspace the rows' features, their flags and the similarities (csrc/track_host.h's layout)
 struct TrackReid {
@@ -454,7 +455,10 @@ struct TrackReid {
 };
 int launch_track_reid(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
                       int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
-                      int* det_index, int* out_counts, const TrackReid& rd, hipStream_t s);
+                      int* det_index, int* out_counts, const TrackReid& rd, bool optimal, hipStream_t s);
+// assign.hip: yh_assign, one wave per problem; the tracker's `optimal` instances above run the same solver
+int launch_assign(const int* weights, int problems, int T, int D, const int* t_counts, const int* d_counts,
+                  int* row_of_slot, int* slot_of_row, hipStream_t s);
 // reid.hip: yh_embed_quantize, the quantise-and-scatter of yh_track_reid, yh_embed_similarity
 int launch_embed_quantize(const float* e, int rows, int dim, const int* count, int8_t* q, hipStream_t s);
 int launch_embed_scatter(const float* embed, int capacity, int dim, const int* counts, const int* feat_counts,

@@ -1,8 +1,9 @@
 // C ABI of the stages after the forward, none of which needs a handle: yh_nms, yh_match, yh_merge, yh_track, yh_embed_quantize, yh_embed_similarity,
-// yh_track_reid, yh_gallery_search, yh_gallery_enrol and their *_host twins.
+// yh_track_reid, yh_gallery_search, yh_gallery_enrol, yh_assign, yh_track2, yh_track_reid2 and their *_host twins.
 #include <algorithm>
 
 #include "common.h"
+#include "assign_host.h"
 #include "gallery_host.h"
 #include "host_util.h"
 #include "match_host.h"
@@ -15,6 +16,8 @@ using yh::guarded;
 namespace {
 // the *_check functions return the complaint, or null
 void checked(const char* bad) { yh::require(!bad, bad ? bad : ""); }
+// what yh_track and yh_track_reid pass on to yh_track2 and yh_track_reid2
+const yh_assign_params kGreedy = {YH_ASSIGN_GREEDY, {0, 0, 0}};
 }  // namespace
 
 extern "C" {
@@ -128,26 +131,61 @@ size_t yh_track_state_bytes(int streams, int max_tracks) {
     return (size_t)streams * yh_track_stream_words(max_tracks) * 4;
 }
 
-int yh_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
-             int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids, int* det_index,
-             int* out_counts, void* stream) {
+int yh_track2(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+              int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids, int* det_index,
+              int* out_counts, const yh_assign_params* ap, void* stream) {
     return guarded([&] {
         checked(yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
                                det_index, out_counts));
+        checked(yh_assign_params_check(ap));
         const int rc = yh::launch_track(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, *p, max_out,
-                                        out, ids, det_index, out_counts, (hipStream_t)stream);
+                                        out, ids, det_index, out_counts, ap->mode == YH_ASSIGN_OPTIMAL,
+                                        (hipStream_t)stream);
         if (rc != 0) throw Fail(YH_EHIP, std::string("track launch failed: ") + hipGetErrorString((hipError_t)rc));
     });
+}
+
+int yh_track2_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                   int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
+                   int* det_index, int* out_counts, const yh_assign_params* ap, int threads) {
+    return guarded([&] {
+        checked(yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
+                               det_index, out_counts));
+        checked(yh_assign_params_check(ap));
+        yh_track_host_run(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
+                          det_index, out_counts, threads, nullptr, ap->mode);
+    });
+}
+
+int yh_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+             int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids, int* det_index,
+             int* out_counts, void* stream) {
+    return yh_track2(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
+                     det_index, out_counts, &kGreedy, stream);
 }
 
 int yh_track_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
                   int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
                   int* det_index, int* out_counts, int threads) {
+    return yh_track2_host(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
+                          det_index, out_counts, &kGreedy, threads);
+}
+
+int yh_assign(const int32_t* weights, int problems, int T, int D, const int32_t* t_counts, const int32_t* d_counts,
+              int32_t* row_of_slot, int32_t* slot_of_row, void* stream) {
     return guarded([&] {
-        checked(yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
-                               det_index, out_counts));
-        yh_track_host_run(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
-                          det_index, out_counts, threads);
+        checked(yh_assign_check(weights, problems, T, D, row_of_slot, slot_of_row));
+        const int rc = yh::launch_assign(weights, problems, T, D, t_counts, d_counts, row_of_slot, slot_of_row,
+                                         (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("assign launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_assign_host(const int32_t* weights, int problems, int T, int D, const int32_t* t_counts,
+                   const int32_t* d_counts, int32_t* row_of_slot, int32_t* slot_of_row, int threads) {
+    return guarded([&] {
+        checked(yh_assign_check(weights, problems, T, D, row_of_slot, slot_of_row));
+        yh_assign_host_run(weights, problems, T, D, t_counts, d_counts, row_of_slot, slot_of_row, threads);
     });
 }
 
@@ -196,12 +234,13 @@ size_t yh_track_reid_workspace_bytes(int batch, int max_det, int max_tracks, int
     return yh_reid_ws_bytes(batch, max_det, max_tracks, dim);
 }
 
-int yh_track_reid(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
-                  int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
-                  int* det_index, int* out_counts, const float* embed, int capacity, int dim, const int* feat_counts,
-                  const int* embed_total, const yh_reid_params* rp, void* workspace, size_t workspace_bytes,
-                  void* stream) {
+int yh_track_reid2(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                   int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
+                   int* det_index, int* out_counts, const float* embed, int capacity, int dim, const int* feat_counts,
+                   const int* embed_total, const yh_reid_params* rp, void* workspace, size_t workspace_bytes,
+                   const yh_assign_params* ap, void* stream) {
     return guarded([&] {
+        checked(yh_assign_params_check(ap));
         checked(yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
                                det_index, out_counts));
         checked(yh_track_reid_check(batch, max_det, max_tracks, capacity, dim, rp, workspace, workspace_bytes));
@@ -234,7 +273,7 @@ int yh_track_reid(const float* dets, const int* counts, int batch, int max_det, 
                                              const_cast<int*>(rd.sim), gnz, const_cast<int*>(rd.sim_t), s);
         if (rc == 0)
             rc = yh::launch_track_reid(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, *p, max_out,
-                                       out, ids, det_index, out_counts, rd, s);
+                                       out, ids, det_index, out_counts, rd, ap->mode == YH_ASSIGN_OPTIMAL, s);
         if (rc == 0)
             rc = yh::launch_gallery_update(state, stream_bytes, gallery_offset, stream_ids, batch, max_tracks, max_det,
                                            dim, rd.q, rd.flags, rd.code, s);
@@ -242,19 +281,40 @@ int yh_track_reid(const float* dets, const int* counts, int batch, int max_det, 
     });
 }
 
-int yh_track_reid_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
-                       int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
-                       int* det_index, int* out_counts, const float* embed, int capacity, int dim,
-                       const int* feat_counts, const int* embed_total, const yh_reid_params* rp, void* workspace,
-                       size_t workspace_bytes, int threads) {
+int yh_track_reid2_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
+                        void* state, int streams, int max_tracks, const yh_track_params* p, int max_out, float* out,
+                        int* ids, int* det_index, int* out_counts, const float* embed, int capacity, int dim,
+                        const int* feat_counts, const int* embed_total, const yh_reid_params* rp, void* workspace,
+                        size_t workspace_bytes, const yh_assign_params* ap, int threads) {
     return guarded([&] {
+        checked(yh_assign_params_check(ap));
         checked(yh_track_check(dets, counts, batch, max_det, state, streams, max_tracks, p, max_out, out, ids,
                                det_index, out_counts));
         checked(yh_track_reid_check(batch, max_det, max_tracks, capacity, dim, rp, workspace, workspace_bytes));
         const yh_track_reid_args ra{embed, capacity, dim, feat_counts, embed_total, *rp, workspace};
         yh_track_host_run(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
-                          det_index, out_counts, threads, &ra);
+                          det_index, out_counts, threads, &ra, ap->mode);
     });
+}
+
+int yh_track_reid(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                  int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
+                  int* det_index, int* out_counts, const float* embed, int capacity, int dim, const int* feat_counts,
+                  const int* embed_total, const yh_reid_params* rp, void* workspace, size_t workspace_bytes,
+                  void* stream) {
+    return yh_track_reid2(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
+                          det_index, out_counts, embed, capacity, dim, feat_counts, embed_total, rp, workspace,
+                          workspace_bytes, &kGreedy, stream);
+}
+
+int yh_track_reid_host(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
+                       int streams, int max_tracks, const yh_track_params* p, int max_out, float* out, int* ids,
+                       int* det_index, int* out_counts, const float* embed, int capacity, int dim,
+                       const int* feat_counts, const int* embed_total, const yh_reid_params* rp, void* workspace,
+                       size_t workspace_bytes, int threads) {
+    return yh_track_reid2_host(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out,
+                               ids, det_index, out_counts, embed, capacity, dim, feat_counts, embed_total, rp, workspace,
+                               workspace_bytes, &kGreedy, threads);
 }
 
 size_t yh_gallery_workspace_bytes(int capacity, int nq, int k, int chunk_rows) {

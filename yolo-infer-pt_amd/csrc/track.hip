@@ -41,10 +41,19 @@
 // of them in flight per lane. Which slots and rows have a feature comes from the workspace too (a
 // word more per slot and per row in LDS). The galleries are not touched here: the kernel leaves
 // each slot's row of this frame in the workspace for the gallery launch behind it.
+//
+// OPT (yh_track2 / yh_track_reid2 in YH_ASSIGN_OPTIMAL mode): a second instance of each, whose
+// associations keep the candidate pairs but choose among them with yh_assign's solver
+// (csrc/assign.h) instead of the rounds: the live slots and rows are compacted as above, wave 0
+// solves the assignment over the two lists - the weights come from the boxes in LDS (and sim) as
+// the solver asks for them, there is no slots x rows matrix here either - while the other waves
+// wait at the barrier behind it; then the slot owners note their rows. Three words more per row in
+// LDS (the solver's column links and duals). The greedy instances are compiled as before.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "assign.h"
 #include "common.h"
 #include "track_host.h"
 #include "yolo_hip.h"
@@ -58,12 +67,13 @@ constexpr int TRACK_WAVES = TRACK_T / 64;
 static_assert(YH_TRACK_MAX_TRACKS <= TRACK_T && YH_TRACK_MAX_DET <= TRACK_T, "a thread owns one slot and one row");
 
 // app: the appearance instance (yh_track_reid) keeps a word more per slot and per row
-constexpr size_t track_lds(int T, int D, bool app = false) {
-    return ((size_t)(app ? 10 : 9) * T + (size_t)(app ? 8 : 7) * D + 2 * TRACK_WAVES + 4) * 4;
+// opt: the assignment instance keeps the solver's three words per row (its per-slot words reuse sact and best)
+constexpr size_t track_lds(int T, int D, bool app = false, bool opt = false) {
+    return ((size_t)(app ? 10 : 9) * T + (size_t)((app ? 8 : 7) + (opt ? 3 : 0)) * D + 2 * TRACK_WAVES + 4) * 4;
 }
 // above the 64 KiB a workgroup gets by default at the caps: launch_track requests the size with the
 // attribute csrc/merge.hip uses (up to 160 KiB per workgroup on gfx950)
-static_assert(track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET, true) <= 160 * 1024, "LDS plan");
+static_assert(track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET, true, true) <= 160 * 1024, "LDS plan");
 
 struct Lds {
     float *sx1, *sy1, *sx2, *sy2, *scls;   // [T] slot box and class
@@ -73,6 +83,7 @@ struct Lds {
     int* wsum;                             // [2][TRACK_WAVES] prefix-sum wave totals
     int* ctl;                              // [0] last round that matched, [1] f, [2] ids handed out, [3] rows
     int *gnz, *qfl;                        // appearance only: [T] the gallery row is non-zero, [D] the row's flags
+    int *asor, *apred, *av;                // assignment only: [D] the solver's column -> slot, predecessor, dual
 };
 
 // One pair of an association: a candidate, and with which sort value? APP: the first association
@@ -250,9 +261,46 @@ __device__ void assoc(const Lds& L, bool slive, bool rlive, float thr, int class
     }
 }
 
+// assoc(T, D, thr) of the specification in YH_ASSIGN_OPTIMAL mode: the same candidate pairs, the
+// matching of yh_assign on their weights over the live slots and rows in ascending order.
+template <bool APP>
+__device__ void assoc_opt(const Lds& L, bool slive, bool rlive, float thr, int class_aware, int tid, int lane,
+                          int wave, const TrackReid& rd, const int* __restrict__ sim, int D) {
+    int rs, ns, rr, nr;
+    scan2(slive, rlive, L.wsum, lane, wave, rs, ns, rr, nr, false);
+    if (slive) L.slist[rs] = tid;
+    if (rlive) L.rlist[rr] = tid;
+    __syncthreads();                    // also frees wsum for the next scan
+    if (ns == 0 || nr == 0) return;     // prefix-sum totals: the same for every thread
+    const AssignLds A{L.best, L.sact, L.asor, L.apred, L.av};
+    if (wave == 0) {
+        assign_solve<true>(A, ns, nr, lane, [&](int a, int c) {
+            const int t = L.slist[a], d = L.rlist[c];
+            if (class_aware && !(L.scls[t] == L.rcls[d])) return 0;
+            const yh_track_box tb{L.sx1[t], L.sy1[t], L.sx2[t], L.sy2[t]};
+            const yh_track_box db{L.rx1[d], L.ry1[d], L.rx2[d], L.ry2[d]};
+            int dot = 0;
+            if constexpr (APP) dot = sim[(size_t)t * D + d];
+            float val;
+            if (!pair_value<APP>(L, rd, dot, t, d, tb, db, thr, val)) return 0;
+            return yh_trk_weight(val);
+        });
+    }
+    __syncthreads();
+    if (slive) {                        // a live slot is the rs-th of the list
+        const int c = A.ros[rs];
+        if (c >= 0) {
+            const int d = L.rlist[c];
+            L.mrow[tid] = d;
+            L.mslot[d] = tid;
+        }
+    }
+    __syncthreads();
+}
+
 // APP: yh_track_reid. A stream's state is then stream_bytes long, its gallery behind the words
 // of yh_track's state; rd is not read otherwise.
-template <bool APP>
+template <bool APP, bool OPT>
 __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict__ dets, const int* __restrict__ counts,
                                                         int D, const int* __restrict__ stream_ids,
                                                         char* __restrict__ state, size_t stream_bytes, int streams,
@@ -282,8 +330,12 @@ __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict_
         L.rlist = reinterpret_cast<int*>(at); at += D;
         L.wsum = reinterpret_cast<int*>(at); at += 2 * TRACK_WAVES;
         L.ctl = reinterpret_cast<int*>(at); at += 4;
-        L.gnz = reinterpret_cast<int*>(at); at += T;   // beyond the request unless APP: never touched then
-        L.qfl = reinterpret_cast<int*>(at);
+        L.gnz = reinterpret_cast<int*>(at);            // beyond the request unless APP: never touched then
+        L.qfl = L.gnz + T;
+        if constexpr (APP) at += T + D;
+        L.asor = reinterpret_cast<int*>(at);           // likewise unless OPT
+        L.apred = L.asor + D;
+        L.av = L.apred + D;
     }
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
@@ -377,13 +429,21 @@ __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict_
         if (has_slot) L.gnz[tid] = rd.gnz ? rd.gnz[(size_t)b * T + tid] : 0;
     }
     // phase 2 (the first barrier of each association's prefix sum orders the writes above)
-    int round = 0;
-    assoc<APP>(L, st0 == 2 || st0 == 3, band == 2, p.iou_first, p.class_aware, tid, lane, wave, round, rd, sim, sim_t, T,
-               D);
-    assoc<false>(L, st0 == 2 && L.mrow[tid] < 0, band == 1, p.iou_second, p.class_aware, tid, lane, wave, round, rd,
-                 sim, sim_t, T, D);
-    assoc<false>(L, st0 == 1, band == 2 && L.mslot[tid] < 0, p.iou_tentative, p.class_aware, tid, lane, wave, round, rd,
-                 sim, sim_t, T, D);
+    if constexpr (OPT) {
+        assoc_opt<APP>(L, st0 == 2 || st0 == 3, band == 2, p.iou_first, p.class_aware, tid, lane, wave, rd, sim, D);
+        assoc_opt<false>(L, st0 == 2 && L.mrow[tid] < 0, band == 1, p.iou_second, p.class_aware, tid, lane, wave, rd, sim,
+                         D);
+        assoc_opt<false>(L, st0 == 1, band == 2 && L.mslot[tid] < 0, p.iou_tentative, p.class_aware, tid, lane, wave, rd,
+                         sim, D);
+    } else {
+        int round = 0;
+        assoc<APP>(L, st0 == 2 || st0 == 3, band == 2, p.iou_first, p.class_aware, tid, lane, wave, round, rd, sim, sim_t,
+                   T, D);
+        assoc<false>(L, st0 == 2 && L.mrow[tid] < 0, band == 1, p.iou_second, p.class_aware, tid, lane, wave, round, rd,
+                     sim, sim_t, T, D);
+        assoc<false>(L, st0 == 1, band == 2 && L.mslot[tid] < 0, p.iou_tentative, p.class_aware, tid, lane, wave, round,
+                     rd, sim, sim_t, T, D);
+    }
 
     // phase 3: step 4 ...
     int st = st0;
@@ -485,34 +545,36 @@ __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict_
 
 }  // namespace
 
-template <bool APP>
+template <bool APP, bool OPT>
 int launch(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
            size_t stream_bytes, int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
            int* det_index, int* out_counts, const TrackReid& rd, hipStream_t s) {
     // arguments were checked by yh_track (yh_track_check): 1 <= max_tracks <= YH_TRACK_MAX_TRACKS,
     // 0 <= max_det <= YH_TRACK_MAX_DET
     if (batch <= 0) return 0;
-    if (int rc = lds_optin(reinterpret_cast<const void*>(track_kernel<APP>),
-                           (int)track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET, APP)))
+    if (int rc = lds_optin(reinterpret_cast<const void*>(track_kernel<APP, OPT>),
+                           (int)track_lds(YH_TRACK_MAX_TRACKS, YH_TRACK_MAX_DET, APP, OPT)))
         return rc;
-    hipLaunchKernelGGL(track_kernel<APP>, dim3(batch), dim3(TRACK_T), track_lds(max_tracks, max_det, APP), s, dets, counts,
-                       max_det, stream_ids, static_cast<char*>(state), stream_bytes, streams, max_tracks, p, max_out, out,
-                       ids, det_index, out_counts, rd);
+    hipLaunchKernelGGL((track_kernel<APP, OPT>), dim3(batch), dim3(TRACK_T), track_lds(max_tracks, max_det, APP, OPT), s,
+                       dets, counts, max_det, stream_ids, static_cast<char*>(state), stream_bytes, streams, max_tracks, p,
+                       max_out, out, ids, det_index, out_counts, rd);
     return (int)hipGetLastError();
 }
 
 int launch_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
                  int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
-                 int* det_index, int* out_counts, hipStream_t s) {
-    return launch<false>(dets, counts, batch, max_det, stream_ids, state, yh_track_stream_words(max_tracks) * 4, streams,
-                         max_tracks, p, max_out, out, ids, det_index, out_counts, TrackReid{}, s);
+                 int* det_index, int* out_counts, bool optimal, hipStream_t s) {
+    const auto run = optimal ? launch<false, true> : launch<false, false>;
+    return run(dets, counts, batch, max_det, stream_ids, state, yh_track_stream_words(max_tracks) * 4, streams, max_tracks,
+               p, max_out, out, ids, det_index, out_counts, TrackReid{}, s);
 }
 
 int launch_track_reid(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
                       int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
-                      int* det_index, int* out_counts, const TrackReid& rd, hipStream_t s) {
-    return launch<true>(dets, counts, batch, max_det, stream_ids, state, yh_track_reid_stream_bytes(max_tracks, rd.dim),
-                        streams, max_tracks, p, max_out, out, ids, det_index, out_counts, rd, s);
+                      int* det_index, int* out_counts, const TrackReid& rd, bool optimal, hipStream_t s) {
+    const auto run = optimal ? launch<true, true> : launch<true, false>;
+    return run(dets, counts, batch, max_det, stream_ids, state, yh_track_reid_stream_bytes(max_tracks, rd.dim), streams,
+               max_tracks, p, max_out, out, ids, det_index, out_counts, rd, s);
 }
 
 }  // namespace yh

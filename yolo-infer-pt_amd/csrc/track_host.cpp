@@ -9,11 +9,15 @@
 // the same matching: a pair that is the best of its slot and of its row under that strict order
 // is preceded by no pair that shares a side with it, so the walk takes it; removing it and
 // repeating is the walk.
+//
+// In YH_ASSIGN_OPTIMAL mode (yh_track2 / yh_track_reid2) the same candidate pairs go, as weights,
+// through csrc/assign_host.h's solver instead of the walk.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "assign_host.h"
 #include "host_parallel.h"
 #include "track_host.h"
 
@@ -38,9 +42,34 @@ yh_track_box row_box(const float* d) { return yh_track_box{d[0], d[1], d[2], d[3
 
 // pair(t, d, val): is (slot t, row d) a candidate, and with which sort value?
 template <class FS, class FR, class FP>
-void assoc(Frame& fr, FS slot_live, FR row_live, int class_aware, FP pair) {
+void assoc(Frame& fr, FS slot_live, FR row_live, int class_aware, FP pair, int mode) {
     std::vector<Pair> pairs;
     const int T = (int)fr.status.size();
+    if (mode == YH_ASSIGN_OPTIMAL) {
+        // the live slots and rows in ascending order, the candidates' weights between them
+        std::vector<int> ts, ds;
+        for (int t = 0; t < T; ++t)
+            if (slot_live(t)) ts.push_back(t);
+        for (int d = 0; d < fr.n; ++d)
+            if (row_live(d)) ds.push_back(d);
+        const int nt = (int)ts.size(), nd = (int)ds.size();
+        if (nt == 0 || nd == 0) return;
+        std::vector<int> w((size_t)nt * nd, 0);
+        for (int a = 0; a < nt; ++a)
+            for (int c = 0; c < nd; ++c) {
+                if (class_aware && !(fr.tcls[ts[a]] == fr.dets[6 * (size_t)ds[c] + 5])) continue;
+                float val;
+                if (pair(ts[a], ds[c], val)) w[(size_t)a * nd + c] = yh_trk_weight(val);
+            }
+        std::vector<int> ros(nt), sor(nd);
+        yh_assign_solve(nt, nd, [&](int a, int c) { return w[(size_t)a * nd + c]; }, ros.data(), sor.data());
+        for (int a = 0; a < nt; ++a) {
+            if (ros[a] < 0) continue;
+            fr.mrow[ts[a]] = ds[ros[a]];
+            fr.mslot[ds[ros[a]]] = ts[a];
+        }
+        return;
+    }
     for (int t = 0; t < T; ++t) {
         if (!slot_live(t)) continue;
         for (int d = 0; d < fr.n; ++d) {
@@ -127,7 +156,7 @@ void gallery_update(const Reid& r, int t, int d, bool born) {
 
 // one frame of one stream; w: the stream's state words; reid: NULL for yh_track
 void track_stream(const float* dets, int count, int max_det, uint32_t* w, int T, const yh_track_params& p,
-                  int max_out, float* out, int* ids, int* det_index, int* out_count, const Reid* reid) {
+                  int max_out, float* out, int* ids, int* det_index, int* out_count, const Reid* reid, int mode) {
     std::fill(out, out + (size_t)max_out * 6, 0.0f);
     std::fill(ids, ids + max_out, 0);
     std::fill(det_index, det_index + max_out, 0);
@@ -178,13 +207,14 @@ void track_stream(const float* dets, int count, int max_det, uint32_t* w, int T,
             }
             return yh_trk_pair_reid(fr.tbox[t], row_box(dets + 6 * (size_t)d), p.iou_first, feat, dot,
                                     reid->rp.cos_min, reid->rp.iou_min, val);
-        });
+        }, mode);
     } else {
-        assoc(fr, first, high, p.class_aware, by_iou(p.iou_first));
+        assoc(fr, first, high, p.class_aware, by_iou(p.iou_first), mode);
     }
-    assoc(fr, [&](int t) { return fr.status[t] == 2 && fr.mrow[t] < 0; }, low, p.class_aware, by_iou(p.iou_second));
+    assoc(fr, [&](int t) { return fr.status[t] == 2 && fr.mrow[t] < 0; }, low, p.class_aware, by_iou(p.iou_second),
+          mode);
     assoc(fr, [&](int t) { return fr.status[t] == 1; }, [&](int d) { return high(d) && fr.mslot[d] < 0; },
-          p.class_aware, by_iou(p.iou_tentative));
+          p.class_aware, by_iou(p.iou_tentative), mode);
     std::vector<int> grow;   // the gallery's work: slot -> its row of this frame, born ones tagged
     if (reid) {
         grow.assign(T, -1);
@@ -354,7 +384,8 @@ int yh_embed_similarity_host_run(const int8_t* a, size_t a_block_stride, int nbl
 
 int yh_track_host_run(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
                       void* state, int streams, int max_tracks, const yh_track_params* p, int max_out, float* out,
-                      int* ids, int* det_index, int* out_counts, int threads, const yh_track_reid_args* ra) {
+                      int* ids, int* det_index, int* out_counts, int threads, const yh_track_reid_args* ra,
+                      int assign_mode) {
     const size_t words = yh_track_stream_words(max_tracks);
     const size_t stride = ra ? yh_track_reid_stream_bytes(max_tracks, ra->dim) : words * 4;
     int8_t* wq = nullptr;
@@ -403,7 +434,7 @@ int yh_track_host_run(const float* dets, const int* counts, int batch, int max_d
             reid.rp = ra->rp;
         }
         track_stream(dets + (size_t)b * max_det * 6, counts[b], max_det, reinterpret_cast<uint32_t*>(w), max_tracks,
-                     *p, max_out, o, oi, od, out_counts + b, ra ? &reid : nullptr);
+                     *p, max_out, o, oi, od, out_counts + b, ra ? &reid : nullptr, assign_mode);
     };
     yh::parallel_strided(batch, threads, run);
     return 0;

@@ -209,11 +209,11 @@ const char* yh_track_check(const void* dets, const void* counts, int batch, int 
                            const void* ids, const void* det_index, const void* out_counts);
 
 // The host twin proper; arguments already checked. Batch rows (streams) run in parallel over
-// `threads` (<= 0: every hardware thread).
+// `threads` (<= 0: every hardware thread). assign_mode: YH_ASSIGN_GREEDY or YH_ASSIGN_OPTIMAL.
 int yh_track_host_run(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids,
                       void* state, int streams, int max_tracks, const yh_track_params* p, int max_out, float* out,
                       int* ids, int* det_index, int* out_counts, int threads,
-                      const yh_track_reid_args* reid = nullptr);
+                      const yh_track_reid_args* reid = nullptr, int assign_mode = YH_ASSIGN_GREEDY);
 
 // The host twins of yh_embed_quantize / yh_embed_similarity; arguments already checked.
 void yh_embed_quantize_row(const float* e, int dim, int8_t* q);   // one row; e NULL: zeros

@@ -92,6 +92,12 @@ _PROTOS = {
                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_track_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "yh_track2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "yh_track2_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "yh_assign": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "yh_assign_host": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "yh_embed_quantize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "yh_embed_quantize_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]),
     "yh_embed_similarity": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
@@ -106,6 +112,12 @@ _PROTOS = {
     "yh_track_reid_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_size_t, c_int]),
+    "yh_track_reid2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "yh_track_reid2_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_size_t, c_void_p, c_int]),
     "yh_gallery_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "yh_gallery_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

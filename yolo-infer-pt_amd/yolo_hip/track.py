@@ -9,6 +9,8 @@ lies - no copy to the host, no synchronisation:
   track_state  the zeroed state tensor of `streams` streams
   Tracks       (dets, ids, det_index, counts) of one call
   track_reid   yh_track_reid: `track` with an appearance term (int8 features, cosine by int8 MFMA)
+  assign       yh_assign: batched maximum-weight assignment; `track(..., assign="optimal")` and
+               `track_reid` likewise choose among an association's candidates with it (yh_track2)
   embed_quantize, embed_similarity   its two primitives, usable alone for gallery search
   Tracker      the state, the thresholds and the buffers of a set of streams; `update` for a
                caller's loop, `post` as the in-stream hook of a DetectPipeline
@@ -16,9 +18,9 @@ lies - no copy to the host, no synchronisation:
 The rules are ByteTrack's with ultralytics' KalmanFilterXYWH (a first association of the high
 scores with tracked and lost tracks, a second of the low scores with the tracks still unmatched,
 a third of the remaining high scores with the tentative tracks; new tracks are tentative for a
-frame), with two deliberate differences: the association is a greedy walk over the pairs by
-IoU where ByteTrack solves an assignment (lapjv), and it only pairs equal classes unless
-class_aware is off. Both make it deterministic, parallel and of the same shape as yh_match. There
+frame), with two deliberate differences: by default the association is a greedy walk over the
+pairs by IoU where ByteTrack solves an assignment (lapjv) - assign="optimal" solves it, with fixed
+tie rules - and it only pairs equal classes unless class_aware is off. There
 is no counterpart in the reference; the semantics are those stated in include/yolo_hip.h, pinned
 by the numpy restatement in tests/_track_cases.py.
 """
@@ -30,6 +32,9 @@ import torch
 MAX_TRACKS = 1024   # YH_TRACK_MAX_TRACKS
 MAX_DET = 1024      # YH_TRACK_MAX_DET
 REID_MAX_DIM = 2048  # YH_REID_MAX_DIM
+ASSIGN_MAX_WEIGHT = 1 << 16   # YH_ASSIGN_MAX_WEIGHT
+ASSIGN_MAX_SIZE = 1024        # YH_ASSIGN_MAX_SIZE
+ASSIGN_MODES = {"greedy": 0, "optimal": 1}   # YH_ASSIGN_GREEDY, YH_ASSIGN_OPTIMAL
 _HDR, _FIELDS = 4, 24   # state words per stream: _HDR + _FIELDS * max_tracks (csrc/track_host.h)
 
 
@@ -51,6 +56,17 @@ def params(track_high=0.25, track_low=0.1, track_new=0.25, iou_first=0.2, iou_se
 class ReidParams(ctypes.Structure):
     """yh_reid_params"""
     _fields_ = [("cos_min", ctypes.c_float), ("iou_min", ctypes.c_float)]
+
+
+class AssignParams(ctypes.Structure):
+    """yh_assign_params"""
+    _fields_ = [("mode", ctypes.c_int), ("reserved", ctypes.c_int * 3)]
+
+
+def _assign_params(assign):
+    if assign not in ASSIGN_MODES:
+        raise ValueError(f"yolo_hip.track: assign must be 'greedy' or 'optimal', got {assign!r}")
+    return AssignParams(ASSIGN_MODES[assign])
 
 
 def _check_dim(dim, who="yolo_hip.track"):
@@ -136,7 +152,7 @@ def _frame_args(dets, counts, state, stream_ids, max_out, out):
     return dev, B, md, max_out, o
 
 
-def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, threads=0):
+def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, threads=0, assign="greedy"):
     """One frame of every stream of a batch, in one launch.
 
     dets (B, max_det, 6) f32 and counts (B,) i32 as `nms` or `Detector` return them (rows at or
@@ -147,7 +163,12 @@ def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, 
     -> Tracks of (B, max_out, ...) (max_out defaults to max_det); out=(dets, ids, det_index, counts)
     reuses buffers. Every byte is written.
 
-    cuda tensors run the HIP kernel (yh_track) asynchronously on the current stream, CPU tensors
+    assign: "greedy" (the default: the sorted walk over the candidate pairs) or "optimal": each
+    association takes, among the same candidate pairs, a matching of maximum total IoU (yh_assign's,
+    deterministic). It keeps ids where tracks compete for the same detections and costs more time;
+    the state is the same, so the mode may change between frames.
+
+    cuda tensors run the HIP kernel (yh_track2) asynchronously on the current stream, CPU tensors
     the host twin (yh_track_host, `threads` <= 0: every hardware thread); both give the same bytes,
     state included. Frames of one stream must be submitted in order on one stream."""
     from ._lib import check, lib
@@ -161,13 +182,14 @@ def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, 
     L = lib()
     if mt <= MAX_TRACKS and L.yh_track_state_bytes(S, mt) != state.numel() * 4:
         raise RuntimeError("yolo_hip.track: the library's state size differs from track_state's")
+    ap = _assign_params(assign)
     args = (ptr(dets), ptr(counts), B, md, ptr(stream_ids), ptr(state), S, mt, ctypes.byref(p), max_out,
-            ptr(o.dets), ptr(o.ids), ptr(o.det_index), ptr(o.counts))
+            ptr(o.dets), ptr(o.ids), ptr(o.det_index), ptr(o.counts), ctypes.byref(ap))
     if dev.type == "cuda":
         with torch.cuda.device(dev):
-            check(L.yh_track(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track")
+            check(L.yh_track2(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track")
     elif dev.type == "cpu":
-        check(L.yh_track_host(*args, int(threads)), "track_host")
+        check(L.yh_track2_host(*args, int(threads)), "track_host")
     else:
         raise ValueError(f"yolo_hip.track: unsupported device {dev}")
     return o
@@ -182,7 +204,8 @@ def reid_workspace(batch, max_det, max_tracks, dim, device="cpu"):
 
 
 def track_reid(dets, counts, state, embed=None, feat_counts=None, embed_total=None, dim=None, reid_cos=0.5,
-               reid_iou=0.5, p=None, stream_ids=None, max_out=None, out=None, workspace=None, threads=0):
+               reid_iou=0.5, p=None, stream_ids=None, max_out=None, out=None, workspace=None, threads=0,
+               assign="greedy"):
     """`track` with an appearance term in its first association (yh_track_reid): a track and a
     high-score row may also pair when their features agree (cosine >= reid_cos) and they overlap
     at least reid_iou, and such a pair is walked at the larger of its IoU and (1 + cosine) / 2.
@@ -196,7 +219,9 @@ def track_reid(dets, counts, state, embed=None, feat_counts=None, embed_total=No
     below capacity and below embed_total[0] when given - `Classified.embed` of `Crops` cut with
     counts=feat_counts, and `Crops.total`, plug in as they lie. dim: the feature length when embed
     is None. workspace: a `reid_workspace` to reuse (None: allocated per call).
-    Without features the result and the tracks are exactly `track`'s.
+    Without features the result and the tracks are exactly `track`'s. assign: as `track`'s; in
+    "optimal" mode the first association maximises the total of the pairs' values (the larger of
+    IoU and (1 + cosine) / 2 where eligible).
 
     cuda tensors run the HIP kernels (quantise, the int8 MFMA similarity, the track kernel) on
     the current stream, CPU tensors the host twin; both give the same bytes, state included."""
@@ -231,18 +256,56 @@ def track_reid(dets, counts, state, embed=None, feat_counts=None, embed_total=No
         _check("workspace", workspace, (None,), torch.uint8, dev)
     p = params() if p is None else p
     rp = ReidParams(float(reid_cos), float(reid_iou))
+    ap = _assign_params(assign)
     args = (_ptr(dets), _ptr(counts), B, md, _ptr(stream_ids), _ptr(state), S, mt, ctypes.byref(p), max_out,
             _ptr(o.dets), _ptr(o.ids), _ptr(o.det_index), _ptr(o.counts), _ptr(embed),
             0 if embed is None else embed.shape[0], dim, _ptr(feat_counts), _ptr(embed_total), ctypes.byref(rp),
-            _ptr(workspace), workspace.numel())
+            _ptr(workspace), workspace.numel(), ctypes.byref(ap))
     if dev.type == "cuda":
         with torch.cuda.device(dev):
-            check(L.yh_track_reid(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track_reid")
+            check(L.yh_track_reid2(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track_reid")
     elif dev.type == "cpu":
-        check(L.yh_track_reid_host(*args, int(threads)), "track_reid_host")
+        check(L.yh_track_reid2_host(*args, int(threads)), "track_reid_host")
     else:
         raise ValueError(f"yolo_hip.track: unsupported device {dev}")
     return o
+
+
+def assign(weights, t_counts=None, d_counts=None, out=None, threads=0):
+    """Batched maximum-weight assignment (yh_assign): weights (problems, T, D) int32, 0 = the pair is
+    forbidden, 1 .. 65536 its weight (values outside are clamped into [0, 65536]); T, D <= 1024.
+    t_counts / d_counts (problems,) int32 or None: only the leading slots / rows of a problem take
+    part and nothing beyond them is read. -> (row_of_slot (problems, T), slot_of_row (problems, D))
+    int32, -1 where unmatched; out=(row_of_slot, slot_of_row) reuses buffers, every element is
+    written. The matching has the largest total weight over the allowed pairs (not the largest
+    size); among equal totals the one the algorithm stated in include/yolo_hip.h finds.
+    cuda tensors run the kernel on the current stream, CPU tensors the host twin: the same bytes."""
+    from ._lib import check, lib
+    who = "yolo_hip.assign"
+    if not isinstance(weights, torch.Tensor) or weights.dim() != 3:
+        raise ValueError(f"{who}: weights must be a (problems, T, D) tensor")
+    dev = weights.device
+    P, T, D = weights.shape
+    _check("weights", weights, (P, T, D), torch.int32, dev, who)
+    if t_counts is not None:
+        _check("t_counts", t_counts, (P,), torch.int32, dev, who)
+    if d_counts is not None:
+        _check("d_counts", d_counts, (P,), torch.int32, dev, who)
+    if out is None:
+        out = (torch.empty((P, T), dtype=torch.int32, device=dev), torch.empty((P, D), dtype=torch.int32, device=dev))
+    else:
+        _check("out row_of_slot", out[0], (P, T), torch.int32, dev, who)
+        _check("out slot_of_row", out[1], (P, D), torch.int32, dev, who)
+    L = lib()
+    args = (_ptr(weights), P, T, D, _ptr(t_counts), _ptr(d_counts), _ptr(out[0]), _ptr(out[1]))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            check(L.yh_assign(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "assign")
+    elif dev.type == "cpu":
+        check(L.yh_assign_host(*args, int(threads)), "assign_host")
+    else:
+        raise ValueError(f"{who}: unsupported device {dev}")
+    return out[0], out[1]
 
 
 def embed_quantize(e, count=None, out=None, threads=0):
@@ -345,12 +408,17 @@ class Tracker:
     at the first call and again when the batch shape grows. `feature_counts` says which rows to cut
     and embed. Without reid_dim a Tracker is the plain IoU tracker and takes no embeddings.
 
+    assign: "greedy" (default) or "optimal", passed to every `track` / `track_reid` call (the
+    attribute may be changed between frames).
+
     Nothing here reads a device value on the host. Outputs are allocated per call on the stream
     the call runs on (DetectPipeline marks its `extra` for the caller's stream)."""
 
     def __init__(self, streams, device, max_tracks=256, max_out=None, track_high=0.25, track_low=0.1, track_new=0.25,
                  iou_first=0.2, iou_second=0.5, iou_tentative=0.3, max_age=30, class_aware=True, reid_dim=None,
-                 reid_cos=0.5, reid_iou=0.5):
+                 reid_cos=0.5, reid_iou=0.5, assign="greedy"):
+        _assign_params(assign)
+        self.assign = assign
         self.device = torch.device(device)
         self.max_tracks = int(max_tracks)
         self.max_out = None if max_out is None else int(max_out)
@@ -406,14 +474,15 @@ class Tracker:
             raise ValueError(f"yolo_hip.Tracker: a batch of {dets.shape[0]} rows for {self.streams} streams")
         if self.reid_dim is None:
             return track(dets, counts, self.state, self.params, stream_ids=stream_ids, max_out=self.max_out,
-                         threads=threads)
+                         threads=threads, assign=self.assign)
         from ._lib import lib
         need = lib().yh_track_reid_workspace_bytes(dets.shape[0], dets.shape[1], self.max_tracks, self.reid_dim)
         if self._workspace is None or self._workspace.numel() < need:
             self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
         return track_reid(dets, counts, self.state, embed=embed, feat_counts=feat_counts, embed_total=embed_total,
                           dim=self.reid_dim, reid_cos=self.reid_cos, reid_iou=self.reid_iou, p=self.params,
-                          stream_ids=stream_ids, max_out=self.max_out, workspace=self._workspace, threads=threads)
+                          stream_ids=stream_ids, max_out=self.max_out, workspace=self._workspace, threads=threads,
+                          assign=self.assign)
 
     def post(self, dets, counts):
         if self.device.type == "cuda":
