@@ -848,6 +848,13 @@ int yh_debug_run_ops(yh_handle* h, const void* x, int x_u8, int batch, int heigh
                      int last, void* stream);
 int yh_debug_operand(const yh_handle* h, int index, int slot, void* dst, size_t dst_bytes, void* stream);
 
+/* The 16-bit epilogues activate two adjacent outputs at once on a register pair (silu2<T>).
+ * yh_debug_silu_pairs (tests/test_gpu_epilogue_pairs.py) runs the scalar silu<T> and silu2<T> of
+ * dtype YH_F16 / YH_BF16 over the n floats at device pointer x, elements 2k and 2k + 1 forming a
+ * pair, and writes both results as fp32 bit patterns to the device arrays y_scalar and y_pair
+ * (n uint32 each), on the current device's null stream, asynchronously. */
+int yh_debug_silu_pairs(int dtype, const void* x, void* y_scalar, void* y_pair, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,7 +54,7 @@ __device__ __forceinline__ void ck_act(const f32x16& acc, const float* b, unsign
     for (int i = 0; i < 4; ++i) bv[i] = reinterpret_cast<const f32x4*>(b)[i];
 #pragma unroll
     for (int e = 0; e < 16; e += 2)
-        w[e >> 1] = pack2<T>(silu<T>(acc[e] + bv[e >> 2][e & 3]), silu<T>(acc[e + 1] + bv[e >> 2][(e + 1) & 3]));
+        w[e >> 1] = bias_act_pack2<T>(f32x2{acc[e], acc[e + 1]}, f32x2{bv[e >> 2][e & 3], bv[e >> 2][(e + 1) & 3]});
 }
 
 // 1x1 conv step chain of one 32-cout tile: NK K blocks, A fragments from LDS at w (read
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
                     unsigned w[4];
 #pragma unroll
                     for (int e = 0; e < 8; e += 2)
-                        w[e >> 1] = pack2<T>(silu<T>(acc[8 * jj + e] + bj[e]), silu<T>(acc[8 * jj + e + 1] + bj[e + 1]));
+                        w[e >> 1] = bias_act_pack2<T>(f32x2{acc[8 * jj + e], acc[8 * jj + e + 1]}, f32x2{bj[e], bj[e + 1]});
                     if (SPLIT) {
                         if (bv) *reinterpret_cast<uint4*>(C2 + ck_off<HH>(bp, 4 * t + 2 * jj + h)) = make_uint4(w[0], w[1], w[2], w[3]);
                     } else {
@@ -441,7 +441,7 @@ __global__ __launch_bounds__(CK_THREADS, 1) void c3k_fused(const C3kArgs A) {
                 const uint4 q1 = *reinterpret_cast<const uint4*>(C1 + o1);
                 const unsigned rv[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
 #pragma unroll
-                for (int q = 0; q < 8; ++q) w[q] = pack2<T>(lo16<T>(w[q]) + lo16<T>(rv[q]), hi16<T>(w[q]) + hi16<T>(rv[q]));
+                for (int q = 0; q < 8; ++q) w[q] = add_pack2<T>(w[q], rv[q]);
             }
             *reinterpret_cast<uint4*>(dst + o0) = make_uint4(w[0], w[1], w[2], w[3]);
             *reinterpret_cast<uint4*>(dst + o1) = make_uint4(w[4], w[5], w[6], w[7]);

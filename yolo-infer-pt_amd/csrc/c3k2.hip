@@ -142,20 +142,21 @@ inline bool cs_index_ok(int TH, int TW, int ni, int nc) {
 // 16 consecutive outputs of one pixel (couts co0 .. co0 + 15): bias, SiLU, one rounding
 template <typename T>
 __device__ __forceinline__ void cs_act(const f32x16& acc, unsigned bias_addr, uint4 (&o)[2]) {
-    float v[16];
+    unsigned w[8];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const float4 b = cs_rdf(bias_addr + 16 * q);
-        v[4 * q] = acc[4 * q] + b.x;
-        v[4 * q + 1] = acc[4 * q + 1] + b.y;
-        v[4 * q + 2] = acc[4 * q + 2] + b.z;
-        v[4 * q + 3] = acc[4 * q + 3] + b.w;
+        w[2 * q] = bias_act_pack2<T>(f32x2{acc[4 * q], acc[4 * q + 1]}, f32x2{b.x, b.y});
+        w[2 * q + 1] = bias_act_pack2<T>(f32x2{acc[4 * q + 2], acc[4 * q + 3]}, f32x2{b.z, b.w});
     }
-    T t[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t[i] = fromf<T>(silu<T>(v[i]));
-    o[0] = *reinterpret_cast<const uint4*>(&t[0]);
-    o[1] = *reinterpret_cast<const uint4*>(&t[8]);
+    o[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+// the residual add of 8 rounded outputs: the sums in fp32, rounded again (nn.py:49)
+template <typename T>
+__device__ __forceinline__ uint4 cs_addres(const uint4& o, const uint4& r) {
+    return make_uint4(add_pack2<T>(o.x, r.x), add_pack2<T>(o.y, r.y), add_pack2<T>(o.z, r.z), add_pack2<T>(o.w, r.w));
 }
 
 // A 16-cout layer in a 32-cout tile leaves lane half 1 without outputs. Lane half 0's outputs
@@ -171,18 +172,17 @@ __device__ __forceinline__ uint4 cs_act_half(const f32x16& acc, unsigned bias_ad
         v[e] = __uint_as_float(
             __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[e]), __float_as_uint(acc[8 + e]), false, false)[0]);
     const float4 b0 = cs_rdf(bias_addr + 32 * hh), b1 = cs_rdf(bias_addr + 32 * hh + 16);
-    v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
-    v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-    T t[8];
+    const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+    unsigned w[4];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        // the product rounds to f32 before it rounds to T, as in cs_act and conv_mx: keep the
-        // compiler from folding both into one v_fma_mixlo_f16, which rounds once
-        float p = silu<T>(v[i]);
+    for (int i = 0; i < 8; i += 2) {
+        // the products round to f32 before they round to T, as in cs_act and conv_mx: keep the
+        // compiler from folding both into v_fma_mixlo_f16, which rounds once
+        f32x2 p = silu2<T>(f32x2{v[i], v[i + 1]} + f32x2{bb[i], bb[i + 1]});
         asm("" : "+v"(p));
-        t[i] = fromf<T>(p);
+        w[i >> 1] = pack2<T>(p);
     }
-    return *reinterpret_cast<const uint4*>(&t[0]);
+    return make_uint4(w[0], w[1], w[2], w[3]);
 #else
     (void)acc; (void)bias_addr; (void)hh;
     return uint4{};
@@ -426,12 +426,7 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                     if constexpr (NC == 1) {   // 16 couts: both lane halves share the epilogue
                         const uint4 o = cs_act_half<T>(acc, lds0 + L.b3, hh);
                         const uint4 rv = cs_rd(tb + 16 * hh);
-                        const T* ov = reinterpret_cast<const T*>(&o);
-                        const T* rr = reinterpret_cast<const T*>(&rv);
-                        T s[8];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) s[e] = fromf<T>(tof(ov[e]) + tof(rr[e]));
-                        cs_wr(LC + cs_px<SC>(px) + 16 * hh, *reinterpret_cast<const uint4*>(s));
+                        cs_wr(LC + cs_px<SC>(px) + 16 * hh, cs_addres<T>(o, rv));
                         return;
                     }
                     const int co = 32 * a + 16 * hh;
@@ -441,13 +436,7 @@ __global__ __launch_bounds__(CSP_THREADS) void csp_fused(const CspArgs A) {
                     const unsigned rs = tb + co * 2;
 #pragma unroll
                     for (int hf = 0; hf < 2; ++hf) {
-                        const uint4 rv = cs_rd(rs + 16 * hf);
-                        const T* ov = reinterpret_cast<const T*>(&o[hf]);
-                        const T* rr = reinterpret_cast<const T*>(&rv);
-                        T s[8];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) s[e] = fromf<T>(tof(ov[e]) + tof(rr[e]));
-                        o[hf] = *reinterpret_cast<const uint4*>(s);
+                        o[hf] = cs_addres<T>(o[hf], cs_rd(rs + 16 * hf));
                     }
                     const unsigned d = LC + cs_px<SC>(px) + co * 2;
                     cs_wr(d, o[0]);

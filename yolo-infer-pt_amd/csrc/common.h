@@ -423,6 +423,8 @@ int launch_set_io_cls(void** io, const void* x, float* probs, float* logits, flo
 int launch_conv(int dtype, int BM, int BN, const ConvArgs& a, hipStream_t s);   // fp32 handle only (conv.hip)
 int launch_first_conv(int dtype, const FirstConvArgs& a, int B, hipStream_t s);
 int launch_dwconv(int dtype, const DwArgs& a, hipStream_t s);
+// silu<T> against silu2<T> over n floats (yh_debug_silu_pairs; the 16-bit dtypes only)
+int launch_silu_pairs(int dtype, const float* x, unsigned* ys, unsigned* yp, size_t n, hipStream_t s);
 int launch_sppf(int dtype, const PoolArgs& a, const LaunchCtx& ctx, hipStream_t s);
 int launch_attention(int dtype, const AttnArgs& a, int B, const LaunchCtx& ctx, hipStream_t s);
 int launch_decode(int dtype, const DecodeArgs& a, hipStream_t s);

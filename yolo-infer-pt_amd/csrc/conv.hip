@@ -660,8 +660,8 @@ __global__ __launch_bounds__(S2_NT) void stem_fused(const Stem2Args p) {
             for (int i = 0; i < C1; ++i) {
                 f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
                 Mma<T>::step(acc, &wf[i], &xf);
-                const unsigned u01 = pack2<T>(silu<T>(acc[0] + bv[i].x), silu<T>(acc[1] + bv[i].y));
-                const unsigned u23 = pack2<T>(silu<T>(acc[2] + bv[i].z), silu<T>(acc[3] + bv[i].w));
+                const unsigned u01 = bias_act_pack2<T>(f32x2{acc[0], acc[1]}, f32x2{bv[i].x, bv[i].y});
+                const unsigned u23 = bias_act_pack2<T>(f32x2{acc[2], acc[3]}, f32x2{bv[i].z, bv[i].w});
                 *reinterpret_cast<uint2*>(so + 32 * i) = make_uint2(live ? u01 : 0u, live ? u23 : 0u);
             }
         };
@@ -713,7 +713,7 @@ __global__ __launch_bounds__(S2_NT) void stem_fused(const Stem2Args p) {
             // of each of 32 pixels per instruction; conv_mx.hip co_stage)
             unsigned w[8];
 #pragma unroll
-            for (int e = 0; e < 16; e += 2) w[e >> 1] = pack2<T>(silu<T>(acc[e] + b2[e]), silu<T>(acc[e + 1] + b2[e + 1]));
+            for (int e = 0; e < 16; e += 2) w[e >> 1] = bias_act_pack2<T>(f32x2{acc[e], acc[e + 1]}, f32x2{b2[e], b2[e + 1]});
             char* E = reinterpret_cast<char*>(&patch[0][0]) + wave * 2048;
             const int sw = (l32 >> 1) & 3;
             *reinterpret_cast<uint4*>(E + (l32 * 4 + ((2 * h) ^ sw)) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -864,15 +864,11 @@ __global__ __launch_bounds__(256) void dwconv3x3_c4(const DwArgs p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[e] = fmaf(wt[kh * 3 + kw][e], tof(xe[e]) * mk, acc[e]);
             }
-        T o4[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v = acc[e] + bias[e];
-            if (p.act == ACT_SILU) v = silu<T>(v);
-            o4[e] = fromf<T>(v);
-        }
+        const bool silu_act = p.act == ACT_SILU;
         const long long m = ((long long)n * p.H + h) * p.W + w;
-        *reinterpret_cast<uint2*>(reinterpret_cast<T*>(p.out) + m * p.ldo + c0) = *reinterpret_cast<const uint2*>(o4);
+        *reinterpret_cast<uint2*>(reinterpret_cast<T*>(p.out) + m * p.ldo + c0) =
+            make_uint2(bias_act_pack2<T>(f32x2{acc[0], acc[1]}, f32x2{bias[0], bias[1]}, silu_act),
+                       bias_act_pack2<T>(f32x2{acc[2], acc[3]}, f32x2{bias[2], bias[3]}, silu_act));
     }
 }
 
@@ -889,7 +885,45 @@ int launch_dw_t(const DwArgs& a, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
+// Test kernel of the pair helpers: silu<T> of x[i] into ys[i], silu2<T> of the pair (x[2k], x[2k+1])
+// into yp[2k], yp[2k+1], both as fp32 bit patterns; an odd n's last element pairs with itself.
+template <typename T>
+__global__ void __launch_bounds__(256) silu_pairs_kernel(const float* __restrict__ x, unsigned* __restrict__ ys,
+                                                         unsigned* __restrict__ yp, size_t n) {
+    const size_t npairs = (n + 1) / 2, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < npairs; k += stride) {
+        const size_t i0 = 2 * k, i1 = i0 + 1 < n ? i0 + 1 : i0;
+        const f32x2 v = {x[i0], x[i1]};
+        const f32x2 p = silu2<T>(v);
+        const float s0 = silu<T>(v.x), s1 = silu<T>(v.y);
+        ys[i0] = __float_as_uint(s0);
+        yp[i0] = __float_as_uint(p.x);
+        if (i1 != i0) {
+            ys[i1] = __float_as_uint(s1);
+            yp[i1] = __float_as_uint(p.y);
+        }
+    }
+}
+
+template <typename T>
+int launch_silu_pairs_t(const float* x, unsigned* ys, unsigned* yp, size_t n, hipStream_t s) {
+    const size_t blocks = ((n + 1) / 2 + 255) / 256;
+    hipLaunchKernelGGL((silu_pairs_kernel<T>), dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, s, x, ys,
+                       yp, n);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
+
+int launch_silu_pairs(int dtype, const float* x, unsigned* ys, unsigned* yp, size_t n, hipStream_t s) {
+    if (!x || !ys || !yp) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    switch (dtype) {
+        case F16: return launch_silu_pairs_t<_Float16>(x, ys, yp, n, s);
+        case BF16: return launch_silu_pairs_t<__bf16>(x, ys, yp, n, s);
+    }
+    return (int)hipErrorInvalidValue;
+}
 
 // Dense convs of the fp32 handle (the exact-parity mode): conv_gemm on the exact
 // f32 MFMA. The 16-bit handles run the conv_mx family (conv_mx.hip).

@@ -88,20 +88,14 @@ __device__ __forceinline__ void mx_epi(const f32x16 (&acc)[NA], const float* bv,
 #pragma unroll
         for (int e = 0; e < 8; e += 2) {
             const int i0 = c8 * 8 + e, i1 = i0 + 1;
-            float x0 = acc[i0 >> 4][i0 & 15] + bv[i0];
-            float x1 = acc[i1 >> 4][i1 & 15] + bv[i1];
-            if constexpr (SILU) {
-                x0 = silu<T>(x0);
-                x1 = silu<T>(x1);
-            }
-            w[e >> 1] = pack2<T>(x0, x1);
+            w[e >> 1] = bias_act_pack2<T, SILU>(f32x2{acc[i0 >> 4][i0 & 15], acc[i1 >> 4][i1 & 15]}, f32x2{bv[i0], bv[i1]});
         }
         if constexpr (RES) {
             const uint4 r = *reinterpret_cast<const uint4*>(resp + c8 * 8);
             const unsigned rr[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                w[q] = pack2<T>(lo16<T>(w[q]) + lo16<T>(rr[q]), hi16<T>(w[q]) + hi16<T>(rr[q]));
+                w[q] = add_pack2<T>(w[q], rr[q]);
         }
         if (c8 < nc8) *reinterpret_cast<uint4*>(outp + c8 * 8) = make_uint4(w[0], w[1], w[2], w[3]);
     }
@@ -128,13 +122,7 @@ __device__ __forceinline__ void co_stage(const f32x16 (&acc)[NA], const float* b
 #pragma unroll
         for (int e = 0; e < 8; e += 2) {
             const int i0 = c8 * 8 + e, i1 = i0 + 1;
-            float x0 = acc[i0 >> 4][i0 & 15] + bv[i0];
-            float x1 = acc[i1 >> 4][i1 & 15] + bv[i1];
-            if constexpr (SILU) {
-                x0 = silu<T>(x0);
-                x1 = silu<T>(x1);
-            }
-            w[e >> 1] = pack2<T>(x0, x1);
+            w[e >> 1] = bias_act_pack2<T, SILU>(f32x2{acc[i0 >> 4][i0 & 15], acc[i1 >> 4][i1 & 15]}, f32x2{bv[i0], bv[i1]});
         }
         const int q = 2 * NA * h + c8;
         *reinterpret_cast<uint4*>(E + (l32 * LPP + (q ^ co_swz<NA>(l32))) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -147,7 +135,7 @@ __device__ __forceinline__ uint4 co_addres(uint4 v, const T* rp) {
     const unsigned vv[4] = {v.x, v.y, v.z, v.w}, rr[4] = {r.x, r.y, r.z, r.w};
     unsigned w[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) w[q] = pack2<T>(lo16<T>(vv[q]) + lo16<T>(rr[q]), hi16<T>(vv[q]) + hi16<T>(rr[q]));
+    for (int q = 0; q < 4; ++q) w[q] = add_pack2<T>(vv[q], rr[q]);
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 

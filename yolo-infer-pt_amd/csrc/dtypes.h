@@ -7,6 +7,7 @@ namespace yh {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 // A "chunk" = 8 consecutive channels of one pixel = 16 B for 2-byte types, 32 B for f32.
 template <typename T> struct Chunk { uint4 v[sizeof(T) / 2]; };
@@ -62,6 +63,20 @@ template <typename T> __device__ __forceinline__ float silu(float x) {
 #endif
 }
 template <> __device__ __forceinline__ float silu<float>(float x) { return x / (1.0f + expf(-x)); }
+// silu<T> of two adjacent outputs of a 16-bit path at once: the two multiplies and the add run on
+// both halves of a register pair (v_pk_mul_f32 / v_pk_add_f32, which round like the scalar forms),
+// the exp and rcp per element. Same formula and constants as silu<T>, -log2e * x being what
+// __expf(-x) expands to; bit-identical to it (tests/test_gpu_epilogue_pairs.py, every fp32 pattern).
+template <typename T> __device__ __forceinline__ f32x2 silu2(f32x2 x) {
+    static_assert(sizeof(T) == 2, "silu2: the 16-bit handles only");
+#ifdef YH_SILU_EXPERIMENT
+    return x * f32x2{fmaf(x.x, 0.25f, 0.5f), fmaf(x.y, 0.25f, 0.5f)};
+#else
+    const f32x2 t = 0x1.715476p+0f * -x;
+    const f32x2 d = 1.0f + f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+    return x * f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+#endif
+}
 
 // One 16(rows) x 16(cols) x 32(k) MFMA step. a/b point at a lane's 8 consecutive
 // k values of its row (A) / column (B). For f32 the 32-deep step is eight exact

@@ -223,6 +223,15 @@ int yh_debug_operand(const yh_handle* h, int index, int slot, void* dst, size_t 
     });
 }
 
+int yh_debug_silu_pairs(int dtype, const void* x, void* y_scalar, void* y_pair, size_t n) {
+    return guarded([&] {
+        yh::require(dtype == YH_F16 || dtype == YH_BF16, "yh_debug_silu_pairs: dtype must be YH_F16 or YH_BF16");
+        yh::require(n == 0 || (x && y_scalar && y_pair), "null argument");
+        HIPCHECK((hipError_t)yh::launch_silu_pairs(dtype, (const float*)x, (unsigned*)y_scalar, (unsigned*)y_pair, n,
+                                                   nullptr));
+    });
+}
+
 int yh_op_count(const yh_handle* h) { return h ? (int)h->net.ops.size() : YH_EINVAL; }
 
 int yh_op_kernel(const yh_handle* h, int index, int batch, int height, int width, const char** name) {

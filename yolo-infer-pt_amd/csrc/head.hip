@@ -149,12 +149,8 @@ __device__ __forceinline__ void hc_dw(const T* src, int SW, int ss, T* dst, int 
                     acc01 = __builtin_elementwise_fma(f32x2{wk.x, wk.y}, xf[o + kh][kw][0], acc01);
                     acc23 = __builtin_elementwise_fma(f32x2{wk.z, wk.w}, xf[o + kh][kw][1], acc23);
                 }
-            T o4[4];
-            o4[0] = fromf<T>(silu<T>(acc01.x + bb.x));
-            o4[1] = fromf<T>(silu<T>(acc01.y + bb.y));
-            o4[2] = fromf<T>(silu<T>(acc23.x + bb.z));
-            o4[3] = fromf<T>(silu<T>(acc23.y + bb.w));
-            *reinterpret_cast<uint2*>(dst + ((r0 + o) * DW + c) * ds + c0) = *reinterpret_cast<const uint2*>(o4);
+            *reinterpret_cast<uint2*>(dst + ((r0 + o) * DW + c) * ds + c0) =
+                make_uint2(bias_act_pack2<T>(acc01, f32x2{bb.x, bb.y}), bias_act_pack2<T>(acc23, f32x2{bb.z, bb.w}));
         }
     }
 }
@@ -222,12 +218,8 @@ __device__ __forceinline__ void hc_pw_run(const T* src, int ss, int NPX, const T
                     const int co = a * 32 + 8 * q + 4 * h;
                     if (co >= M) continue;
                     const float4 bb = *reinterpret_cast<const float4*>(bias + co);
-                    float v[4] = {acc[4 * q] + bb.x, acc[4 * q + 1] + bb.y, acc[4 * q + 2] + bb.z,
-                                  acc[4 * q + 3] + bb.w};
-                    T o4[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o4[e] = fromf<T>(silu_act ? silu<T>(v[e]) : v[e]);
-                    store(px, co, *reinterpret_cast<const uint2*>(o4));
+                    store(px, co, make_uint2(bias_act_pack2<T>(f32x2{acc[4 * q], acc[4 * q + 1]}, f32x2{bb.x, bb.y}, silu_act),
+                                             bias_act_pack2<T>(f32x2{acc[4 * q + 2], acc[4 * q + 3]}, f32x2{bb.z, bb.w}, silu_act)));
                 }
             }
         }
@@ -296,11 +288,8 @@ __device__ __forceinline__ void hc_pw_units(const T* src, int ss, int NPX, const
                 const int co = a * 32 + 8 * q + 4 * h;
                 if (co >= M) continue;
                 const float4 bb = *reinterpret_cast<const float4*>(bias + co);
-                float v[4] = {acc[4 * q] + bb.x, acc[4 * q + 1] + bb.y, acc[4 * q + 2] + bb.z, acc[4 * q + 3] + bb.w};
-                T o4[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o4[e] = fromf<T>(silu_act ? silu<T>(v[e]) : v[e]);
-                store(px, co, *reinterpret_cast<const uint2*>(o4));
+                store(px, co, make_uint2(bias_act_pack2<T>(f32x2{acc[4 * q], acc[4 * q + 1]}, f32x2{bb.x, bb.y}, silu_act),
+                                         bias_act_pack2<T>(f32x2{acc[4 * q + 2], acc[4 * q + 3]}, f32x2{bb.z, bb.w}, silu_act)));
             }
         }
     }
@@ -447,9 +436,10 @@ __device__ __forceinline__ void hc_body(const HeadClsArgs& A, int li, char* hsm)
             const int gh = h0 + r, gw = w0 + cc;
             if ((unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W) {
                 const gptr<T> col = yio + ((long long)n * (4 + A.nc) + 4 + co) * A.A + V.aoff + gh * W + gw;
-                const T* o = reinterpret_cast<const T*>(&v);
+                const f32x2 s01 = sigmoid2<T>(lohi16<T>(v.x)), s23 = sigmoid2<T>(lohi16<T>(v.y));
+                const float sg[4] = {s01.x, s01.y, s23.x, s23.y};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) col[(long long)e * A.A] = fromf<T>(sigmoid<T>(tof(o[e])));
+                for (int e = 0; e < 4; ++e) col[(long long)e * A.A] = fromf<T>(sg[e]);
             }
         });
     else

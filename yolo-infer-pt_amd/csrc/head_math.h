@@ -15,6 +15,14 @@ template <> __device__ __forceinline__ float ex<float>(float x) { return expf(x)
 template <typename T> __device__ __forceinline__ float dv(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 template <> __device__ __forceinline__ float dv<float>(float a, float b) { return a / b; }
 template <typename T> __device__ __forceinline__ float sigmoid(float x) { return dv<T>(1.0f, 1.0f + ex<T>(-x)); }
+// sigmoid<T> of two adjacent values of a 16-bit path on one register pair (as silu2, dtypes.h): the
+// multiply by -log2e that ex<T>(-x) expands to and the add packed, exp and rcp per element
+template <typename T> __device__ __forceinline__ f32x2 sigmoid2(f32x2 x) {
+    static_assert(sizeof(T) == 2, "sigmoid2: the 16-bit handles only");
+    const f32x2 t = 0x1.715476p+0f * -x;
+    const f32x2 d = 1.0f + f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+    return f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+}
 
 // DFL: softmax over the 16 bins of one box side, expectation with weights 0..15 (v is overwritten)
 template <typename T>

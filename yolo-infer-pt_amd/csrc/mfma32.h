@@ -10,7 +10,6 @@
 namespace yh {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 // One 32(rows) x 32(cols) x 16(k) MFMA step: a / b are a lane's 8 consecutive k values of its row
 // (A) / column (B), c the lane's 16 accumulators.
@@ -85,9 +84,34 @@ __device__ __forceinline__ unsigned pack2(float a, float b) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, typename Pk2<T>::v2));
 }
 template <typename T>
+__device__ __forceinline__ unsigned pack2(f32x2 v) {
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, typename Pk2<T>::v2));
+}
+template <typename T>
 __device__ __forceinline__ float lo16(unsigned u) { return (float)__builtin_bit_cast(T, (unsigned short)(u & 0xffffu)); }
 template <typename T>
 __device__ __forceinline__ float hi16(unsigned u) { return (float)__builtin_bit_cast(T, (unsigned short)(u >> 16)); }
+
+template <typename T>
+__device__ __forceinline__ f32x2 lohi16(unsigned u) { return f32x2{lo16<T>(u), hi16<T>(u)}; }
+
+// The epilogue of two adjacent outputs on one register pair: bias add, SiLU (silu2) where the
+// layer has one, one rounding to T. acc / bias: the two accumulators and their biases.
+template <typename T, bool SILU = true>
+__device__ __forceinline__ unsigned bias_act_pack2(f32x2 acc, f32x2 bias) {
+    const f32x2 v = acc + bias;
+    if constexpr (SILU) return pack2<T>(silu2<T>(v));
+    else return pack2<T>(v);
+}
+// the same with the activation chosen at run time: a select, not a branch
+template <typename T>
+__device__ __forceinline__ unsigned bias_act_pack2(f32x2 acc, f32x2 bias, bool silu_act) {
+    const f32x2 v = acc + bias, s = silu2<T>(v);
+    return pack2<T>(silu_act ? s : v);
+}
+// Residual add of two rounded outputs: pack2(lo16(w) + lo16(r), hi16(w) + hi16(r)), the sum in fp32
+template <typename T>
+__device__ __forceinline__ unsigned add_pack2(unsigned w, unsigned r) { return pack2<T>(lohi16<T>(w) + lohi16<T>(r)); }
 
 // x / d for the divisor behind d (make_fastdiv)
 __device__ __forceinline__ uint32_t fast_div(uint32_t x, FastDiv d) {

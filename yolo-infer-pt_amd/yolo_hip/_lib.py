@@ -142,6 +142,7 @@ _PROTOS = {
     "yh_debug_op_desc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
     "yh_debug_run_ops": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "yh_debug_operand": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "yh_debug_silu_pairs": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_size_t]),
 }
 
 _lib = None
