@@ -17,15 +17,15 @@ NET := engine net_build net_weights net_forward net_launch net_debug
 HOSTHIP := post_abi nms_host
 # kernels; the NOFMA ones promise bit-exact arithmetic against host code: no FMA contraction
 KERNELS := conv sppf attn decode conv_mx conv_rw head c3k2 c3k pwchain cls
-KERNELS_NOFMA := preprocess nms match merge track reid gallery assign
+KERNELS_NOFMA := preprocess nms match merge track reid gallery assign motion
 # HIP-free translation units: plain C++, no device pass, no FMA contraction
-HOSTCXX := match_host merge_host track_host gallery_host assign_host
+HOSTCXX := match_host merge_host track_host gallery_host assign_host motion_host
 
 objs = $(patsubst %,$(OBJDIR)/%.o,$(1))
 OBJS := $(call objs,$(NET) $(HOSTHIP) $(KERNELS) $(KERNELS_NOFMA) $(HOSTCXX))
 HOST_H := $(SRC)/host_util.h $(SRC)/host_parallel.h $(SRC)/box_math.h \
           $(SRC)/match_host.h $(SRC)/merge_host.h $(SRC)/track_host.h $(SRC)/gallery_host.h \
-          $(SRC)/assign_host.h
+          $(SRC)/assign_host.h $(SRC)/motion_host.h
 
 all: $(OUT)
 
@@ -51,7 +51,7 @@ $(call objs,$(HOSTCXX)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/%.h $(SRC)/box_math.
 # the decode's value arithmetic, shared by its kernels and the fused head's
 $(call objs,decode head): $(SRC)/head_math.h
 # each shares its arithmetic with its host twin through box_math.h and the twin's header
-$(call objs,match merge track): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
+$(call objs,match merge track motion): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
 # the appearance kernels share the tracker's header: the twins live in track_host.cpp
 $(OBJDIR)/reid.o: $(SRC)/track_host.h $(SRC)/box_math.h
 # the int8 MFMA kernels share their fragment loads and lane map; the search shares its candidate

@@ -53,6 +53,11 @@
  *   yh_track_reid2      yh_track / yh_track_reid with that assignment in place of the greedy walk
  *                       of the associations, on request (ByteTrack's lapjv step)
  *   yh_assign_host, yh_track2_host, yh_track_reid2_host   the same in host memory
+ *   yh_motion           no reference counterpart: the camera's translation between consecutive frames
+ *                       of a stream, by block matching on luma thumbnails (BoT-SORT's global-motion step)
+ *   yh_track_warp       no reference counterpart: that motion applied to a stream's tracks before the
+ *                       frame's yh_track* call
+ *   yh_motion_host, yh_track_warp_host   the same in host memory
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -772,6 +777,92 @@ int yh_crop_rois(const yh_frame* frames, int batch, const float* boxes, int box_
 int yh_crop_rois_host(const yh_frame* frames, int batch, const float* boxes, int box_stride, const int* counts,
                       int max_rois, int out_h, int out_w, int keep_aspect, float pad, int capacity, void* crops,
                       int* rois, int* total, int threads);
+
+/* Camera-motion compensation for the tracker (no reference counterpart: the rules below are the
+ * specification; tests/_motion_cases.py restates them in numpy). yh_track predicts a track with its
+ * own velocity and gates on the IoU with the new rows, which assumes a camera at rest. yh_motion
+ * estimates the global translation between a stream's previous and current frame from their luma,
+ * yh_track_warp (below) moves the stream's tracks by it before the frame's yh_track* call - BoT-SORT's
+ * and ultralytics' global-motion step. Everything up to the last few fp32 operations is integer
+ * arithmetic: the device and the host compute the same bytes.
+ *
+ *   frames:     host array of `batch` descriptors as for yh_letterbox_frames (BGR or NV12, mixed, any
+ *               sizes, strided rows); the planes are device memory for yh_motion and host memory for
+ *               yh_motion_host. Row b is the next frame of stream stream_ids[b] (NULL: of stream b;
+ *               device memory for yh_motion); the ids must be distinct. Frames of one stream must
+ *               arrive in order and keep their size.
+ *   state:      yh_motion_state_bytes(streams, thumb_h, thumb_w) bytes, all-zero = no previous frame.
+ *               Per stream a 16-byte header (word 0 is 1 once a thumbnail is stored, the other words
+ *               are 0) and the stream's last thumbnail, thumb_h * thumb_w bytes; behind the `streams`
+ *               blocks a staging area of 32 thumbnails: batch row b leaves its current thumbnail in
+ *               slot b % 32 (the thumbnail launch needs a place for it while the search still reads
+ *               the previous one; the host writes the same bytes). No pointers, the same bytes on host
+ *               and device: the state can be copied between them in the middle of a sequence.
+ *   motion:     (batch, 3) f32: s, tx, ty - the rows of yh_track_warp. sad: (batch, 2) int32.
+ *               Every byte of both is written.
+ *
+ * 1. Luma. NV12: the Y byte. BGR: Y = (1868 B + 9617 G + 4899 R + 8192) >> 14 (OpenCV's fixed-point
+ *    BGR2GRAY).
+ * 2. Thumbnail. Pixel (i, j) covers the source rows (i * H) / thumb_h .. ((i + 1) * H) / thumb_h and the
+ *    columns alike (integer divisions, the end exclusive); its value is (sum + n / 2) / n over the
+ *    box's n luma bytes, unsigned and exact.
+ * 3. Search. With C the current and P the stored thumbnail and R = radius, for every (dy, dx) in
+ *    [-R, R]^2: SAD(dy, dx) = sum |C[i][j] - P[i - dy][j - dx]| over i in [R, thumb_h - R), j in
+ *    [R, thumb_w - R). The best shift minimises (SAD, |dy| + |dx|, dy, dx) lexicographically.
+ * 4. Refinement, fp32, one rounding per operation, no FMA. With s0 the best SAD and sm, sp the SADs at
+ *    dx - 1 and dx + 1 in the same row: if |dx| < R and den = (sm - s0) + (sp - s0) > 0,
+ *    fx = (0.5f * (float)(sm - sp)) / (float)den, else fx = 0; fy alike along dy. Then
+ *    tx = ((float)dx + fx) * ((float)W / (float)thumb_w), ty = ((float)dy + fy) * ((float)H / (float)thumb_h).
+ * 5. Output. motion[b] = (1, tx, ty), sad[b] = (s0, SAD(0, 0)). Without a previous frame: (1, 0, 0)
+ *    and (0, 0). If max_mad >= 0 and s0 > max_mad * (thumb_h - 2 R) * (thumb_w - 2 R) - a scene cut, or a
+ *    match not to be trusted - motion is (1, 0, 0) and sad still reports both values. A row whose id
+ *    is outside [0, streams) writes (1, 0, 0) and (0, 0) and touches no state. In every other case C
+ *    becomes the stream's thumbnail and the header word is set.
+ * Sign: content at source pixel (x, y) of the previous frame is at about (x + tx, y + ty) now.
+ * Limits of the model: one translation per frame, found to within a fraction of a thumbnail pixel and
+ * at most R thumbnail pixels long; no rotation, zoom, rolling shutter or parallax, and a moving
+ * foreground that fills much of the frame pulls the estimate towards its own motion.
+ *
+ * yh_motion: asynchronous on `stream`, allocates nothing, never synchronises, uses no atomics; two
+ * launches per 32 frames; state 4-byte aligned. yh_motion_host: the same bytes for host pointers, rows
+ * in parallel over `threads` (<= 0: all hardware threads), synchronous.
+ * YH_EINVAL (message in yh_last_error()), nothing launched or written: a frame yh_letterbox_frames'
+ * validation rejects, or smaller than the thumbnail (or so much larger that a box sum could pass
+ * 2^32); thumb_w % 4 != 0; radius outside [1, YH_MOTION_MAX_RADIUS]; thumb_h - 2 radius < 4 or
+ * thumb_w - 2 radius < 4; thumb_h * thumb_w > YH_MOTION_MAX_THUMB (both thumbnails then fit the
+ * workgroup's LDS); a negative size; a NULL required pointer. */
+#define YH_MOTION_MAX_RADIUS 32
+#define YH_MOTION_MAX_THUMB 32768
+size_t yh_motion_state_bytes(int streams, int thumb_h, int thumb_w);
+int yh_motion(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
+              int thumb_h, int thumb_w, int radius, int max_mad, float* motion /* (batch, 3) */,
+              int32_t* sad /* (batch, 2) */, void* stream);
+int yh_motion_host(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
+                   int thumb_h, int thumb_w, int radius, int max_mad, float* motion, int32_t* sad, int threads);
+
+/* Apply a motion to the tracks of a batch's streams before the frame's yh_track* call (no reference
+ * counterpart; tests/_motion_cases.py restates the rule). state: yh_track's (reid_dim 0; a stream's
+ * block is yh_track_state_bytes(1, max_tracks) bytes) or yh_track_reid's (reid_dim = its dim; the
+ * block is yh_track_reid_state_bytes(1, max_tracks, reid_dim) bytes). motion (batch, 3) f32: s, tx, ty
+ * of batch row b, whose stream is stream_ids[b] (NULL: b) as for yh_track.
+ * For a row with a valid id and finite s > 0, tx, ty, every slot whose status is not 0 is warped, in
+ * fp32 with one rounding per operation and no FMA; s2 = s * s:
+ *   x[0] = s * x[0] + tx; x[1] = s * x[1] + ty; x[2] = s * x[2]; x[3] = s * x[3];
+ *   v[i] = s * v[i]; a[i] = s2 * a[i]; b[i] = s2 * b[i]; c[i] = s2 * c[i].
+ * With s == 1 only the two centre coordinates change bits. A row with an invalid id, or a motion that
+ * is not finite or has s <= 0, changes nothing. Free slots, the header words and the gallery bytes are
+ * never written.
+ * Translation plus isotropic scale is all the state can represent: its four filters (cx, cy, w, h) are
+ * independent, and a rotation or shear would couple cx with cy. yh_motion only ever emits s = 1; the
+ * scale is for callers with an estimate of their own (zoom telemetry).
+ * yh_track_warp: device pointers, one workgroup per batch row, asynchronous on `stream`, allocates
+ * nothing, never synchronises. yh_track_warp_host: the same bytes in host memory.
+ * YH_EINVAL: a negative batch or streams, max_tracks outside [1, YH_TRACK_MAX_TRACKS], reid_dim neither
+ * 0 nor a legal feature length, a NULL required pointer. Nothing is launched or written then. */
+int yh_track_warp(void* state, int streams, int max_tracks, int reid_dim /* 0: yh_track's state */,
+                  const float* motion /* (batch, 3): s, tx, ty */, const int* stream_ids, int batch, void* stream);
+int yh_track_warp_host(void* state, int streams, int max_tracks, int reid_dim, const float* motion,
+                       const int* stream_ids, int batch, int threads);
 
 /* cv2.resize(src, (new_w, new_h), INTER_LINEAR) of one uint8 HWC 3-channel host image
  * (the resize step alone; dst is new_h x new_w x 3, channel order kept). */

@@ -9,6 +9,8 @@
 
 #include "yolo_hip.h"   // yh_track_params (launch_track)
 
+struct yh_motion_src;   // csrc/motion_host.h (launch_motion)
+
 namespace yh {
 
 enum DType { F32 = 0, F16 = 1, BF16 = 2 };
@@ -458,6 +460,13 @@ struct TrackReid {
 int launch_track_reid(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,
                       int streams, int max_tracks, const yh_track_params& p, int max_out, float* out, int* ids,
                       int* det_index, int* out_counts, const TrackReid& rd, bool optimal, hipStream_t s);
+// track.hip: yh_track_warp, a motion (s, tx, ty) per batch row applied to the stream's live slots
+int launch_track_warp(void* state, int streams, int max_tracks, int reid_dim, const float* motion,
+                      const int* stream_ids, int batch, hipStream_t s);
+// motion.hip: yh_motion, a thumbnail launch and a search launch per 32 frames; src from
+// csrc/motion_host.h's yh_motion_check
+int launch_motion(const ::yh_motion_src* src, int batch, const int* stream_ids, void* state, int streams,
+                  int thumb_h, int thumb_w, int radius, int max_mad, float* motion, int32_t* sad, hipStream_t s);
 // assign.hip: yh_assign, one wave per problem; the tracker's `optimal` instances above run the same solver
 int launch_assign(const int* weights, int problems, int T, int D, const int* t_counts, const int* d_counts,
                   int* row_of_slot, int* slot_of_row, hipStream_t s);

@@ -1,6 +1,8 @@
 // C ABI of the stages after the forward, none of which needs a handle: yh_nms, yh_match, yh_merge, yh_track, yh_embed_quantize, yh_embed_similarity,
-// yh_track_reid, yh_gallery_search, yh_gallery_enrol, yh_assign, yh_track2, yh_track_reid2 and their *_host twins.
+// yh_track_reid, yh_gallery_search, yh_gallery_enrol, yh_assign, yh_track2, yh_track_reid2, yh_motion, yh_track_warp
+// and their *_host twins.
 #include <algorithm>
+#include <vector>
 
 #include "common.h"
 #include "assign_host.h"
@@ -8,6 +10,7 @@
 #include "host_util.h"
 #include "match_host.h"
 #include "merge_host.h"
+#include "motion_host.h"
 #include "track_host.h"
 
 using yh::Fail;
@@ -169,6 +172,52 @@ int yh_track_host(const float* dets, const int* counts, int batch, int max_det, 
                   int* det_index, int* out_counts, int threads) {
     return yh_track2_host(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, p, max_out, out, ids,
                           det_index, out_counts, &kGreedy, threads);
+}
+
+int yh_track_warp(void* state, int streams, int max_tracks, int reid_dim, const float* motion, const int* stream_ids,
+                  int batch, void* stream) {
+    return guarded([&] {
+        checked(yh_track_warp_check(state, streams, max_tracks, reid_dim, motion, batch));
+        yh::require((uintptr_t)state % 4 == 0, "state must be 4-byte aligned");
+        const int rc = yh::launch_track_warp(state, streams, max_tracks, reid_dim, motion, stream_ids, batch,
+                                             (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("track_warp launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_track_warp_host(void* state, int streams, int max_tracks, int reid_dim, const float* motion,
+                       const int* stream_ids, int batch, int threads) {
+    return guarded([&] {
+        checked(yh_track_warp_check(state, streams, max_tracks, reid_dim, motion, batch));
+        yh_track_warp_host_run(state, streams, max_tracks, reid_dim, motion, stream_ids, batch, threads);
+    });
+}
+
+size_t yh_motion_state_bytes(int streams, int thumb_h, int thumb_w) {
+    if (streams < 0 || thumb_h < 1 || thumb_w < 1 || (long long)thumb_h * thumb_w > YH_MOTION_MAX_THUMB) return 0;
+    return yh_motion_staging_offset(streams, thumb_h, thumb_w) + (size_t)YH_MOTION_LAUNCH * thumb_h * thumb_w;
+}
+
+int yh_motion(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams, int thumb_h,
+              int thumb_w, int radius, int max_mad, float* motion, int32_t* sad, void* stream) {
+    return guarded([&] {
+        std::vector<yh_motion_src> src((size_t)std::max(batch, 0));
+        checked(yh_motion_check(frames, batch, state, streams, thumb_h, thumb_w, radius, motion, sad, src.data()));
+        yh::require((uintptr_t)state % 4 == 0, "motion: state must be 4-byte aligned on the device");
+        const int rc = yh::launch_motion(src.data(), batch, stream_ids, state, streams, thumb_h, thumb_w, radius, max_mad,
+                                         motion, sad, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("motion launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_motion_host(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams, int thumb_h,
+                   int thumb_w, int radius, int max_mad, float* motion, int32_t* sad, int threads) {
+    return guarded([&] {
+        std::vector<yh_motion_src> src((size_t)std::max(batch, 0));
+        checked(yh_motion_check(frames, batch, state, streams, thumb_h, thumb_w, radius, motion, sad, src.data()));
+        yh_motion_host_run(src.data(), batch, stream_ids, state, streams, thumb_h, thumb_w, radius, max_mad, motion, sad,
+                           threads);
+    });
 }
 
 int yh_assign(const int32_t* weights, int problems, int T, int D, const int32_t* t_counts, const int32_t* d_counts,

@@ -543,7 +543,53 @@ __global__ __launch_bounds__(TRACK_T) void track_kernel(const float* __restrict_
     }
 }
 
+// yh_track_warp: one workgroup per batch row, slots over threads; a slot's fields are a column of the
+// field-major state, so neighbouring threads read and write neighbouring words. Free slots, the
+// header and (behind the words) the gallery are not touched.
+constexpr int WARP_T = 256;
+__global__ __launch_bounds__(WARP_T) void track_warp_kernel(char* __restrict__ state, size_t stream_bytes, int streams,
+                                                            int T, const float* __restrict__ motion,
+                                                            const int* __restrict__ stream_ids) {
+    const int b = blockIdx.x;
+    const int s = stream_ids ? stream_ids[b] : b;      // one address for the workgroup: uniform
+    if (s < 0 || s >= streams) return;
+    const float m[3] = {motion[(size_t)b * 3], motion[(size_t)b * 3 + 1], motion[(size_t)b * 3 + 2]};
+    if (!yh_trk_warp_valid(m)) return;
+    uint32_t* w = reinterpret_cast<uint32_t*>(state + (size_t)s * stream_bytes);
+    for (int t = threadIdx.x; t < T; t += WARP_T) {
+        uint32_t* fld = w + YH_TRACK_HDR + t;
+        if (fld[(size_t)YH_TRK_STATUS * T] == 0u) continue;
+        yh_track_kal k;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            k.x[i] = __uint_as_float(fld[(size_t)(YH_TRK_X + i) * T]);
+            k.v[i] = __uint_as_float(fld[(size_t)(YH_TRK_V + i) * T]);
+            k.a[i] = __uint_as_float(fld[(size_t)(YH_TRK_A + i) * T]);
+            k.b[i] = __uint_as_float(fld[(size_t)(YH_TRK_B + i) * T]);
+            k.c[i] = __uint_as_float(fld[(size_t)(YH_TRK_C + i) * T]);
+        }
+        yh_trk_warp(k, m[0], m[1], m[2]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            fld[(size_t)(YH_TRK_X + i) * T] = __float_as_uint(k.x[i]);
+            fld[(size_t)(YH_TRK_V + i) * T] = __float_as_uint(k.v[i]);
+            fld[(size_t)(YH_TRK_A + i) * T] = __float_as_uint(k.a[i]);
+            fld[(size_t)(YH_TRK_B + i) * T] = __float_as_uint(k.b[i]);
+            fld[(size_t)(YH_TRK_C + i) * T] = __float_as_uint(k.c[i]);
+        }
+    }
+}
+
 }  // namespace
+
+int launch_track_warp(void* state, int streams, int max_tracks, int reid_dim, const float* motion,
+                      const int* stream_ids, int batch, hipStream_t s) {
+    // arguments were checked by yh_track_warp (yh_track_warp_check)
+    if (batch <= 0 || streams <= 0) return 0;
+    hipLaunchKernelGGL(track_warp_kernel, dim3(batch), dim3(WARP_T), 0, s, static_cast<char*>(state),
+                       yh_track_warp_stride(max_tracks, reid_dim), streams, max_tracks, motion, stream_ids);
+    return (int)hipGetLastError();
+}
 
 template <bool APP, bool OPT>
 int launch(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,

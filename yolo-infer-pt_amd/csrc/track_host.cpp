@@ -439,3 +439,37 @@ int yh_track_host_run(const float* dets, const int* counts, int batch, int max_d
     yh::parallel_strided(batch, threads, run);
     return 0;
 }
+
+const char* yh_track_warp_check(const void* state, int streams, int max_tracks, int reid_dim, const void* motion,
+                                int batch) {
+    if (batch < 0) return "batch must be >= 0";
+    if (streams < 0) return "streams must be >= 0";
+    if (max_tracks < 1) return "max_tracks must be >= 1";
+    if (max_tracks > YH_TRACK_MAX_TRACKS) return "max_tracks exceeds YH_TRACK_MAX_TRACKS (" YH_STR(YH_TRACK_MAX_TRACKS) ")";
+    if (reid_dim != 0)
+        if (const char* bad = yh_reid_dim_check(reid_dim)) return bad;
+    if (batch > 0 && !motion) return "null motion";
+    if (batch > 0 && streams > 0 && !state) return "null state";
+    return nullptr;
+}
+
+int yh_track_warp_host_run(void* state, int streams, int max_tracks, int reid_dim, const float* motion,
+                           const int* stream_ids, int batch, int threads) {
+    const size_t stride = yh_track_warp_stride(max_tracks, reid_dim);
+    const int T = max_tracks;
+    yh::parallel_strided(batch, threads, [&](int b) {
+        const int s = stream_ids ? stream_ids[b] : b;
+        const float* m = motion + (size_t)b * 3;
+        if (s < 0 || s >= streams || !yh_trk_warp_valid(m)) return;
+        uint32_t* w = reinterpret_cast<uint32_t*>(static_cast<char*>(state) + (size_t)s * stride);
+        const int* st = reinterpret_cast<const int*>(w) + YH_TRACK_HDR + (size_t)YH_TRK_STATUS * T;
+        for (int t = 0; t < T; ++t) {
+            if (st[t] == 0) continue;
+            yh_track_kal k;
+            load_kal(w, T, t, k);
+            yh_trk_warp(k, m[0], m[1], m[2]);
+            store_kal(w, T, t, k);
+        }
+    });
+    return 0;
+}

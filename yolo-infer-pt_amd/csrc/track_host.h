@@ -120,6 +120,36 @@ YH_HD void yh_trk_birth(yh_track_kal& k, const yh_track_box& d) {
     }
 }
 
+// yh_track_warp: is (s, tx, ty) a motion to apply? Finite (the exponent is not all ones: a bit
+// test, which no floating-point assumption can fold away) and s > 0.
+YH_HD bool yh_trk_warp_valid(const float* m) {
+    for (int i = 0; i < 3; ++i) {
+        uint32_t u;
+#ifdef __HIP_DEVICE_COMPILE__
+        u = __float_as_uint(m[i]);
+#else
+        __builtin_memcpy(&u, m + i, 4);
+#endif
+        if ((u & 0x7f800000u) == 0x7f800000u) return false;
+    }
+    return m[0] > 0.0f;
+}
+
+// yh_track_warp of one non-free slot: x -> s x + t for the centre, s x for the size, s v, s^2 P
+YH_HD void yh_trk_warp(yh_track_kal& k, float s, float tx, float ty) {
+    const float s2 = s * s;
+    k.x[0] = s * k.x[0] + tx;
+    k.x[1] = s * k.x[1] + ty;
+    k.x[2] = s * k.x[2];
+    k.x[3] = s * k.x[3];
+    for (int i = 0; i < 4; ++i) {
+        k.v[i] = s * k.v[i];
+        k.a[i] = s2 * k.a[i];
+        k.b[i] = s2 * k.b[i];
+        k.c[i] = s2 * k.c[i];
+    }
+}
+
 // step 3: is (slot box t, row box d) a candidate pair at threshold thr, and with which IoU?
 // (the class test is the caller's) The pair order is yh::float_order(iou) descending, then the
 // slot, then the row.
@@ -214,6 +244,16 @@ int yh_track_host_run(const float* dets, const int* counts, int batch, int max_d
                       void* state, int streams, int max_tracks, const yh_track_params* p, int max_out, float* out,
                       int* ids, int* det_index, int* out_counts, int threads,
                       const yh_track_reid_args* reid = nullptr, int assign_mode = YH_ASSIGN_GREEDY);
+
+// yh_track_warp: the argument check of both entry points, the bytes of one stream's block
+// (reid_dim 0: yh_track's state, else yh_track_reid's), and the host twin (arguments already checked).
+const char* yh_track_warp_check(const void* state, int streams, int max_tracks, int reid_dim, const void* motion,
+                                int batch);
+YH_HD size_t yh_track_warp_stride(int max_tracks, int reid_dim) {
+    return reid_dim ? yh_track_reid_stream_bytes(max_tracks, reid_dim) : yh_track_stream_words(max_tracks) * 4;
+}
+int yh_track_warp_host_run(void* state, int streams, int max_tracks, int reid_dim, const float* motion,
+                           const int* stream_ids, int batch, int threads);
 
 // The host twins of yh_embed_quantize / yh_embed_similarity; arguments already checked.
 void yh_embed_quantize_row(const float* e, int dim, int8_t* q);   // one row; e NULL: zeros

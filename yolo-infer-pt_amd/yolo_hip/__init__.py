@@ -10,7 +10,9 @@ those frames for a second-stage model (`Crops`);
 `Tracker` (yolo_hip.track) gives the detections of video streams identities across frames
 (`track`, `track_state`, `Tracks`), with re-identification by appearance when it is given
 embeddings (`track_reid`, `embed_quantize`, `embed_similarity`), and with an optimal assignment in
-place of the greedy association on request (`assign="optimal"`; `assign` is the batched solver alone); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
+place of the greedy association on request (`assign="optimal"`; `assign` is the batched solver alone), and
+with camera-motion compensation (`MotionEstimator`, yolo_hip.motion: the translation between consecutive
+frames from their luma; `warp` / `Tracker.update(motion=...)` moves the tracks by it); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
 those crops (`Classified`: class, confidence and embedding per detection); `Gallery` (yolo_hip.gallery)
 turns those embeddings into identities across streams and time (`gallery_search`, `gallery_enrol`,
 `gallery_workspace`: the k best rows of a large int8 gallery per query on the int8 MFMA). The drop-in module API lives in `nets.nn` / `utils.util`.
@@ -38,8 +40,11 @@ def __getattr__(name):
     if name in ("Classifier", "Classified"):
         from . import classify
         return getattr(classify, name)
+    if name in ("MotionEstimator", "Motion", "motion_state"):
+        from . import motion
+        return getattr(motion, name)
     if name in ("Tracker", "Tracks", "track", "track_state", "track_reid", "embed_quantize", "embed_similarity",
-                "assign"):
+                "assign", "warp"):
         # the function shares its name with its module, and importing the module binds the name
         # here: the module is callable as the function (yolo_hip/track.py, at its end)
         import importlib

@@ -96,6 +96,13 @@ _PROTOS = {
                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_track2_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "yh_track_warp": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "yh_track_warp_host": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int]),
+    "yh_motion_state_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "yh_motion": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                          c_void_p, c_void_p]),
+    "yh_motion_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                               c_void_p, c_int]),
     "yh_assign": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_assign_host": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "yh_embed_quantize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

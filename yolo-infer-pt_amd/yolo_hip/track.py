@@ -9,6 +9,7 @@ lies - no copy to the host, no synchronisation:
   track_state  the zeroed state tensor of `streams` streams
   Tracks       (dets, ids, det_index, counts) of one call
   track_reid   yh_track_reid: `track` with an appearance term (int8 features, cosine by int8 MFMA)
+  warp         yh_track_warp: a camera motion (yolo_hip.motion) applied to the tracks before a frame
   assign       yh_assign: batched maximum-weight assignment; `track(..., assign="optimal")` and
                `track_reid` likewise choose among an association's candidates with it (yh_track2)
   embed_quantize, embed_similarity   its two primitives, usable alone for gallery search
@@ -193,6 +194,43 @@ def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, 
     else:
         raise ValueError(f"yolo_hip.track: unsupported device {dev}")
     return o
+
+
+def warp(state, motion, max_tracks, reid_dim=None, stream_ids=None, threads=0):
+    """Move the tracks of a batch's streams by a camera motion, before the frame's `track` call
+    (yh_track_warp). state: a `track_state` tensor (reid_dim: as it was made), changed in place;
+    motion (B, 3) f32 rows of s, tx, ty - a `yolo_hip.motion.Motion` or its tensor: a track's centre
+    becomes s * c + t, its size, velocities and covariances scale with s (s * s); stream_ids as
+    `track`'s. A row with an id out of range, or a motion that is not finite or has s <= 0, changes
+    nothing; with s == 1 only the centres change. cuda tensors run the kernel on the current stream,
+    CPU tensors the host twin: the same bytes. -> state"""
+    from ._lib import check, lib
+    motion = getattr(motion, "motion", motion)
+    if not isinstance(motion, torch.Tensor) or motion.dim() != 2:
+        raise ValueError("yolo_hip.track: motion must be a (B, 3) tensor")
+    dev = motion.device
+    B = motion.shape[0]
+    _check("motion", motion, (B, 3), torch.float32, dev)
+    _check("state", state, (None, None), torch.int32, dev)
+    if stream_ids is not None:
+        _check("stream_ids", stream_ids, (B,), torch.int32, dev)
+    mt = int(max_tracks)
+    dim = 0 if reid_dim is None else _check_dim(reid_dim)
+    S, words = state.shape
+    want = _HDR + _FIELDS * mt if not dim else _reid_words(mt, dim)
+    if not 1 <= mt <= MAX_TRACKS or words != want:
+        raise ValueError(f"yolo_hip.track: state has {words} words per stream, expected {want} for max_tracks {mt}"
+                         f"{'' if not dim else f' and reid_dim {dim}'}")
+    L = lib()
+    args = (_ptr(state), S, mt, dim, _ptr(motion), _ptr(stream_ids), B)
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            check(L.yh_track_warp(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track_warp")
+    elif dev.type == "cpu":
+        check(L.yh_track_warp_host(*args, int(threads)), "track_warp_host")
+    else:
+        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+    return state
 
 
 def reid_workspace(batch, max_det, max_tracks, dim, device="cpu"):
@@ -411,6 +449,11 @@ class Tracker:
     assign: "greedy" (default) or "optimal", passed to every `track` / `track_reid` call (the
     attribute may be changed between frames).
 
+    Camera motion. update(..., motion=m) with a (B, 3) tensor of s, tx, ty per batch row - or the
+    `Motion` a `yolo_hip.motion.MotionEstimator` returns for the batch's frames - first moves the
+    tracks of the batch's streams by it (`warp`, same stream_ids, same stream), so that a moving
+    camera does not break the IoU association. post() takes none: the pipeline's hook has no frames.
+
     Nothing here reads a device value on the host. Outputs are allocated per call on the stream
     the call runs on (DetectPipeline marks its `extra` for the caller's stream)."""
 
@@ -458,7 +501,8 @@ class Tracker:
         high = (dets[:, :, 4] >= self.params.track_high) & live      # NaN padding compares false
         return torch.cumprod(high.to(torch.int32), dim=1).sum(dim=1).to(torch.int32)
 
-    def update(self, dets, counts=None, stream_ids=None, threads=0, embed=None, feat_counts=None, embed_total=None):
+    def update(self, dets, counts=None, stream_ids=None, threads=0, embed=None, feat_counts=None, embed_total=None,
+               motion=None):
         if counts is None:                       # a Detections
             dets, counts = dets.dets, dets.counts
         if self.reid_dim is None and (embed is not None or feat_counts is not None or embed_total is not None):
@@ -472,6 +516,8 @@ class Tracker:
             stream_ids = torch.tensor(host, dtype=torch.int32).to(self.device, non_blocking=True)
         elif stream_ids is None and isinstance(dets, torch.Tensor) and dets.dim() == 3 and dets.shape[0] > self.streams:
             raise ValueError(f"yolo_hip.Tracker: a batch of {dets.shape[0]} rows for {self.streams} streams")
+        if motion is not None:                   # the camera's motion first, on the same stream
+            warp(self.state, motion, self.max_tracks, reid_dim=self.reid_dim, stream_ids=stream_ids, threads=threads)
         if self.reid_dim is None:
             return track(dets, counts, self.state, self.params, stream_ids=stream_ids, max_out=self.max_out,
                          threads=threads, assign=self.assign)
