@@ -64,13 +64,28 @@ $(OBJDIR)/gallery_host.o: $(SRC)/track_host.h
 $(call objs,assign track): $(SRC)/assign.h $(SRC)/assign_host.h
 $(OBJDIR)/assign.o: $(SRC)/box_math.h
 $(OBJDIR)/track_host.o: $(SRC)/assign_host.h
+# the motion estimates promise the host twins' bytes down to the last fp32 operations; the compiler
+# pairs those into packed fp32 instructions (v_pk_mul_f32, v_pk_add_f32) when left to itself, and the
+# file is built without them: scalar fp32 only, one rounding per operation as the rules say
+$(OBJDIR)/motion.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # reports its argument errors through host_util.h's guarded(); its host functions use the pool
 $(OBJDIR)/preprocess.o: $(SRC)/host_util.h $(SRC)/host_parallel.h
 
 $(OUT): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
 
+# yh_motion_field's host twin under AddressSanitizer and UBSan: a stand-alone program, CPU only
+HOSTCC ?= c++
+build/motion_field_host_check: tools/motion_field_host_check.cpp $(SRC)/motion_host.cpp $(SRC)/motion_host.h \
+                               $(SRC)/box_math.h $(SRC)/host_parallel.h include/yolo_hip.h
+	mkdir -p build
+	$(HOSTCC) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off \
+	    -Iinclude -I$(SRC) tools/motion_field_host_check.cpp $(SRC)/motion_host.cpp -lpthread -o $@
+
+motion_field_host_check: build/motion_field_host_check
+	build/motion_field_host_check
+
 clean:
 	rm -rf build $(OUT)
 
-.PHONY: all clean
+.PHONY: all clean motion_field_host_check

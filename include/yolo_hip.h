@@ -57,7 +57,9 @@
  *                       of a stream, by block matching on luma thumbnails (BoT-SORT's global-motion step)
  *   yh_track_warp       no reference counterpart: that motion applied to a stream's tracks before the
  *                       frame's yh_track* call
- *   yh_motion_host, yh_track_warp_host   the same in host memory
+ *   yh_motion_field     no reference counterpart: translation plus zoom from a per-block motion field
+ *                       on the same state, for cameras that zoom, climb or descend
+ *   yh_motion_host, yh_motion_field_host, yh_track_warp_host   the same in host memory
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -840,6 +842,88 @@ int yh_motion(const yh_frame* frames, int batch, const int* stream_ids, void* st
 int yh_motion_host(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
                    int thumb_h, int thumb_w, int radius, int max_mad, float* motion, int32_t* sad, int threads);
 
+/* Zoom-aware camera motion from a block motion field (no reference counterpart: the rules below are
+ * the specification; tests/_motion_field_cases.py restates them in numpy). A second estimator beside
+ * yh_motion on the same state (yh_motion_state_bytes; header, thumbnail and staging area as above): a
+ * stream may be advanced by either call from frame to frame. Where yh_motion fits one translation,
+ * yh_motion_field searches per block of a grid_h x grid_w grid and fits translation plus isotropic
+ * zoom - the (s, tx, ty) yh_track_warp takes - to the blocks' shifts; where the field cannot be
+ * trusted the row is yh_motion's, byte for byte. frames, stream_ids, state, motion, sad: as yh_motion.
+ * With R = radius, wh = thumb_h - 2 R, ww = thumb_w - 2 R and C, P the current and stored thumbnail:
+ *
+ * 1. Luma and thumbnail: rules 1 and 2 of yh_motion.
+ * 2. Blocks. Block (p, q), index p * grid_w + q, covers the thumbnail rows R + (p * wh) / grid_h ..
+ *    R + ((p + 1) * wh) / grid_h and the columns R + (q * ww) / grid_w .. R + ((q + 1) * ww) / grid_w
+ *    (integer divisions, the end exclusive), n_b pixels. For every (dy, dx) in [-R, R]^2,
+ *    SAD_b(dy, dx) = sum |C[i][j] - P[i - dy][j - dx]| over the block's pixels; the block's best shift
+ *    minimises (SAD_b, |dy| + |dx|, dy, dx). The block tables sum to yh_motion's table SAD(dy, dx).
+ * 3. Votes. A block votes when its best shift is interior (|dy| < R and |dx| < R), its best SAD is at
+ *    most max_mad * n_b (max_mad < 0: no such condition), and max SAD_b - min SAD_b over its table is at
+ *    least min_contrast * n_b. Flat or blurred blocks, which the tie rule would send to (0, 0), and
+ *    blocks that found no match have no say.
+ * 4. Fit. Thumbnail pixel j spans [j, j + 1) on a continuous axis (its centre is at j + 1/2), so a
+ *    block's centre is ((c0 + c1) / 2, (r0 + r1) / 2) with its edge columns c0, c1 and rows r0, r1, and
+ *    the window's centre (thumb_w / 2, thumb_h / 2). Doubled, all are integers: X = c0 + c1 - thumb_w,
+ *    Y = r0 + r1 - thumb_h, U = 2 dx, V = 2 dy. The model is U = Tx + z X, V = Ty + z Y.
+ *    Consensus over every unordered pair (a, b), a < b, of voting blocks, in int64: with d* = *a - *b,
+ *    num = dX dU + dY dV and den = dX dX + dY dY (the pair's least-squares z = num / den),
+ *    TxN = (Ua + Ub) den - num (Xa + Xb), TyN alike (Tx = TxN / (2 den)). A voting block k is an inlier
+ *    of the pair when |2 den Uk - TxN - 2 num Xk| <= 4 tol den and |2 den Vk - TyN - 2 num Yk| <= 4 tol den:
+ *    both residuals at most tol thumbnail pixels. The winner has the most inliers; among equals the
+ *    smaller a, then the smaller b.
+ *    Refit over the winner's n inliers from the int64 sums Sx, Sy, Su, Sv, Sxx = sum (X X + Y Y),
+ *    Sxu = sum (X U + Y V): zn = n Sxu - Sx Su - Sy Sv, zd = n Sxx - Sx Sx - Sy Sy, then in fp32, one
+ *    rounding per operation, no FMA:
+ *      z = (float)zn / (float)zd;  s = 1.0f + z;
+ *      tu = ((float)Su - z * (float)Sx) / (float)(2 n);  tv alike        (thumbnail pixels at the centre)
+ *      tx = tu * ((float)W / (float)thumb_w) - z * (0.5f * (float)W);
+ *      ty = tv * ((float)H / (float)thumb_h) - z * (0.5f * (float)H).
+ *    The mapping: source pixel x spans [x, x + 1) as well, so thumbnail coordinate c is source
+ *    coordinate c W / thumb_w; content at c of the previous frame is at c + t + z (c - thumb_w / 2) now,
+ *    which is s c + (t - z thumb_w / 2) - about the source origin, as yh_track_warp applies it.
+ * 5. Fallback. motion[b] and sad[b] are what yh_motion writes for the summed table (its rules 3 - 5,
+ *    the same max_mad) when fewer than min_blocks blocks vote; when yh_motion's gate trips (max_mad >= 0
+ *    and the best global SAD > max_mad wh ww: a scene cut); when the winner has fewer than 2 inliers or
+ *    fewer than half the voters (2 n < voters); or when s lies outside [0.8, 1.25]. A 1 x 1 grid
+ *    therefore always equals yh_motion. Rows without a previous frame or with an invalid id: as
+ *    yh_motion.
+ * 6. Outputs. motion (batch, 3): (s, tx, ty) of the fit, or the fallback's row. sad (batch, 2): the
+ *    global (best SAD, SAD(0, 0)) of the summed table in either case. field (optional, NULL: not
+ *    written), (batch, grid_h * grid_w, 4) int32: per block dy, dx, its best SAD, flags - bit 0: the
+ *    block voted, bit 1: it is an inlier of the winner and the row is the fit's (clear in every
+ *    fallback row); all zero for a row without a previous frame or with an invalid id. Every byte of
+ *    all three is written. The state advances exactly as under yh_motion.
+ *
+ * yh_motion_field: asynchronous on `stream`, allocates nothing, never synchronises, no atomics; three
+ * launches per 32 frames (the thumbnails; one workgroup per block row and frame for the search; one
+ * per frame for the fit); state and workspace 4-byte aligned. workspace: caller-owned device memory
+ * of yh_motion_field_workspace_bytes(batch, grid_h, grid_w, radius) bytes (0 for illegal arguments),
+ * contents undefined before and after. yh_motion_field_host: the same bytes for host pointers.
+ * YH_EINVAL, nothing launched or written: whatever yh_motion rejects; p NULL; grid_h or grid_w < 1 or
+ * grid_h * grid_w > YH_MOTION_FIELD_MAX_BLOCKS; a block smaller than 4 x 4 (wh / grid_h < 4 or
+ * ww / grid_w < 4); min_contrast < 0, tol < 0 or > 64, min_blocks < 2; workspace NULL or too small
+ * (device entry, batch > 0); a block row beyond the search workgroup's LDS: with bh = (wh + grid_h - 1)
+ * / grid_h, (2 bh + 2 R) (thumb_w + 4) + 4 grid_w (2 R + 1)^2 + 4160 > YH_MOTION_FIELD_LDS. */
+#define YH_MOTION_FIELD_MAX_BLOCKS 256
+#define YH_MOTION_FIELD_LDS 163840
+typedef struct {
+    int grid_h, grid_w; /* blocks down and across the search window */
+    int radius;         /* R, thumbnail pixels */
+    int max_mad;        /* per pixel: the block vote's and the global gate's; < 0: none */
+    int min_contrast;   /* per pixel: the least spread of a voting block's SAD table */
+    int tol;            /* inlier tolerance, thumbnail pixels */
+    int min_blocks;     /* fewer voting blocks: fall back to yh_motion's row */
+    int reserved;       /* 0 */
+} yh_motion_field_params;
+size_t yh_motion_field_workspace_bytes(int batch, int grid_h, int grid_w, int radius);
+int yh_motion_field(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
+                    int thumb_h, int thumb_w, const yh_motion_field_params* p, float* motion /* (batch, 3) */,
+                    int32_t* sad /* (batch, 2) */, int32_t* field /* (batch, grid_h * grid_w, 4) or NULL */,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int yh_motion_field_host(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
+                         int thumb_h, int thumb_w, const yh_motion_field_params* p, float* motion, int32_t* sad,
+                         int32_t* field, int threads);
+
 /* Apply a motion to the tracks of a batch's streams before the frame's yh_track* call (no reference
  * counterpart; tests/_motion_cases.py restates the rule). state: yh_track's (reid_dim 0; a stream's
  * block is yh_track_state_bytes(1, max_tracks) bytes) or yh_track_reid's (reid_dim = its dim; the
@@ -854,7 +938,7 @@ int yh_motion_host(const yh_frame* frames, int batch, const int* stream_ids, voi
  * never written.
  * Translation plus isotropic scale is all the state can represent: its four filters (cx, cy, w, h) are
  * independent, and a rotation or shear would couple cx with cy. yh_motion only ever emits s = 1; the
- * scale is for callers with an estimate of their own (zoom telemetry).
+ * scale is yh_motion_field's, or a caller's own estimate (zoom telemetry).
  * yh_track_warp: device pointers, one workgroup per batch row, asynchronous on `stream`, allocates
  * nothing, never synchronises. yh_track_warp_host: the same bytes in host memory.
  * YH_EINVAL: a negative batch or streams, max_tracks outside [1, YH_TRACK_MAX_TRACKS], reid_dim neither

@@ -1,5 +1,6 @@
-"""What camera-motion compensation costs (yh_motion, yh_track_warp): 32 resident 1080 x 1920 frames,
-BGR and NV12, thumbnail 96 x 160, radius 8 and 16; 32 streams of 256 slots for the warp.
+"""What camera-motion compensation costs (yh_motion, yh_motion_field, yh_track_warp): 32 resident
+1080 x 1920 frames, BGR and NV12, thumbnail 96 x 160, radius 8 and 16, the field's grid 6 x 10; 32 streams
+of 256 slots for the warp.
 
   python tools/motion_bench.py [--out DIR] [--blocks 15] [--launches 20]
 
@@ -7,7 +8,8 @@ BGR and NV12, thumbnail 96 x 160, radius 8 and 16; 32 streams of 256 slots for t
      min-max over the blocks: yh_motion (its two launches together) per format and radius,
      yh_track_warp, and yh_letterbox_frames of the same frames to 384 x 640 for comparison.
  (b) per kernel, from a `rocprofv3 --kernel-trace` run per configuration (a fresh child each):
-     motion_thumb and motion_search apart, track_warp_kernel, letterbox_frames_u8. For the thumbnail
+     motion_thumb and motion_search apart, motion_field_search and motion_field_fit (yh_motion_field's
+     launches after the thumbnails), track_warp_kernel, letterbox_frames_u8. For the thumbnail
      kernel the source-pixel rate beside the letterbox kernel's on the same frames, and its share of
      the HBM floor: the bytes it must read (3 per BGR pixel, 1 per NV12 pixel) / 8 TB/s over its time.
 
@@ -33,6 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, "yolo-infer-pt_amd"))
 
 B, FH, FW = 32, 1080, 1920
 THUMB = (96, 160)
+GRID = (6, 10)          # yh_motion_field's block grid
 RECT = (384, 640)
 STREAMS, SLOTS = 32, 256
 HBM_BYTES_S = 8e12
@@ -71,6 +74,9 @@ def _calls(torch, ym, yt, frames, tstate, motion):
         est.estimate(frames[fmt][0])
         out = ym.Motion(torch.empty((B, 3), device=tstate.device), torch.empty((B, 2), dtype=torch.int32, device=tstate.device))
         cases[f"motion_{fmt}_r{r}"] = (lambda est=est, fr=frames[fmt][1], out=out: est.estimate(fr, out=out))
+        fest = ym.MotionEstimator(B, tstate.device, thumb=THUMB, radius=r, model="similarity", grid=GRID)
+        fest.estimate(frames[fmt][0])
+        cases[f"motion_field_{fmt}_r{r}"] = (lambda est=fest, fr=frames[fmt][1], out=out: est.estimate(fr, out=out))
     cases["track_warp"] = lambda: yt.warp(tstate, motion, SLOTS)
     canvas = torch.empty((B, 3) + RECT, dtype=torch.uint8, device=tstate.device)
     for fmt in ("bgr", "nv12"):
@@ -78,10 +84,12 @@ def _calls(torch, ym, yt, frames, tstate, motion):
     return cases
 
 
-def events_child(blocks, launches):
+def events_child(blocks, launches, match=""):
     torch, ym, yt, dev, frames, tstate, motion = _setup()
     res = {}
     for name, fn in _calls(torch, ym, yt, frames, tstate, motion).items():
+        if match not in name:
+            continue
         for _ in range(launches):
             fn()
         torch.cuda.synchronize()
@@ -128,7 +136,8 @@ def kernel_times(name, out_dir, calls):
     for fn in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
         with open(fn) as f:
             for row in csv.DictReader(f):
-                m = re.search(r"motion_thumb|motion_search|track_warp_kernel|letterbox_frames_u8", row["Kernel_Name"])
+                m = re.search(r"motion_thumb|motion_search|motion_field_search|motion_field_fit|track_warp_kernel|"
+                              r"letterbox_frames_u8", row["Kernel_Name"])
                 if m:
                     stats.setdefault(m.group(0), []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
     # the first calls warm up: the median of the rest
@@ -141,25 +150,31 @@ def main():
     ap.add_argument("--blocks", type=int, default=15)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--calls", type=int, default=40)
+    ap.add_argument("--match", default="", help="only the cases whose name contains this (motion_field, _r16, ...)")
     ap.add_argument("--child", default=None)
     ap.add_argument("--case", default=None)
     args = ap.parse_args()
     if args.child == "events":
-        return events_child(args.blocks, args.launches)
+        return events_child(args.blocks, args.launches, args.match)
     if args.child == "trace":
         return trace_child(args.case, args.calls)
     out_dir = args.out or os.path.join(ROOT, "build", "motion_bench")
     os.makedirs(out_dir, exist_ok=True)
     res = dict(shape=f"{B} frames {FW}x{FH}, thumbnail {THUMB[0]}x{THUMB[1]}, warp {STREAMS} streams x {SLOTS} slots",
-               a=json.loads(step(["--child", "events", "--blocks", str(args.blocks), "--launches", str(args.launches)],
-                                 300).strip().splitlines()[-1]))
+               a=json.loads(step(["--child", "events", "--blocks", str(args.blocks), "--launches", str(args.launches),
+                                  "--match", args.match], 300).strip().splitlines()[-1]))
     kern = {}
-    for name in [f"motion_{fmt}_r{r}" for fmt, r in CONFIGS] + ["track_warp", "letterbox_bgr_384x640", "letterbox_nv12_384x640"]:
+    for name in ([f"motion_{fmt}_r{r}" for fmt, r in CONFIGS] + [f"motion_field_{fmt}_r{r}" for fmt, r in CONFIGS] +
+                 ["track_warp", "letterbox_bgr_384x640", "letterbox_nv12_384x640"]):
+        if args.match not in name:
+            continue
         kern[name] = kernel_times(name, out_dir, args.calls)
     res["b"] = kern
     px = B * FH * FW
     rates = {}
     for fmt, bpp in (("bgr", 3), ("nv12", 1)):
+        if f"motion_{fmt}_r8" not in kern or f"letterbox_{fmt}_384x640" not in kern:
+            continue
         t = kern[f"motion_{fmt}_r8"]["motion_thumb"]["us"]["median"]
         lb = kern[f"letterbox_{fmt}_384x640"]["letterbox_frames_u8"]["us"]["median"]
         floor_us = px * bpp / HBM_BYTES_S * 1e6

@@ -467,6 +467,10 @@ int launch_track_warp(void* state, int streams, int max_tracks, int reid_dim, co
 // csrc/motion_host.h's yh_motion_check
 int launch_motion(const ::yh_motion_src* src, int batch, const int* stream_ids, void* state, int streams,
                   int thumb_h, int thumb_w, int radius, int max_mad, float* motion, int32_t* sad, hipStream_t s);
+// motion.hip: yh_motion_field, a thumbnail, a block-search and a fit launch per 32 frames
+int launch_motion_field(const ::yh_motion_src* src, int batch, const int* stream_ids, void* state, int streams,
+                        int thumb_h, int thumb_w, const ::yh_motion_field_params& p, float* motion, int32_t* sad,
+                        int32_t* field, void* workspace, hipStream_t s);
 // assign.hip: yh_assign, one wave per problem; the tracker's `optimal` instances above run the same solver
 int launch_assign(const int* weights, int problems, int T, int D, const int* t_counts, const int* d_counts,
                   int* row_of_slot, int* slot_of_row, hipStream_t s);

@@ -23,6 +23,24 @@
 //                (SAD, |dy| + |dx|, dy, dx) - a total order, so the spread over lanes and waves cannot
 //                matter -, thread 0 refines and writes the row's outputs, and all threads store the
 //                current thumbnail and the header into the stream's block.
+//
+// yh_motion_field, the zoom-aware estimate on the same state, is three launches per YH_MOTION_LAUNCH
+// frames: motion_thumb as above, then
+// motion_field_search  grid (grid_h, frames), 1024 threads: a workgroup owns one block row of one
+//                frame. It stages only that row's strip - its rows of the current thumbnail and those
+//                rows +- R of the previous one, same pitch and dword shift as motion_search - and a
+//                thread takes a work item (block, dy, c), four dx per item as above, and walks the
+//                block's dwords alone with the same inner step: a block is smaller than a wave, and
+//                lanes spread over it would spend more on adding their sums than on the sums. A
+//                block's columns begin and end anywhere, so a row's walk runs from the dword that holds
+//                the block's first column to the one that holds its last, with a mask on each. The blocks' tables stay
+//                in LDS; the workgroup writes each block's best key and table spread, and the sum of
+//                its tables - the block row's part of motion_search's table -, to the workspace.
+// motion_field_fit  one workgroup per frame, a launch later (every search workgroup has read the
+//                previous thumbnail by then): adds the grid_h partial tables, finds yh_motion's best
+//                key, spreads the pairs of voting blocks over the threads (a pair's model against
+//                every voter, int64), reduces the winner under its total order with lane exchanges,
+//                lets thread 0 refit and write the row, then stores the thumbnail and the header.
 // Built with -ffp-contract=off: the refinement must round exactly as in the host twin.
 #include <hip/hip_runtime.h>
 
@@ -121,6 +139,18 @@ __global__ __launch_bounds__(MT_THREADS) void motion_thumb(const MotionBatch mb)
         for (int c = c0; c < c1; ++c) sum += colsum[c - cb8];
         dst[j] = (unsigned char)yh_motion_mean(sum, (unsigned)(r1 - r0) * (unsigned)(c1 - c0));
     }
+}
+
+// the smallest 64-bit key of a wave's lanes, in every lane
+__device__ inline uint64_t wave_min_key(uint64_t best) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)best, d);
+        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(best >> 32), d);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        if (o < best) best = o;
+    }
+    return best;
 }
 
 // LDS of motion_search: the two thumbnails at pitch thumb_w + 4 (+ 8 bytes of slack each: the shift
@@ -232,13 +262,7 @@ __global__ __launch_bounds__(MS_THREADS) void motion_search(const MotionSearch m
             const uint64_t key = yh_motion_key((uint32_t)table[e], dyi - R, dxi - R);
             if (key < best) best = key;
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)best, d);
-            const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(best >> 32), d);
-            const uint64_t o = ((uint64_t)hi << 32) | lo;
-            if (o < best) best = o;
-        }
+        best = wave_min_key(best);
         if (lane == 0) wkey[wave] = best;
         __syncthreads();
         if (tid == 0) {
@@ -261,7 +285,327 @@ __global__ __launch_bounds__(MS_THREADS) void motion_search(const MotionSearch m
     if (tid < 4) reinterpret_cast<uint32_t*>(blk)[tid] = tid == 0 ? 1u : 0u;
 }
 
+// ---- yh_motion_field
+constexpr int MF_THREADS = 1024;
+constexpr int MF_WAVES = MF_THREADS / 64;
+constexpr int MF_TABLE = (2 * YH_MOTION_MAX_RADIUS + 1) * (2 * YH_MOTION_MAX_RADIUS + 1);
+constexpr size_t mf_align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+struct MotionField {
+    int hw[YH_MOTION_LAUNCH][2];   // source height, width of the launch's frames
+    const int* stream_ids;
+    unsigned char* state;
+    const unsigned char* staging;
+    unsigned char* ws;             // yh_mf_ws_row_bytes per row of the launch
+    float* motion;                 // the launch's first row
+    int32_t* sad;
+    int32_t* field;                // or NULL
+    yh_motion_field_params p;
+    int b0, streams, th, tw;
+};
+
+__global__ __launch_bounds__(MF_THREADS) void motion_field_search(const MotionField mf) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int bp = blockIdx.x, k = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int th = mf.th, tw = mf.tw, R = mf.p.radius, n = 2 * R + 1, gh = mf.p.grid_h, gw = mf.p.grid_w;
+    const int s = mf.stream_ids ? mf.stream_ids[k] : mf.b0 + k;   // uniform
+    if (s < 0 || s >= mf.streams) return;
+    const unsigned char* blk = mf.state + (size_t)s * yh_motion_stream_bytes(th, tw);
+    if (*reinterpret_cast<const uint32_t*>(blk) == 0u) return;     // no previous frame: the fit writes the row
+    const int wh = th - 2 * R, ww = tw - 2 * R;
+    const int r0 = R + yh_motion_edge(bp, wh, gh), bh = R + yh_motion_edge(bp + 1, wh, gh) - r0;
+    const int ph = bh + 2 * R;             // rows of the previous strip: thumbnail rows r0 - R .. r0 + bh + R
+    const int pitch = tw + 4;
+    const int padc = (4 - (R & 3)) & 3;    // column R of the current strip at a dword
+    unsigned char* lc = smem;
+    unsigned char* lp = smem + mf_align16((size_t)bh * pitch + 8);
+    int32_t* tables = reinterpret_cast<int32_t*>(lp + mf_align16((size_t)ph * pitch + 8));   // gw tables of n * n
+    const int rowdw = tw >> 2;
+    const uint32_t* gprev = reinterpret_cast<const uint32_t*>(blk + YH_MOTION_HDR) + (size_t)(r0 - R) * rowdw;
+    const uint32_t* gcur = reinterpret_cast<const uint32_t*>(mf.staging + (size_t)k * th * tw) + (size_t)r0 * rowdw;
+    for (int e = tid; e < ph * rowdw; e += MF_THREADS) {
+        const int i = e / rowdw, q = e - i * rowdw;
+        *reinterpret_cast<uint32_t*>(lp + i * pitch + 4 * q) = gprev[e];
+        if (i < bh) {
+            const uint32_t c = gcur[e];
+            unsigned char* d = lc + i * pitch + padc + 4 * q;
+            d[0] = (unsigned char)c; d[1] = (unsigned char)(c >> 8); d[2] = (unsigned char)(c >> 16); d[3] = (unsigned char)(c >> 24);
+        }
+    }
+    // the bytes around the rows, as in motion_search: read by a pair's second dword, dropped by the masks
+    for (int i = tid; i < ph; i += MF_THREADS) {
+        *reinterpret_cast<uint32_t*>(lp + i * pitch + tw) = 0u;
+        if (i < bh) {
+            unsigned char* d = lc + i * pitch + padc + tw;
+            for (int q = 0; q < 4 - padc; ++q) d[q] = 0;
+            for (int q = 0; q < padc; ++q) lc[i * pitch + q] = 0;
+        }
+    }
+    if (tid < 8) {
+        lc[bh * pitch + tid] = 0;
+        lp[ph * pitch + tid] = 0;
+    }
+    // per block: the dwords of the current strip that hold its columns c0 .. c1 - 1 (first, count), and
+    // the bytes of the first and the last that belong to it
+    uint32_t* bcol = reinterpret_cast<uint32_t*>(tables + (size_t)gw * n * n);   // gw x 4
+    for (int bq = tid; bq < gw; bq += MF_THREADS) {
+        const int c0 = R + yh_motion_edge(bq, ww, gw), c1 = R + yh_motion_edge(bq + 1, ww, gw);
+        const int d0 = (padc + c0) >> 2, rem = ((padc + c1 - 1) & 3) + 1;
+        bcol[4 * bq] = (uint32_t)d0;
+        bcol[4 * bq + 1] = (uint32_t)(((padc + c1 - 1) >> 2) - d0 + 1);
+        bcol[4 * bq + 2] = 0xffffffffu << (8 * ((padc + c0) & 3));
+        bcol[4 * bq + 3] = rem == 4 ? 0xffffffffu : (1u << (8 * rem)) - 1u;
+    }
+    __syncthreads();
+    // A thread takes an item (block, dy, c) - the block's four candidates whose previous-frame column
+    // offset R - dx is 4 c + 0 .. 3 - and walks the block's dwords alone. A block is a few dozen dwords,
+    // less than a wave: spread over lanes, the exchange that adds the lanes' sums would cost more than
+    // the sums. Neighbouring threads differ in c, then dy: one current dword for all of them (a
+    // broadcast), consecutive previous dwords. A row's pair shares its dword with the next pair.
+    const int cchunks = ((2 * R) >> 2) + 1, per = n * cchunks;
+    const uint32_t* cdw = reinterpret_cast<const uint32_t*>(lc);
+    const uint32_t* pdw = reinterpret_cast<const uint32_t*>(lp);
+    const int pdwp = pitch >> 2, cofs = (padc + R) >> 2;
+    for (int item = tid; item < gw * per; item += MF_THREADS) {
+        const int bq = item / per, rest = item - bq * per;
+        const int dyi = rest / cchunks, c = rest - dyi * cchunks;
+        const int d0 = (int)bcol[4 * bq], nq = (int)bcol[4 * bq + 1];
+        const uint32_t firstmask = bcol[4 * bq + 2], lastmask = bcol[4 * bq + 3];
+        const uint32_t* crow = cdw + d0;
+        const uint32_t* prow = pdw + (2 * R - dyi) * pdwp + c + (d0 - cofs);   // strip row wi + R - dy; d0 >= cofs: c0 >= R
+        uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+        for (int wi = 0; wi < bh; ++wi) {
+            uint32_t lo = prow[0];
+            for (int q = 0; q < nq; ++q) {
+                const uint32_t m = (q == 0 ? firstmask : 0xffffffffu) & (q == nq - 1 ? lastmask : 0xffffffffu);
+                const uint32_t cv = crow[q] & m;
+                const uint32_t hi = prow[q + 1];
+                a0 = __builtin_amdgcn_sad_u8(cv, lo & m, a0);
+                a1 = __builtin_amdgcn_sad_u8(cv, __builtin_amdgcn_alignbyte(hi, lo, 1) & m, a1);
+                a2 = __builtin_amdgcn_sad_u8(cv, __builtin_amdgcn_alignbyte(hi, lo, 2) & m, a2);
+                a3 = __builtin_amdgcn_sad_u8(cv, __builtin_amdgcn_alignbyte(hi, lo, 3) & m, a3);
+                lo = hi;
+            }
+            crow += pdwp;
+            prow += pdwp;
+        }
+        int32_t* t = tables + (bq * n + dyi) * n;
+        const int o = 4 * c;                       // o + j = R - dx
+        t[2 * R - o] = (int32_t)a0;
+        if (o + 1 <= 2 * R) t[2 * R - o - 1] = (int32_t)a1;
+        if (o + 2 <= 2 * R) t[2 * R - o - 2] = (int32_t)a2;
+        if (o + 3 <= 2 * R) t[2 * R - o - 3] = (int32_t)a3;
+    }
+    __syncthreads();
+    unsigned char* wrow = mf.ws + (size_t)k * yh_mf_ws_row_bytes(gh, gw, R);
+    // a wave per block: its best key and the spread of its table
+    for (int bq = wave; bq < gw; bq += MF_WAVES) {
+        const int32_t* t = tables + bq * n * n;
+        uint64_t best = ~(uint64_t)0;
+        uint32_t top = 0;
+        for (int e = lane; e < n * n; e += 64) {
+            const int dyi = e / n, dxi = e - dyi * n;
+            const uint32_t v = (uint32_t)t[e];
+            const uint64_t key = yh_motion_key(v, dyi - R, dxi - R);
+            if (key < best) best = key;
+            top = v > top ? v : top;
+        }
+        best = wave_min_key(best);
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)top, d);
+            top = o > top ? o : top;
+        }
+        if (lane == 0) {
+            int32_t* rec = reinterpret_cast<int32_t*>(wrow) + (size_t)(bp * gw + bq) * 4;
+            rec[0] = yh_motion_key_dy(best);
+            rec[1] = yh_motion_key_dx(best);
+            rec[2] = (int32_t)(best >> 32);
+            rec[3] = (int32_t)(top - (uint32_t)(best >> 32));
+        }
+    }
+    // the block row's part of the global table
+    int32_t* part = reinterpret_cast<int32_t*>(wrow + (size_t)gh * gw * 16) + (size_t)bp * n * n;
+    for (int e = tid; e < n * n; e += MF_THREADS) {
+        int32_t sum = 0;
+        for (int bq = 0; bq < gw; ++bq) sum += tables[bq * n * n + e];
+        part[e] = sum;
+    }
+}
+
+__global__ __launch_bounds__(MF_THREADS) void motion_field_fit(const MotionField mf) {
+    __shared__ int32_t table[MF_TABLE];
+    __shared__ int32_t rec[YH_MOTION_FIELD_MAX_BLOCKS * 4];
+    __shared__ yh_mf_pt pts[YH_MOTION_FIELD_MAX_BLOCKS];
+    __shared__ int32_t flags[YH_MOTION_FIELD_MAX_BLOCKS];
+    __shared__ int32_t voter[YH_MOTION_FIELD_MAX_BLOCKS];
+    __shared__ uint64_t wkey[MF_WAVES], wwin[MF_WAVES];
+    __shared__ int nvoters;
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int th = mf.th, tw = mf.tw, R = mf.p.radius, n = 2 * R + 1, gh = mf.p.grid_h, gw = mf.p.grid_w, NB = gh * gw;
+    float* mo = mf.motion + (size_t)k * 3;
+    int32_t* so = mf.sad + (size_t)k * 2;
+    int32_t* fo = mf.field ? mf.field + (size_t)k * NB * 4 : nullptr;
+    const int s = mf.stream_ids ? mf.stream_ids[k] : mf.b0 + k;   // uniform
+    const bool valid = s >= 0 && s < mf.streams;
+    unsigned char* blk = mf.state + (size_t)(valid ? s : 0) * yh_motion_stream_bytes(th, tw);
+    const uint32_t have = valid ? *reinterpret_cast<const uint32_t*>(blk) : 0u;   // uniform
+    if (!have) {
+        if (tid == 0) {
+            mo[0] = 1.0f; mo[1] = 0.0f; mo[2] = 0.0f;
+            so[0] = 0; so[1] = 0;
+        }
+        if (fo)
+            for (int e = tid; e < NB * 4; e += MF_THREADS) fo[e] = 0;
+        if (!valid) return;
+    } else {
+        const unsigned char* wrow = mf.ws + (size_t)k * yh_mf_ws_row_bytes(gh, gw, R);
+        const int32_t* grec = reinterpret_cast<const int32_t*>(wrow);
+        const int32_t* part = reinterpret_cast<const int32_t*>(wrow + (size_t)NB * 16);
+        uint64_t best = ~(uint64_t)0;
+        for (int e = tid; e < n * n; e += MF_THREADS) {
+            int32_t sum = 0;
+            for (int p = 0; p < gh; ++p) sum += part[(size_t)p * n * n + e];
+            table[e] = sum;
+            const int dyi = e / n, dxi = e - dyi * n;
+            const uint64_t key = yh_motion_key((uint32_t)sum, dyi - R, dxi - R);
+            if (key < best) best = key;
+        }
+        best = wave_min_key(best);
+        if (lane == 0) wkey[wave] = best;
+        for (int b = tid; b < NB; b += MF_THREADS) {
+            int nb;
+            for (int q = 0; q < 4; ++q) rec[4 * b + q] = grec[4 * b + q];
+            yh_mf_block_pt(b / gw, b % gw, th, tw, gh, gw, R, grec + 4 * b, &pts[b], &nb);
+            flags[b] = yh_mf_votes(grec[4 * b], grec[4 * b + 1], grec[4 * b + 2], grec[4 * b + 3], nb, R, mf.p.max_mad,
+                                   mf.p.min_contrast) ? 1 : 0;
+        }
+        __syncthreads();
+        if (wave == 0) {   // the voters' indices in ascending order
+            int count = 0;
+            for (int b0 = 0; b0 < NB; b0 += 64) {
+                const bool v = b0 + lane < NB && flags[b0 + lane];
+                const unsigned long long mask = __ballot(v);
+                if (v) voter[count + __popcll(mask & ((1ull << lane) - 1ull))] = b0 + lane;
+                count += __popcll(mask);
+            }
+            if (lane == 0) nvoters = count;
+        }
+        __syncthreads();
+        const int nv = nvoters;
+        uint64_t win = 0;   // the largest pair key; found as the smallest complement
+        if (nv >= mf.p.min_blocks) {
+            for (int e = tid; e < nv * (nv - 1) / 2; e += MF_THREADS) {
+                int ia = 0, r = e;   // pair e of the list (0, 1), (0, 2), .., (1, 2), ..
+                while (r >= nv - 1 - ia) {
+                    r -= nv - 1 - ia;
+                    ++ia;
+                }
+                const int a = voter[ia], b = voter[ia + 1 + r];
+                const yh_mf_pair pm = yh_mf_pair_fit(pts[a], pts[b]);
+                int cnt = 0;
+                for (int v = 0; v < nv; ++v) cnt += yh_mf_inlier(pm, pts[voter[v]], mf.p.tol) ? 1 : 0;
+                const uint64_t key = yh_mf_pair_key(cnt, a, b);
+                if (key > win) win = key;
+            }
+            win = ~wave_min_key(~win);
+        }
+        if (lane == 0) wwin[wave] = win;
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < MF_WAVES; ++w) {
+                if (wkey[w] < best) best = wkey[w];
+                if (wwin[w] > win) win = wwin[w];
+            }
+            float m[3];
+            int32_t sv[2];
+            yh_motion_result(table, R, yh_motion_key_dy(best), yh_motion_key_dx(best), mf.hw[k][0], mf.hw[k][1], th, tw,
+                             mf.p.max_mad, m, sv);
+            const bool cut = mf.p.max_mad >= 0 && (long long)sv[0] > (long long)mf.p.max_mad * (th - 2 * R) * (tw - 2 * R);
+            float fm[3];
+            if (nv >= mf.p.min_blocks && !cut &&
+                yh_mf_refit(pts, flags, NB, nv, win, mf.p.tol, mf.hw[k][0], mf.hw[k][1], th, tw, fm)) {
+                m[0] = fm[0]; m[1] = fm[1]; m[2] = fm[2];
+            }
+            mo[0] = m[0]; mo[1] = m[1]; mo[2] = m[2];
+            so[0] = sv[0]; so[1] = sv[1];
+        }
+        __syncthreads();   // thread 0 marked the inliers
+        if (fo)
+            for (int e = tid; e < NB * 4; e += MF_THREADS) fo[e] = (e & 3) == 3 ? flags[e >> 2] : rec[e];
+    }
+    // the current thumbnail becomes the stream's
+    const uint32_t* gcur = reinterpret_cast<const uint32_t*>(mf.staging + (size_t)k * th * tw);
+    uint32_t* gout = reinterpret_cast<uint32_t*>(blk + YH_MOTION_HDR);
+    for (int e = tid; e < (th * tw) >> 2; e += MF_THREADS) gout[e] = gcur[e];
+    if (tid < 4) reinterpret_cast<uint32_t*>(blk)[tid] = tid == 0 ? 1u : 0u;
+}
+
+// the thumbnail launch of rows b0 .. b0 + nb - 1, shared by both estimators
+int launch_thumbs(const yh_motion_src* src, int b0, int nb, const int* stream_ids, unsigned char* staging, int streams,
+                  int thumb_h, int thumb_w, hipStream_t s) {
+    MotionBatch mb{};
+    int wmax = 1;
+    for (int k = 0; k < nb; ++k) {
+        const yh_motion_src& f = src[b0 + k];
+        mb.fr[k] = MotionFrame{f.p0, f.h, f.w, f.stride0, f.format,
+                               (reinterpret_cast<uintptr_t>(f.p0) | (uintptr_t)f.stride0) % 8 == 0 ? 1 : 0};
+        wmax = f.w > wmax ? f.w : wmax;
+    }
+    // thumbnail columns per workgroup: their source columns (from the 8-aligned column at or
+    // below the first) fit the workgroup's MT_COLS column sums
+    int chunks = 1, tcw = thumb_w;
+    while (tcw > 1 && ((long long)tcw * wmax + thumb_w - 1) / thumb_w + 1 + MT_PX > MT_COLS) {
+        ++chunks;
+        tcw = (thumb_w + chunks - 1) / chunks;
+    }
+    if (((long long)tcw * wmax + thumb_w - 1) / thumb_w + 1 + MT_PX > MT_COLS) return (int)hipErrorInvalidValue;
+    chunks = (thumb_w + tcw - 1) / tcw;
+    mb.stream_ids = stream_ids ? stream_ids + b0 : nullptr;
+    mb.staging = staging;
+    mb.b0 = b0; mb.streams = streams; mb.th = thumb_h; mb.tw = thumb_w; mb.chunks = chunks; mb.tcw = tcw;
+    hipLaunchKernelGGL(motion_thumb, dim3((unsigned)(thumb_h * chunks), (unsigned)nb), dim3(MT_THREADS), 0, s, mb);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
+
+int launch_motion_field(const yh_motion_src* src, int batch, const int* stream_ids, void* state, int streams,
+                        int thumb_h, int thumb_w, const yh_motion_field_params& p, float* motion, int32_t* sad,
+                        int32_t* field, void* workspace, hipStream_t s) {
+    // arguments were checked by yh_motion_field (yh_motion_check, yh_motion_field_check, the workspace)
+    if (batch <= 0) return 0;
+    const size_t lds = yh_mf_lds_bytes(thumb_h, thumb_w, p.grid_h, p.grid_w, p.radius);
+    if (lds > YH_MOTION_FIELD_LDS) return (int)hipErrorInvalidValue;
+    if (int rc = lds_optin(reinterpret_cast<const void*>(motion_field_search), YH_MOTION_FIELD_LDS)) return rc;
+    unsigned char* base = static_cast<unsigned char*>(state);
+    unsigned char* staging = base + yh_motion_staging_offset(streams, thumb_h, thumb_w);
+    const int NB = p.grid_h * p.grid_w;
+    for (int b0 = 0; b0 < batch; b0 += YH_MOTION_LAUNCH) {
+        const int nb = batch - b0 < YH_MOTION_LAUNCH ? batch - b0 : YH_MOTION_LAUNCH;
+        if (int rc = launch_thumbs(src, b0, nb, stream_ids, staging, streams, thumb_h, thumb_w, s)) return rc;
+        MotionField mf{};
+        for (int k = 0; k < nb; ++k) {
+            mf.hw[k][0] = src[b0 + k].h;
+            mf.hw[k][1] = src[b0 + k].w;
+        }
+        mf.stream_ids = stream_ids ? stream_ids + b0 : nullptr;
+        mf.state = base;
+        mf.staging = staging;
+        mf.ws = static_cast<unsigned char*>(workspace);
+        mf.motion = motion + (size_t)b0 * 3;
+        mf.sad = sad + (size_t)b0 * 2;
+        mf.field = field ? field + (size_t)b0 * NB * 4 : nullptr;
+        mf.p = p;
+        mf.b0 = b0; mf.streams = streams; mf.th = thumb_h; mf.tw = thumb_w;
+        hipLaunchKernelGGL(motion_field_search, dim3((unsigned)p.grid_h, (unsigned)nb), dim3(MF_THREADS), lds, s, mf);
+        if (hipError_t e = hipGetLastError()) return (int)e;
+        hipLaunchKernelGGL(motion_field_fit, dim3((unsigned)nb), dim3(MF_THREADS), 0, s, mf);
+        if (hipError_t e = hipGetLastError()) return (int)e;
+    }
+    return 0;
+}
 
 int launch_motion(const yh_motion_src* src, int batch, const int* stream_ids, void* state, int streams, int thumb_h,
                   int thumb_w, int radius, int max_mad, float* motion, int32_t* sad, hipStream_t s) {
@@ -273,32 +617,13 @@ int launch_motion(const yh_motion_src* src, int batch, const int* stream_ids, vo
     unsigned char* staging = base + yh_motion_staging_offset(streams, thumb_h, thumb_w);
     for (int b0 = 0; b0 < batch; b0 += YH_MOTION_LAUNCH) {
         const int nb = batch - b0 < YH_MOTION_LAUNCH ? batch - b0 : YH_MOTION_LAUNCH;
-        MotionBatch mb{};
+        if (int rc = launch_thumbs(src, b0, nb, stream_ids, staging, streams, thumb_h, thumb_w, s)) return rc;
         MotionSearch ms{};
-        int wmax = 1;
         for (int k = 0; k < nb; ++k) {
-            const yh_motion_src& f = src[b0 + k];
-            mb.fr[k] = MotionFrame{f.p0, f.h, f.w, f.stride0, f.format,
-                                   (reinterpret_cast<uintptr_t>(f.p0) | (uintptr_t)f.stride0) % 8 == 0 ? 1 : 0};
-            ms.hw[k][0] = f.h;
-            ms.hw[k][1] = f.w;
-            wmax = f.w > wmax ? f.w : wmax;
+            ms.hw[k][0] = src[b0 + k].h;
+            ms.hw[k][1] = src[b0 + k].w;
         }
-        // thumbnail columns per workgroup: their source columns (from the 8-aligned column at or
-        // below the first) fit the workgroup's MT_COLS column sums
-        int chunks = 1, tcw = thumb_w;
-        while (tcw > 1 && ((long long)tcw * wmax + thumb_w - 1) / thumb_w + 1 + MT_PX > MT_COLS) {
-            ++chunks;
-            tcw = (thumb_w + chunks - 1) / chunks;
-        }
-        if (((long long)tcw * wmax + thumb_w - 1) / thumb_w + 1 + MT_PX > MT_COLS) return (int)hipErrorInvalidValue;
-        chunks = (thumb_w + tcw - 1) / tcw;
-        mb.stream_ids = stream_ids ? stream_ids + b0 : nullptr;
-        mb.staging = staging;
-        mb.b0 = b0; mb.streams = streams; mb.th = thumb_h; mb.tw = thumb_w; mb.chunks = chunks; mb.tcw = tcw;
-        hipLaunchKernelGGL(motion_thumb, dim3((unsigned)(thumb_h * chunks), (unsigned)nb), dim3(MT_THREADS), 0, s, mb);
-        if (hipError_t e = hipGetLastError()) return (int)e;
-        ms.stream_ids = mb.stream_ids;
+        ms.stream_ids = stream_ids ? stream_ids + b0 : nullptr;
         ms.state = base;
         ms.staging = staging;
         ms.motion = motion + (size_t)b0 * 3;

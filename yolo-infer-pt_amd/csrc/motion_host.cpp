@@ -139,3 +139,123 @@ int yh_motion_host_run(const yh_motion_src* src, int batch, const int* stream_id
     }
     return 0;
 }
+
+// ---- yh_motion_field: the block motion field and the similarity fit (rules at yh_motion_field in
+// include/yolo_hip.h). As the text says it: a table per block, their sum, the votes, every pair of
+// voters against every voter, the refit.
+const char* yh_motion_field_check(const yh_motion_field_params* p, int thumb_h, int thumb_w) {
+    if (!p) return "motion_field: null params";
+    // radius and the thumbnail were checked by yh_motion_check
+    if (p->grid_h < 1 || p->grid_w < 1 || (long long)p->grid_h * p->grid_w > YH_MOTION_FIELD_MAX_BLOCKS)
+        return "motion_field: grid_h, grid_w must be >= 1 and grid_h * grid_w <= " YH_STR(YH_MOTION_FIELD_MAX_BLOCKS);
+    if ((thumb_h - 2 * p->radius) / p->grid_h < 4 || (thumb_w - 2 * p->radius) / p->grid_w < 4)
+        return "motion_field: a block must be at least 4 x 4 thumbnail pixels";
+    if (p->min_contrast < 0) return "motion_field: min_contrast must be >= 0";
+    if (p->tol < 0 || p->tol > 64) return "motion_field: tol must be in [0, 64]";
+    if (p->min_blocks < 2) return "motion_field: min_blocks must be >= 2";
+    if (yh_mf_lds_bytes(thumb_h, thumb_w, p->grid_h, p->grid_w, p->radius) > YH_MOTION_FIELD_LDS)
+        return "motion_field: a block row's strips and tables exceed YH_MOTION_FIELD_LDS (" YH_STR(YH_MOTION_FIELD_LDS) ")";
+    return nullptr;
+}
+
+int yh_motion_field_host_run(const yh_motion_src* src, int batch, const int* stream_ids, void* state, int streams,
+                             int thumb_h, int thumb_w, const yh_motion_field_params* p, float* motion, int32_t* sad,
+                             int32_t* field, int threads) {
+    const int R = p->radius, n = 2 * R + 1, gh = p->grid_h, gw = p->grid_w, NB = gh * gw;
+    const int wh = thumb_h - 2 * R, ww = thumb_w - 2 * R;
+    const size_t pixels = (size_t)thumb_h * thumb_w;
+    const size_t stride = yh_motion_stream_bytes(thumb_h, thumb_w);
+    unsigned char* base = static_cast<unsigned char*>(state);
+    unsigned char* staging = base + yh_motion_staging_offset(streams, thumb_h, thumb_w);
+    auto row = [&](int b) {
+        float* m = motion + (size_t)b * 3;
+        int32_t* so = sad + (size_t)b * 2;
+        int32_t* fo = field ? field + (size_t)b * NB * 4 : nullptr;
+        m[0] = 1.0f; m[1] = 0.0f; m[2] = 0.0f;
+        so[0] = 0; so[1] = 0;
+        if (fo) std::memset(fo, 0, (size_t)NB * 16);
+        const int s = stream_ids ? stream_ids[b] : b;
+        if (s < 0 || s >= streams) return;
+        std::vector<unsigned char> cur(pixels);
+        thumbnail(src[b], thumb_h, thumb_w, cur.data());
+        unsigned char* blk = base + (size_t)s * stride;
+        uint32_t have;
+        std::memcpy(&have, blk, 4);
+        unsigned char* prev = blk + YH_MOTION_HDR;
+        if (have) {
+            std::vector<int32_t> table((size_t)n * n, 0), bt((size_t)n * n), rec((size_t)NB * 4), flags(NB);
+            std::vector<yh_mf_pt> pts(NB);
+            int voters = 0;
+            for (int bp = 0; bp < gh; ++bp)
+                for (int bq = 0; bq < gw; ++bq) {
+                    const int r0 = R + yh_motion_edge(bp, wh, gh), r1 = R + yh_motion_edge(bp + 1, wh, gh);
+                    const int c0 = R + yh_motion_edge(bq, ww, gw), c1 = R + yh_motion_edge(bq + 1, ww, gw);
+                    uint64_t best = ~(uint64_t)0;
+                    uint32_t top = 0;
+                    for (int dy = -R; dy <= R; ++dy)
+                        for (int dx = -R; dx <= R; ++dx) {
+                            uint32_t acc = 0;
+                            for (int i = r0; i < r1; ++i) {
+                                const unsigned char* c = cur.data() + (size_t)i * thumb_w;
+                                const unsigned char* q = prev + (size_t)(i - dy) * thumb_w - dx;
+                                for (int j = c0; j < c1; ++j) acc += (uint32_t)(c[j] > q[j] ? c[j] - q[j] : q[j] - c[j]);
+                            }
+                            bt[(size_t)(dy + R) * n + (dx + R)] = (int32_t)acc;
+                            const uint64_t key = yh_motion_key(acc, dy, dx);
+                            if (key < best) best = key;
+                            if (acc > top) top = acc;
+                        }
+                    for (size_t e = 0; e < bt.size(); ++e) table[e] += bt[e];
+                    const int k = bp * gw + bq;
+                    int32_t* r = rec.data() + (size_t)k * 4;
+                    r[0] = yh_motion_key_dy(best);
+                    r[1] = yh_motion_key_dx(best);
+                    r[2] = (int32_t)(best >> 32);
+                    r[3] = (int32_t)(top - (uint32_t)(best >> 32));
+                    int nb;
+                    yh_mf_block_pt(bp, bq, thumb_h, thumb_w, gh, gw, R, r, &pts[k], &nb);
+                    flags[k] = yh_mf_votes(r[0], r[1], r[2], r[3], nb, R, p->max_mad, p->min_contrast) ? 1 : 0;
+                    voters += flags[k];
+                }
+            uint64_t gbest = ~(uint64_t)0;
+            for (int dy = -R; dy <= R; ++dy)
+                for (int dx = -R; dx <= R; ++dx) {
+                    const uint64_t key = yh_motion_key((uint32_t)table[(size_t)(dy + R) * n + (dx + R)], dy, dx);
+                    if (key < gbest) gbest = key;
+                }
+            yh_motion_result(table.data(), R, yh_motion_key_dy(gbest), yh_motion_key_dx(gbest), src[b].h, src[b].w,
+                             thumb_h, thumb_w, p->max_mad, m, so);
+            const bool cut = p->max_mad >= 0 && (long long)so[0] > (long long)p->max_mad * wh * ww;
+            if (voters >= p->min_blocks && !cut) {
+                uint64_t win = 0;
+                for (int a = 0; a < NB; ++a)
+                    for (int c = a + 1; c < NB; ++c) {
+                        if (!flags[a] || !flags[c]) continue;
+                        const yh_mf_pair pm = yh_mf_pair_fit(pts[a], pts[c]);
+                        int cnt = 0;
+                        for (int k = 0; k < NB; ++k) cnt += flags[k] && yh_mf_inlier(pm, pts[k], p->tol) ? 1 : 0;
+                        const uint64_t key = yh_mf_pair_key(cnt, a, c);
+                        if (key > win) win = key;
+                    }
+                float fm[3];
+                if (yh_mf_refit(pts.data(), flags.data(), NB, voters, win, p->tol, src[b].h, src[b].w, thumb_h, thumb_w, fm)) {
+                    m[0] = fm[0]; m[1] = fm[1]; m[2] = fm[2];
+                }
+            }
+            if (fo)
+                for (int k = 0; k < NB; ++k) {
+                    fo[4 * k] = rec[4 * k]; fo[4 * k + 1] = rec[4 * k + 1]; fo[4 * k + 2] = rec[4 * k + 2];
+                    fo[4 * k + 3] = flags[k];
+                }
+        }
+        const uint32_t hdr[4] = {1u, 0u, 0u, 0u};
+        std::memcpy(blk, hdr, YH_MOTION_HDR);
+        std::memcpy(prev, cur.data(), pixels);
+        std::memcpy(staging + (size_t)(b % YH_MOTION_LAUNCH) * pixels, cur.data(), pixels);
+    };
+    for (int b0 = 0; b0 < batch; b0 += YH_MOTION_LAUNCH) {
+        const int nb = batch - b0 < YH_MOTION_LAUNCH ? batch - b0 : YH_MOTION_LAUNCH;
+        yh::parallel_strided(nb, threads, [&](int k) { row(b0 + k); });
+    }
+    return 0;
+}

@@ -220,6 +220,45 @@ int yh_motion_host(const yh_frame* frames, int batch, const int* stream_ids, voi
     });
 }
 
+size_t yh_motion_field_workspace_bytes(int batch, int grid_h, int grid_w, int radius) {
+    if (batch < 0 || grid_h < 1 || grid_w < 1 || (long long)grid_h * grid_w > YH_MOTION_FIELD_MAX_BLOCKS || radius < 1 ||
+        radius > YH_MOTION_MAX_RADIUS)
+        return 0;
+    return (size_t)std::min(batch, (int)YH_MOTION_LAUNCH) * yh_mf_ws_row_bytes(grid_h, grid_w, radius);
+}
+
+int yh_motion_field(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams, int thumb_h,
+                    int thumb_w, const yh_motion_field_params* p, float* motion, int32_t* sad, int32_t* field,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        yh::require(p, "motion_field: null params");
+        std::vector<yh_motion_src> src((size_t)std::max(batch, 0));
+        checked(yh_motion_check(frames, batch, state, streams, thumb_h, thumb_w, p->radius, motion, sad, src.data()));
+        checked(yh_motion_field_check(p, thumb_h, thumb_w));
+        yh::require(batch == 0 || workspace, "motion_field: null workspace");
+        yh::require(workspace_bytes >= yh_motion_field_workspace_bytes(batch, p->grid_h, p->grid_w, p->radius),
+                    "motion_field: workspace too small");
+        yh::require(((uintptr_t)state | (uintptr_t)workspace) % 4 == 0,
+                    "motion_field: state and workspace must be 4-byte aligned on the device");
+        const int rc = yh::launch_motion_field(src.data(), batch, stream_ids, state, streams, thumb_h, thumb_w, *p, motion,
+                                               sad, field, workspace, (hipStream_t)stream);
+        if (rc != 0) throw Fail(YH_EHIP, std::string("motion_field launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int yh_motion_field_host(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
+                         int thumb_h, int thumb_w, const yh_motion_field_params* p, float* motion, int32_t* sad,
+                         int32_t* field, int threads) {
+    return guarded([&] {
+        yh::require(p, "motion_field: null params");
+        std::vector<yh_motion_src> src((size_t)std::max(batch, 0));
+        checked(yh_motion_check(frames, batch, state, streams, thumb_h, thumb_w, p->radius, motion, sad, src.data()));
+        checked(yh_motion_field_check(p, thumb_h, thumb_w));
+        yh_motion_field_host_run(src.data(), batch, stream_ids, state, streams, thumb_h, thumb_w, p, motion, sad, field,
+                                 threads);
+    });
+}
+
 int yh_assign(const int32_t* weights, int problems, int T, int D, const int32_t* t_counts, const int32_t* d_counts,
               int32_t* row_of_slot, int32_t* slot_of_row, void* stream) {
     return guarded([&] {

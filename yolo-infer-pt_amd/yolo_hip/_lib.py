@@ -44,6 +44,11 @@ class YhFrame(ctypes.Structure):
     ]
 
 
+class YhMotionFieldParams(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("grid_h", "grid_w", "radius", "max_mad", "min_contrast", "tol", "min_blocks",
+                                     "reserved")]
+
+
 # name -> (restype, argtypes); mirrors include/yolo_hip.h
 _PROTOS = {
     "yh_abi_version": (c_int, []),
@@ -103,6 +108,11 @@ _PROTOS = {
                           c_void_p, c_void_p]),
     "yh_motion_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                c_void_p, c_int]),
+    "yh_motion_field_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "yh_motion_field": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "yh_motion_field_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_int]),
     "yh_assign": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_assign_host": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "yh_embed_quantize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -9,24 +9,29 @@ against the stream's previous thumbnail, sub-pixel refinement), and `track.warp`
 ultralytics' global-motion step, without a host read:
 
   motion_state     the zeroed state of `streams` streams (their last thumbnails)
-  estimate         yh_motion / yh_motion_host: one frame of every stream of a batch (functional)
+  estimate         yh_motion / yh_motion_field and their host twins: one frame of every stream of a batch
+  field_workspace  the device workspace of model="similarity"
   Motion           (motion (B, 3) f32 = s, tx, ty; sad (B, 2) i32 = best SAD, SAD at no shift)
   MotionEstimator  the state and the parameters of a set of streams
 
     dets = detector.predict(frames, keep_frames=True)
     tracks = tracker.update(dets, motion=estimator.estimate(dets.frames))
 
-The model is one translation per frame, at most `radius` thumbnail pixels long; rotation, zoom,
-rolling shutter and parallax are not modelled, and a moving foreground that fills much of the frame
-biases the estimate. There is no counterpart in the reference; the semantics are those stated in
-include/yolo_hip.h, pinned by the numpy restatement in tests/_motion_cases.py.
+The default model is one translation per frame, at most `radius` thumbnail pixels long.
+model="similarity" (yh_motion_field) adds an isotropic zoom for PTZ cameras and drones that climb or
+descend: a shift per block of a grid over the thumbnail, a consensus among the blocks with texture,
+and a least-squares (s, tx, ty) - the row `warp` takes - with the translation model's row as the
+fallback. Rotation, rolling shutter and parallax are not modelled, and a moving foreground that fills
+much of the frame biases either estimate. There is no counterpart in the reference; the semantics are
+those stated in include/yolo_hip.h, pinned by the numpy restatements in tests/_motion_cases.py and
+tests/_motion_field_cases.py.
 """
-from ctypes import c_void_p
+from ctypes import byref, c_void_p
 from typing import NamedTuple
 
 import torch
 
-from ._lib import YhFrame, check, lib
+from ._lib import YhFrame, YhMotionFieldParams, check, lib
 from .preprocess import NV12, _bgr, _bgr_desc
 
 MAX_RADIUS = 32      # YH_MOTION_MAX_RADIUS
@@ -58,15 +63,43 @@ def motion_state(streams, thumb=(96, 160), device="cpu"):
 
 
 class Motion(NamedTuple):
-    """Result of `estimate`: motion (B, 3) f32 rows of s, tx, ty (s is always 1) in source pixels -
-    content at (x, y) of the previous frame is at about (x + tx, y + ty) now; sad (B, 2) i32: the
-    best candidate's sum of absolute differences and the one at no shift."""
+    """Result of `estimate`: motion (B, 3) f32 rows of s, tx, ty in source pixels (s is 1 under the
+    translation model) - content at (x, y) of the previous frame is at about (s x + tx, s y + ty)
+    now; sad (B, 2) i32: the best global candidate's sum of absolute differences and the one at no
+    shift."""
     motion: torch.Tensor
     sad: torch.Tensor
 
 
-def estimate(frames, state, thumb=(96, 160), radius=8, max_mad=24, stream_ids=None, out=None, threads=0):
-    """The translation of every frame of a batch against its stream's previous frame (yh_motion).
+def _field_params(grid, radius, max_mad, min_contrast, tol, min_blocks):
+    if not isinstance(grid, (tuple, list)) or len(grid) != 2:
+        raise ValueError("yolo_hip.motion: grid is (grid_h, grid_w)")
+    return YhMotionFieldParams(int(grid[0]), int(grid[1]), int(radius), int(max_mad), int(min_contrast), int(tol),
+                               int(min_blocks), 0)
+
+
+def field_workspace(batch, grid=(6, 10), radius=8, device="cuda"):
+    """The caller-owned workspace of `estimate(model="similarity")` on a device, for batches of up to
+    `batch` frames (uint8; yh_motion_field_workspace_bytes). Its contents mean nothing between calls."""
+    n = lib().yh_motion_field_workspace_bytes(int(batch), int(grid[0]), int(grid[1]), int(radius))
+    if n == 0 and batch > 0:
+        raise ValueError("yolo_hip.motion: illegal grid or radius")
+    return torch.empty((n,), dtype=torch.uint8, device=device)
+
+
+def estimate(frames, state, thumb=(96, 160), radius=8, max_mad=24, stream_ids=None, out=None, threads=0,
+             model="translation", grid=(6, 10), min_contrast=4, tol=1, min_blocks=6, field=None, workspace=None):
+    """The motion of every frame of a batch against its stream's previous frame: one translation
+    (model="translation", yh_motion) or translation plus zoom (model="similarity", yh_motion_field).
+
+    model="similarity": the search window is cut into grid = (grid_h, grid_w) blocks, each block finds
+    its own shift, the blocks that found texture and a match vote (max_mad and min_contrast per
+    pixel), and s, tx, ty are fitted to a consensus of the votes within `tol` thumbnail pixels; with
+    fewer than `min_blocks` votes, no consensus, a scene cut or a scale outside [0.8, 1.25] the row is
+    the translation model's, byte for byte. field: an optional (B, grid_h * grid_w, 4) int32 tensor
+    that receives per block dy, dx, best SAD, flags (1: voted, 2: inlier of the fit). workspace: a
+    `field_workspace` tensor for the device path (None: allocated here). Both models advance the same
+    state: a stream may change model from frame to frame.
 
     frames: B frames as `Detections.frames` holds and `letterbox_frames` takes them (BGR tensors /
     arrays and `NV12`, mixed, any sizes at least the thumbnail's). state: a `motion_state` tensor,
@@ -126,17 +159,38 @@ def estimate(frames, state, thumb=(96, 160), radius=8, max_mad=24, stream_ids=No
     def ptr(t):
         return c_void_p(t.data_ptr()) if t is not None else None
 
-    args = (descs, B, ptr(stream_ids), ptr(state), S, th, tw, int(radius), int(max_mad), ptr(out.motion), ptr(out.sad))
+    if dev.type not in ("cuda", "cpu"):
+        raise ValueError(f"{who}: unsupported device {dev}")
+    if model == "translation":
+        args = (descs, B, ptr(stream_ids), ptr(state), S, th, tw, int(radius), int(max_mad), ptr(out.motion), ptr(out.sad))
+        entry, tail = ("yh_motion", ()) if dev.type == "cuda" else ("yh_motion_host", (int(threads),))
+    elif model == "similarity":
+        fp = _field_params(grid, radius, max_mad, min_contrast, tol, min_blocks)
+        if field is not None and (not isinstance(field, torch.Tensor) or field.dtype != torch.int32 or field.device != dev
+                                  or tuple(field.shape) != (B, fp.grid_h * fp.grid_w, 4) or not field.is_contiguous()):
+            raise ValueError(f"{who}: field must be a contiguous (B, grid_h * grid_w, 4) int32 tensor on {dev}")
+        args = (descs, B, ptr(stream_ids), ptr(state), S, th, tw, byref(fp), ptr(out.motion), ptr(out.sad), ptr(field))
+        if dev.type == "cuda":
+            need = lib().yh_motion_field_workspace_bytes(B, fp.grid_h, fp.grid_w, fp.radius)
+            if workspace is None:
+                workspace = torch.empty((max(need, 4),), dtype=torch.uint8, device=dev)
+            elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev
+                  or not workspace.is_contiguous() or workspace.numel() < need):
+                raise ValueError(f"{who}: workspace must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+            srcs.append(workspace)
+            entry, tail = "yh_motion_field", (ptr(workspace), workspace.numel())
+        else:
+            entry, tail = "yh_motion_field_host", (int(threads),)
+    else:
+        raise ValueError(f"{who}: model is 'translation' or 'similarity'")
     if dev.type == "cuda":
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            check(lib().yh_motion(*args, c_void_p(stream.cuda_stream)), "motion")
+            check(getattr(lib(), entry)(*args, *tail, c_void_p(stream.cuda_stream)), entry[3:])
         for t in srcs:   # keep the sources alive for the queued kernels
             t.record_stream(stream)
-    elif dev.type == "cpu":
-        check(lib().yh_motion_host(*args, int(threads)), "motion_host")
     else:
-        raise ValueError(f"{who}: unsupported device {dev}")
+        check(getattr(lib(), entry)(*args, *tail), entry[3:])
     del srcs
     return out
 
@@ -148,12 +202,23 @@ class MotionEstimator:
     frame and keeps the new thumbnails; the first frame of a stream, and a frame the gate rejects,
     give the identity. stream_ids as `Tracker.update`'s: None, a host sequence of ints (checked) or
     an int32 tensor on the device (not checked). reset() forgets every frame; `state` is the state
-    tensor. The launches of one estimator must run on one stream, frames of a stream in order."""
+    tensor. The launches of one estimator must run on one stream, frames of a stream in order.
+    model="similarity" estimates a zoom as well (`estimate`'s grid, min_contrast, tol, min_blocks);
+    the estimator then owns the device workspace. estimate(..., field=t) fills a per-block tensor."""
 
-    def __init__(self, streams, device, thumb=(96, 160), radius=8, max_mad=24):
+    def __init__(self, streams, device, thumb=(96, 160), radius=8, max_mad=24, model="translation", grid=(6, 10),
+                 min_contrast=4, tol=1, min_blocks=6):
         self.device = torch.device(device)
         self.thumb = _thumb(thumb)
         self.radius, self.max_mad = int(radius), int(max_mad)
+        if model not in ("translation", "similarity"):
+            raise ValueError("yolo_hip.MotionEstimator: model is 'translation' or 'similarity'")
+        self.model = model
+        self.field = dict(grid=(int(grid[0]), int(grid[1])), min_contrast=int(min_contrast), tol=int(tol),
+                          min_blocks=int(min_blocks))
+        self.workspace = None
+        if model == "similarity" and self.device.type == "cuda":
+            self.workspace = field_workspace(_LAUNCH, self.field["grid"], self.radius, self.device)
         if not 1 <= self.radius <= MAX_RADIUS or min(self.thumb) - 2 * self.radius < 4:
             raise ValueError(f"yolo_hip.MotionEstimator: radius must be in [1, {MAX_RADIUS}] and leave a window of "
                              "at least 4 x 4 (thumb - 2 * radius)")
@@ -163,7 +228,7 @@ class MotionEstimator:
     def reset(self):
         self.state.zero_()
 
-    def estimate(self, frames, stream_ids=None, out=None, threads=0):
+    def estimate(self, frames, stream_ids=None, out=None, threads=0, field=None):
         if stream_ids is not None and not isinstance(stream_ids, torch.Tensor):
             host = [int(v) for v in stream_ids]
             if len(set(host)) != len(host):
@@ -173,5 +238,8 @@ class MotionEstimator:
             stream_ids = torch.tensor(host, dtype=torch.int32).to(self.device, non_blocking=True)
         elif stream_ids is None and len(frames) > self.streams:
             raise ValueError(f"yolo_hip.MotionEstimator: a batch of {len(frames)} frames for {self.streams} streams")
+        if self.model == "translation":
+            return estimate(frames, self.state, self.thumb, self.radius, self.max_mad, stream_ids=stream_ids, out=out,
+                            threads=threads)
         return estimate(frames, self.state, self.thumb, self.radius, self.max_mad, stream_ids=stream_ids, out=out,
-                        threads=threads)
+                        threads=threads, model="similarity", field=field, workspace=self.workspace, **self.field)
