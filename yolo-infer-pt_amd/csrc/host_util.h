@@ -30,6 +30,13 @@ inline void require(bool ok, const std::string& msg, int code = YH_EINVAL) {
     if (!ok) throw Fail(code, msg);
 }
 
+// after a kernel launch wrapper that returns the hipError_t of its launch as an int. The set_io
+// launches of the forward said "set_io launch failed" alone before they came here; with the rest
+// they now end in ": " and the HIP error's text.
+inline void launched(const char* what, int rc) {
+    if (rc != 0) throw Fail(YH_EHIP, std::string(what) + " launch failed: " + hipGetErrorString((hipError_t)rc));
+}
+
 // body of an extern "C" entry point: exceptions become a status code and yh_last_error's text
 template <typename F>
 int guarded(F&& f) {

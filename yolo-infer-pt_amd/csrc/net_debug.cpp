@@ -324,8 +324,8 @@ void Net::debug_run(const void* x, int x_u8, int B, int H, int W, void* y, int f
             YH_ESTATE);
     require(first >= 0 && first <= last && last <= (int)ops.size(), "op range out of bounds");
     HIPCHECK(hipSetDevice(device));
-    const int rc = task == 1 ? launch_set_io_cls(io_dev, x, (float*)y, nullptr, nullptr, nullptr, s) : launch_set_io(io_dev, x, y, s);
-    require(rc == 0, "set_io launch failed", YH_EHIP);
+    launched("set_io", task == 1 ? launch_set_io_cls(io_dev, x, (float*)y, nullptr, nullptr, nullptr, s)
+                                 : launch_set_io(io_dev, x, y, s));
     ensure_plan(B, H, W);
     ensure_tuned(B, H, W, s);
     for (int i = first; i < last; ++i)

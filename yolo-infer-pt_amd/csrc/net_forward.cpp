@@ -148,7 +148,7 @@ void Net::forward(const void* x, int B, int H, int W, void* y, hipStream_t s, in
     for (auto& d : convs) require(d.loaded, "weights of " + d.name + " not loaded", YH_ESTATE);
     reserve(B, H, W);
     HIPCHECK(hipSetDevice(device));
-    require(launch_set_io(io_dev, x, y, s) == 0, "set_io launch failed", YH_EHIP);
+    launched("set_io", launch_set_io(io_dev, x, y, s));
     launch_plan(B, H, W, s);
 }
 
@@ -160,7 +160,7 @@ void Net::classify(const void* x, int x_u8, int B, int H, int W, const int* coun
     for (auto& d : convs) require(d.loaded, "weights of " + d.name + " not loaded", YH_ESTATE);
     reserve(B, H, W);
     HIPCHECK(hipSetDevice(device));
-    require(launch_set_io_cls(io_dev, x, probs, logits, embed, count, s) == 0, "set_io launch failed", YH_EHIP);
+    launched("set_io", launch_set_io_cls(io_dev, x, probs, logits, embed, count, s));
     launch_plan(B, H, W, s);
 }
 

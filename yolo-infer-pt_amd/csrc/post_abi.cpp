@@ -80,7 +80,7 @@ int yh_nms(int dtype, const void* y, int batch, int num_classes, int anchors, fl
         a.dets = dets;
         a.ndet = counts;
         const int rc = yh::launch_nms(dtype, a, (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("NMS launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("NMS", rc);
     });
 }
 
@@ -92,7 +92,7 @@ int yh_match(const float* dets, const int* counts, int batch, int max_det, const
         checked(yh_match_check(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp));
         const int rc = yh::launch_match(dets, counts, batch, max_det, labels, label_offsets, iou_v, num_iou, tp,
                                         score_cls, counts_out, (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("match launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("match", rc);
     });
 }
 
@@ -114,7 +114,7 @@ int yh_merge(const float* dets, const int* counts, int tiles, int max_det, const
                                max_tiles, max_out, out, out_counts));
         const int rc = yh::launch_merge(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images,
                                         max_tiles, iou_threshold, max_out, out, out_counts, (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("merge launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("merge", rc);
     });
 }
 
@@ -144,7 +144,7 @@ int yh_track2(const float* dets, const int* counts, int batch, int max_det, cons
         const int rc = yh::launch_track(dets, counts, batch, max_det, stream_ids, state, streams, max_tracks, *p, max_out,
                                         out, ids, det_index, out_counts, ap->mode == YH_ASSIGN_OPTIMAL,
                                         (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("track launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("track", rc);
     });
 }
 
@@ -181,7 +181,7 @@ int yh_track_warp(void* state, int streams, int max_tracks, int reid_dim, const 
         yh::require((uintptr_t)state % 4 == 0, "state must be 4-byte aligned");
         const int rc = yh::launch_track_warp(state, streams, max_tracks, reid_dim, motion, stream_ids, batch,
                                              (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("track_warp launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("track_warp", rc);
     });
 }
 
@@ -206,7 +206,7 @@ int yh_motion(const yh_frame* frames, int batch, const int* stream_ids, void* st
         yh::require((uintptr_t)state % 4 == 0, "motion: state must be 4-byte aligned on the device");
         const int rc = yh::launch_motion(src.data(), batch, stream_ids, state, streams, thumb_h, thumb_w, radius, max_mad,
                                          motion, sad, (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("motion launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("motion", rc);
     });
 }
 
@@ -242,7 +242,7 @@ int yh_motion_field(const yh_frame* frames, int batch, const int* stream_ids, vo
                     "motion_field: state and workspace must be 4-byte aligned on the device");
         const int rc = yh::launch_motion_field(src.data(), batch, stream_ids, state, streams, thumb_h, thumb_w, *p, motion,
                                                sad, field, workspace, (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("motion_field launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("motion_field", rc);
     });
 }
 
@@ -265,7 +265,7 @@ int yh_assign(const int32_t* weights, int problems, int T, int D, const int32_t*
         checked(yh_assign_check(weights, problems, T, D, row_of_slot, slot_of_row));
         const int rc = yh::launch_assign(weights, problems, T, D, t_counts, d_counts, row_of_slot, slot_of_row,
                                          (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("assign launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("assign", rc);
     });
 }
 
@@ -281,7 +281,7 @@ int yh_embed_quantize(const float* e, int rows, int dim, const int* count, int8_
     return guarded([&] {
         checked(yh_embed_quantize_check(e, rows, dim, q));
         const int rc = yh::launch_embed_quantize(e, rows, dim, count, q, (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("embed_quantize launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("embed_quantize", rc);
     });
 }
 
@@ -300,7 +300,7 @@ int yh_embed_similarity(const int8_t* a, size_t a_block_stride, int nblocks, con
                     "a, b and a_block_stride must be multiples of 16 bytes on the device");
         const int rc = yh::launch_embed_similarity(a, a_block_stride, nblocks, a_index, b, batch, ra, rb, dim, out,
                                                    nullptr, nullptr, (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("embed_similarity launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("embed_similarity", rc);
     });
 }
 
@@ -365,7 +365,7 @@ int yh_track_reid2(const float* dets, const int* counts, int batch, int max_det,
         if (rc == 0)
             rc = yh::launch_gallery_update(state, stream_bytes, gallery_offset, stream_ids, batch, max_tracks, max_det,
                                            dim, rd.q, rd.flags, rd.code, s);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("track_reid launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("track_reid", rc);
     });
 }
 
@@ -422,7 +422,7 @@ int yh_gallery_search(const int8_t* gallery, const int32_t* labels, const int32_
                     "gallery, q and workspace must be 16-byte aligned on the device");
         const int rc = yh::launch_gallery_search(gallery, labels, size, capacity, dim, q, nq, nq_count, k, chunk_rows,
                                                  scores, index, workspace, (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("gallery_search launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("gallery_search", rc);
     });
 }
 
@@ -444,7 +444,7 @@ int yh_gallery_enrol(int8_t* gallery, int32_t* labels, int32_t* size, int capaci
         yh::require(((uintptr_t)gallery | (uintptr_t)q) % 16 == 0, "gallery and q must be 16-byte aligned on the device");
         const int rc = yh::launch_gallery_enrol(gallery, labels, size, capacity, dim, q, nq, nq_count, take, labels_in,
                                                 next_label, rows_out, (hipStream_t)stream);
-        if (rc != 0) throw Fail(YH_EHIP, std::string("gallery_enrol launch failed: ") + hipGetErrorString((hipError_t)rc));
+        yh::launched("gallery_enrol", rc);
     });
 }
 

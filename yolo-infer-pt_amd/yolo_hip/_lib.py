@@ -49,6 +49,12 @@ class YhMotionFieldParams(ctypes.Structure):
                                      "reserved")]
 
 
+def _twins(name, *shared):
+    """The prototypes of a device entry point and its host twin: the shared arguments, then the stream
+    (c_void_p) for `name` and the thread count (c_int) for `name`_host."""
+    return {name: (c_int, [*shared, c_void_p]), name + "_host": (c_int, [*shared, c_int])}
+
+
 # name -> (restype, argtypes); mirrors include/yolo_hip.h
 _PROTOS = {
     "yh_abi_version": (c_int, []),
@@ -84,66 +90,41 @@ _PROTOS = {
                              POINTER(c_double), POINTER(c_int)]),
     "yh_nms_host": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_float, c_double, c_int, c_int, c_float,
                             c_void_p, c_void_p, c_int]),
-    "yh_match": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                         c_void_p, c_void_p, c_void_p, c_void_p]),
-    "yh_match_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                              c_void_p, c_void_p, c_void_p, c_int]),
-    "yh_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
-                         c_int, c_void_p, c_void_p, c_void_p]),
-    "yh_merge_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
-                              c_int, c_void_p, c_void_p, c_int]),
+    **_twins("yh_match", c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                         c_void_p),
+    **_twins("yh_merge", c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                         c_int, c_void_p, c_void_p),
     "yh_track_state_bytes": (c_size_t, [c_int, c_int]),
-    "yh_track": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
-                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "yh_track_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
-    "yh_track2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
-                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "yh_track2_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
-    "yh_track_warp": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
-    "yh_track_warp_host": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int]),
+    **_twins("yh_track", c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                         c_void_p, c_void_p, c_void_p, c_void_p),
+    **_twins("yh_track2", c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p),
+    **_twins("yh_track_warp", c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int),
     "yh_motion_state_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "yh_motion": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                          c_void_p, c_void_p]),
-    "yh_motion_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                               c_void_p, c_int]),
+    **_twins("yh_motion", POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                          c_void_p),
     "yh_motion_field_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "yh_motion_field": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "yh_motion_field_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_int]),
-    "yh_assign": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "yh_assign_host": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
-    "yh_embed_quantize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "yh_embed_quantize_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]),
-    "yh_embed_similarity": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
-                                    c_void_p]),
-    "yh_embed_similarity_host": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                         c_void_p, c_int]),
+    **_twins("yh_assign", c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p),
+    **_twins("yh_embed_quantize", c_void_p, c_int, c_int, c_void_p, c_void_p),
+    **_twins("yh_embed_similarity", c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                    c_void_p),
     "yh_track_reid_state_bytes": (c_size_t, [c_int, c_int, c_int]),
     "yh_track_reid_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "yh_track_reid": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+    **_twins("yh_track_reid", c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                              c_void_p, c_void_p, c_size_t, c_void_p]),
-    "yh_track_reid_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_size_t, c_int]),
-    "yh_track_reid2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                              c_void_p, c_void_p, c_size_t),
+    **_twins("yh_track_reid2", c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "yh_track_reid2_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_size_t, c_void_p, c_int]),
+                               c_void_p, c_void_p, c_size_t, c_void_p),
     "yh_gallery_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "yh_gallery_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
-                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "yh_gallery_search_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
-                                       c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int]),
-    "yh_gallery_enrol": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                 c_void_p, c_void_p, c_void_p, c_void_p]),
-    "yh_gallery_enrol_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_int]),
+    **_twins("yh_gallery_search", c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_size_t),
+    **_twins("yh_gallery_enrol", c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p),
     "yh_letterbox_geometry": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yh_letterbox": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "yh_letterbox_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),
@@ -151,10 +132,8 @@ _PROTOS = {
     "yh_letterbox_frames": (c_int, [POINTER(YhFrame), c_int, c_int, c_int, c_void_p, c_void_p]),
     "yh_letterbox_frames_host": (c_int, [POINTER(YhFrame), c_int, c_int, c_void_p, c_int]),
     "yh_nv12_to_bgr_host": (c_int, [POINTER(YhFrame), c_void_p]),
-    "yh_crop_rois": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float,
-                             c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "yh_crop_rois_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
-                                  c_float, c_int, c_void_p, c_void_p, c_void_p, c_int]),
+    **_twins("yh_crop_rois", POINTER(YhFrame), c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                             c_int, c_void_p, c_void_p, c_void_p),
     "yh_resize_linear_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "yh_debug_op_desc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
     "yh_debug_run_ops": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),

@@ -23,7 +23,10 @@ import ctypes
 import numpy as np
 import torch
 
+from ._call import run, tensor
 from ._lib import MERGE_MAX_CAND
+
+_WHO = "yolo_hip.merge"
 
 
 def _starts(length, tile, step):
@@ -70,20 +73,6 @@ def tile_transform(crop, size):
             np.float32(x0), np.float32(y0))
 
 
-def _check(name, t, shape, dtype, device):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"yolo_hip.merge: {name} must be a tensor")
-    if t.dtype != dtype:
-        raise TypeError(f"yolo_hip.merge: {name} must be {dtype}, got {t.dtype}")
-    if t.device != device:
-        raise ValueError(f"yolo_hip.merge: {name} is on {t.device}, expected {device}")
-    if len(shape) != t.dim() or any(w is not None and w != g for w, g in zip(shape, t.shape)):
-        want = tuple("*" if w is None else w for w in shape)
-        raise ValueError(f"yolo_hip.merge: {name} has shape {tuple(t.shape)}, expected {want}")
-    if not t.is_contiguous():
-        raise ValueError(f"yolo_hip.merge: {name} must be contiguous")
-
-
 def merge(dets, counts, tile_xf, tile_offsets, image_wh, max_tiles, iou=0.65, max_out=300, out=None, threads=0):
     """Tile detections -> source-image detections, all images of a call in one launch.
 
@@ -101,40 +90,28 @@ def merge(dets, counts, tile_xf, tile_offsets, image_wh, max_tiles, iou=0.65, ma
     equal classes (include/yolo_hip.h). cuda tensors run the HIP kernel (yh_merge) asynchronously
     on the current stream, CPU tensors the host twin (yh_merge_host, `threads` <= 0: every
     hardware thread)."""
-    from ._lib import check, lib
     if not isinstance(dets, torch.Tensor) or dets.dim() != 3:
         raise ValueError("yolo_hip.merge: dets must be a (T, max_det, 6) tensor")
     dev = dets.device
     T, md = dets.shape[0], dets.shape[1]
-    _check("dets", dets, (T, md, 6), torch.float32, dev)
-    _check("counts", counts, (T,), torch.int32, dev)
-    _check("tile_xf", tile_xf, (T, 6), torch.float32, dev)
-    _check("tile_offsets", tile_offsets, (None,), torch.int32, dev)
+    tensor(_WHO, "dets", dets, (T, md, 6), torch.float32, dev)
+    tensor(_WHO, "counts", counts, (T,), torch.int32, dev)
+    tensor(_WHO, "tile_xf", tile_xf, (T, 6), torch.float32, dev)
+    tensor(_WHO, "tile_offsets", tile_offsets, (None,), torch.int32, dev)
     if tile_offsets.shape[0] < 1:
         raise ValueError("yolo_hip.merge: tile_offsets must hold images + 1 entries")
     N = tile_offsets.shape[0] - 1
-    _check("image_wh", image_wh, (N, 2), torch.float32, dev)
+    tensor(_WHO, "image_wh", image_wh, (N, 2), torch.float32, dev)
     max_out = int(max_out)
     if out is None:
         o = torch.empty((N, max(max_out, 0), 6), dtype=torch.float32, device=dev)
         oc = torch.empty((N,), dtype=torch.int32, device=dev)
     else:
         o, oc = out
-        _check("out", o, (N, max_out, 6), torch.float32, dev)
-        _check("out_counts", oc, (N,), torch.int32, dev)
-
-    def ptr(t):
-        return ctypes.c_void_p(t.data_ptr())
-
-    args = (ptr(dets), ptr(counts), T, md, ptr(tile_xf), ptr(tile_offsets), ptr(image_wh), N, int(max_tiles),
-            ctypes.c_double(iou), max_out, ptr(o), ptr(oc))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(lib().yh_merge(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "merge")
-    elif dev.type == "cpu":
-        check(lib().yh_merge_host(*args, int(threads)), "merge_host")
-    else:
-        raise ValueError(f"yolo_hip.merge: unsupported device {dev}")
+        tensor(_WHO, "out", o, (N, max_out, 6), torch.float32, dev)
+        tensor(_WHO, "out_counts", oc, (N,), torch.int32, dev)
+    args = (dets, counts, T, md, tile_xf, tile_offsets, image_wh, N, int(max_tiles), ctypes.c_double(iou), max_out, o, oc)
+    run(_WHO, "merge", dev, args, threads)
     return o, oc
 
 

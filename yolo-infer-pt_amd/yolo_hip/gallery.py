@@ -15,24 +15,15 @@ There is no counterpart in the reference; the semantics are those stated in incl
 pinned by the numpy restatement in tests/_gallery_cases.py. cuda tensors run the HIP kernels on
 the current stream, CPU tensors the host twins: the same bytes.
 """
-import ctypes
 import math
 
 import torch
 
-from . import track as _track
-from .track import _ptr, embed_quantize
+from ._call import run, tensor
+from .track import _check_dim, embed_quantize
 
 MAX_K = 32   # YH_GALLERY_MAX_K
 _WHO = "yolo_hip.gallery"
-
-
-def _check(name, t, shape, dtype, device):
-    _track._check(name, t, shape, dtype, device, who=_WHO)
-
-
-def _check_dim(dim):
-    return _track._check_dim(dim, who=_WHO)
 
 
 def _check_k(k):
@@ -60,7 +51,7 @@ def gallery_workspace(capacity, nq, k=1, chunk_rows=0, device="cpu"):
 def _matrix(name, t, dtype=torch.int8):
     if not isinstance(t, torch.Tensor) or t.dim() != 2:
         raise ValueError(f"yolo_hip.gallery: {name} must be a (rows, dim) tensor")
-    _check(name, t, tuple(t.shape), dtype, t.device)
+    tensor(_WHO, name, t, tuple(t.shape), dtype, t.device)
 
 
 def gallery_search(gallery, q, k=1, labels=None, size=None, count=None, chunk_rows=0, out=None, workspace=None,
@@ -75,44 +66,36 @@ def gallery_search(gallery, q, k=1, labels=None, size=None, count=None, chunk_ro
     the chunks the gallery is searched in (a multiple of 64); the result does not depend on it.
     out: (scores, index) to write. workspace: a `gallery_workspace` to reuse (None: allocated per
     call)."""
-    from ._lib import check, lib
+    from ._lib import lib
     _matrix("gallery", gallery)
     _matrix("q", q)
     dev = gallery.device
     capacity, dim = gallery.shape
     nq = q.shape[0]
-    _check_dim(dim)
-    _check("q", q, (nq, dim), torch.int8, dev)
+    _check_dim(dim, _WHO)
+    tensor(_WHO, "q", q, (nq, dim), torch.int8, dev)
     k, chunk_rows = _check_k(k), _check_chunk(chunk_rows)
     if labels is not None:
-        _check("labels", labels, (capacity,), torch.int32, dev)
+        tensor(_WHO, "labels", labels, (capacity,), torch.int32, dev)
     if size is not None:
-        _check("size", size, (1,), torch.int32, dev)
+        tensor(_WHO, "size", size, (1,), torch.int32, dev)
     if count is not None:
-        _check("count", count, (1,), torch.int32, dev)
+        tensor(_WHO, "count", count, (1,), torch.int32, dev)
     if out is None:
         scores = torch.empty((nq, k), dtype=torch.int32, device=dev)
         index = torch.empty((nq, k), dtype=torch.int32, device=dev)
     else:
         scores, index = out
-        _check("out scores", scores, (nq, k), torch.int32, dev)
-        _check("out index", index, (nq, k), torch.int32, dev)
-    L = lib()
-    need = L.yh_gallery_workspace_bytes(capacity, nq, k, chunk_rows)
+        tensor(_WHO, "out scores", scores, (nq, k), torch.int32, dev)
+        tensor(_WHO, "out index", index, (nq, k), torch.int32, dev)
+    need = lib().yh_gallery_workspace_bytes(capacity, nq, k, chunk_rows)
     if workspace is None:
         workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
     else:
-        _check("workspace", workspace, (None,), torch.uint8, dev)
-    args = (_ptr(gallery), _ptr(labels), _ptr(size), capacity, dim, _ptr(q), nq, _ptr(count), k, chunk_rows,
-            _ptr(scores), _ptr(index), _ptr(workspace), workspace.numel())
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(L.yh_gallery_search(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                  "gallery_search")
-    elif dev.type == "cpu":
-        check(L.yh_gallery_search_host(*args, int(threads)), "gallery_search_host")
-    else:
-        raise ValueError(f"yolo_hip.gallery: unsupported device {dev}")
+        tensor(_WHO, "workspace", workspace, (None,), torch.uint8, dev)
+    args = (gallery, labels, size, capacity, dim, q, nq, count, k, chunk_rows, scores, index, workspace,
+            workspace.numel())
+    run(_WHO, "gallery_search", dev, args, threads)
     return scores, index
 
 
@@ -124,40 +107,30 @@ def gallery_enrol(gallery, labels, size, q, take=None, labels_in=None, next_labe
     gallery is not full. It takes row size[0], which then grows by one, and the label labels_in[i],
     or next_label[0], which then grows by one. gallery, labels, size (1,) i32 and next_label (1,)
     i32 are updated in place; nothing is read back to the host."""
-    from ._lib import check, lib
     _matrix("gallery", gallery)
     _matrix("q", q)
     dev = gallery.device
     capacity, dim = gallery.shape
     nq = q.shape[0]
-    _check_dim(dim)
-    _check("q", q, (nq, dim), torch.int8, dev)
-    _check("labels", labels, (capacity,), torch.int32, dev)
-    _check("size", size, (1,), torch.int32, dev)
+    _check_dim(dim, _WHO)
+    tensor(_WHO, "q", q, (nq, dim), torch.int8, dev)
+    tensor(_WHO, "labels", labels, (capacity,), torch.int32, dev)
+    tensor(_WHO, "size", size, (1,), torch.int32, dev)
     for name, t in (("take", take), ("labels_in", labels_in)):
         if t is not None:
-            _check(name, t, (nq,), torch.int32, dev)
+            tensor(_WHO, name, t, (nq,), torch.int32, dev)
     if labels_in is None and next_label is None:
         raise ValueError("yolo_hip.gallery: without labels_in, next_label must be given")
     if next_label is not None:
-        _check("next_label", next_label, (1,), torch.int32, dev)
+        tensor(_WHO, "next_label", next_label, (1,), torch.int32, dev)
     if count is not None:
-        _check("count", count, (1,), torch.int32, dev)
+        tensor(_WHO, "count", count, (1,), torch.int32, dev)
     if out is None:
         out = torch.empty((nq,), dtype=torch.int32, device=dev)
     else:
-        _check("out", out, (nq,), torch.int32, dev)
-    L = lib()
-    args = (_ptr(gallery), _ptr(labels), _ptr(size), capacity, dim, _ptr(q), nq, _ptr(count), _ptr(take),
-            _ptr(labels_in), _ptr(next_label), _ptr(out))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(L.yh_gallery_enrol(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                  "gallery_enrol")
-    elif dev.type == "cpu":
-        check(L.yh_gallery_enrol_host(*args, int(threads)), "gallery_enrol_host")
-    else:
-        raise ValueError(f"yolo_hip.gallery: unsupported device {dev}")
+        tensor(_WHO, "out", out, (nq,), torch.int32, dev)
+    args = (gallery, labels, size, capacity, dim, q, nq, count, take, labels_in, next_label, out)
+    run(_WHO, "gallery_enrol", dev, args, threads)
     return out
 
 
@@ -181,7 +154,7 @@ class Gallery:
     Gallery on one stream. Nothing here reads a device value on the host."""
 
     def __init__(self, capacity, dim, device="cpu"):
-        self.capacity, self.dim = int(capacity), _check_dim(dim)
+        self.capacity, self.dim = int(capacity), _check_dim(dim, _WHO)
         if self.capacity < 0:
             raise ValueError("yolo_hip.Gallery: capacity must be >= 0")
         self.device = torch.device(device)

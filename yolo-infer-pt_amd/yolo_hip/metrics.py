@@ -29,11 +29,14 @@ best[e] == best[d] has biou[e] >= iou_v[t]. (At threshold t a detection's best
 candidate is its overall best label whenever that one is a candidate at all, so
 the per-threshold argmax of compute_metric never picks another label.)
 """
-import ctypes
 import os
 
 import numpy
 import torch
+
+from ._call import run, tensor
+
+_WHO = "yolo_hip.match_batch"
 
 
 def _iou(target, output):
@@ -68,20 +71,6 @@ def compute_metric(output, target, iou_v):
     return correct[:, :D].t().contiguous()
 
 
-def _check(name, t, shape, dtype, device):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"yolo_hip.match_batch: {name} must be a tensor")
-    if t.dtype != dtype:
-        raise TypeError(f"yolo_hip.match_batch: {name} must be {dtype}, got {t.dtype}")
-    if t.device != device:
-        raise ValueError(f"yolo_hip.match_batch: {name} is on {t.device}, expected {device}")
-    if len(shape) != t.dim() or any(w is not None and w != g for w, g in zip(shape, t.shape)):
-        want = tuple("*" if w is None else w for w in shape)
-        raise ValueError(f"yolo_hip.match_batch: {name} has shape {tuple(t.shape)}, expected {want}")
-    if not t.is_contiguous():
-        raise ValueError(f"yolo_hip.match_batch: {name} must be contiguous")
-
-
 def match_batch(dets, counts, labels, offsets, iou_v, out=None, score_cls=None, counts_out=None, threads=0):
     """compute_metric for a whole batch in one launch, from the NMS output as it stands.
 
@@ -95,38 +84,26 @@ def match_batch(dets, counts, labels, offsets, iou_v, out=None, score_cls=None, 
     tensors the host twin (yh_match_host, `threads` <= 0: every hardware thread). Optional
     score_cls (B, max_det, 2) f32 receives columns 4, 5 of the valid rows (0 beyond) and
     counts_out (B,) i32 the counts clamped to [0, max_det]."""
-    from ._lib import check, lib
     if not isinstance(dets, torch.Tensor) or dets.dim() != 3:
         raise ValueError("yolo_hip.match_batch: dets must be a (B, max_det, 6) tensor")
     dev = dets.device
     B, md = dets.shape[0], dets.shape[1]
-    _check("dets", dets, (B, md, 6), torch.float32, dev)
-    _check("counts", counts, (B,), torch.int32, dev)
-    _check("labels", labels, (None, 5), torch.float32, dev)
-    _check("offsets", offsets, (B + 1,), torch.int32, dev)
-    _check("iou_v", iou_v, (None,), torch.float32, dev)
+    tensor(_WHO, "dets", dets, (B, md, 6), torch.float32, dev)
+    tensor(_WHO, "counts", counts, (B,), torch.int32, dev)
+    tensor(_WHO, "labels", labels, (None, 5), torch.float32, dev)
+    tensor(_WHO, "offsets", offsets, (B + 1,), torch.int32, dev)
+    tensor(_WHO, "iou_v", iou_v, (None,), torch.float32, dev)
     T = iou_v.shape[0]
     if out is None:
         out = torch.empty((B, md, T), dtype=torch.uint8, device=dev)
     else:
-        _check("out", out, (B, md, T), torch.uint8, dev)
+        tensor(_WHO, "out", out, (B, md, T), torch.uint8, dev)
     if score_cls is not None:
-        _check("score_cls", score_cls, (B, md, 2), torch.float32, dev)
+        tensor(_WHO, "score_cls", score_cls, (B, md, 2), torch.float32, dev)
     if counts_out is not None:
-        _check("counts_out", counts_out, (B,), torch.int32, dev)
-
-    def ptr(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    args = (ptr(dets), ptr(counts), B, md, ptr(labels), ptr(offsets), ptr(iou_v), T, ptr(out), ptr(score_cls),
-            ptr(counts_out))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(lib().yh_match(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "match")
-    elif dev.type == "cpu":
-        check(lib().yh_match_host(*args, int(threads)), "match_host")
-    else:
-        raise ValueError(f"yolo_hip.match_batch: unsupported device {dev}")
+        tensor(_WHO, "counts_out", counts_out, (B,), torch.int32, dev)
+    args = (dets, counts, B, md, labels, offsets, iou_v, T, out, score_cls, counts_out)
+    run(_WHO, "match", dev, args, threads)
     return out
 
 

@@ -26,13 +26,13 @@ much of the frame biases either estimate. There is no counterpart in the referen
 those stated in include/yolo_hip.h, pinned by the numpy restatements in tests/_motion_cases.py and
 tests/_motion_field_cases.py.
 """
-from ctypes import byref, c_void_p
+from ctypes import byref
 from typing import NamedTuple
 
 import torch
 
-from ._lib import YhFrame, YhMotionFieldParams, check, lib
-from .preprocess import NV12, _bgr, _bgr_desc
+from ._call import frame_descs, host_stream_ids, run, tensor
+from ._lib import YhMotionFieldParams, lib
 
 MAX_RADIUS = 32      # YH_MOTION_MAX_RADIUS
 MAX_THUMB = 32768    # YH_MOTION_MAX_THUMB
@@ -125,73 +125,38 @@ def estimate(frames, state, thumb=(96, 160), radius=8, max_mad=24, stream_ids=No
         raise ValueError(f"{who}: state has {state.numel()} bytes, not a motion_state of {th} x {tw} thumbnails")
     S = rest // per
     B = len(frames)
-    srcs, descs = [], (YhFrame * max(1, B))()
-    for k, f in enumerate(frames):
-        if isinstance(f, NV12):
-            if dev.type == "cuda":
-                f = f.to(dev, non_blocking=True)
-            elif f.device != dev:
-                raise ValueError(f"{who}: a CPU state needs host frames")
-            srcs.extend(f.tensors())
-            descs[k] = f._desc()
-        else:
-            t = _bgr(f, "motion.estimate")
-            if dev.type == "cuda":
-                t = t.to(dev, non_blocking=True)
-            elif t.device != dev:
-                raise ValueError(f"{who}: a CPU state needs host frames")
-            srcs.append(t)
-            descs[k] = _bgr_desc(t)
+    descs, srcs = frame_descs(who, frames, dev, "motion.estimate", "a CPU state needs host frames")
     if stream_ids is not None:
-        if (not isinstance(stream_ids, torch.Tensor) or stream_ids.dtype != torch.int32 or stream_ids.device != dev
-                or tuple(stream_ids.shape) != (B,) or not stream_ids.is_contiguous()):
-            raise ValueError(f"{who}: stream_ids must be a contiguous (B,) int32 tensor on {dev}")
+        tensor(who, "stream_ids", stream_ids, (B,), torch.int32, dev)
     if out is None:
         out = Motion(torch.empty((B, 3), dtype=torch.float32, device=dev),
                      torch.empty((B, 2), dtype=torch.int32, device=dev))
     else:
         out = Motion(*out)
-        for name, t, shape, dt in (("motion", out.motion, (B, 3), torch.float32), ("sad", out.sad, (B, 2), torch.int32)):
-            if (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != dev or tuple(t.shape) != shape
-                    or not t.is_contiguous()):
-                raise ValueError(f"{who}: out {name} must be a contiguous {shape} {dt} tensor on {dev}")
-
-    def ptr(t):
-        return c_void_p(t.data_ptr()) if t is not None else None
-
-    if dev.type not in ("cuda", "cpu"):
-        raise ValueError(f"{who}: unsupported device {dev}")
+        tensor(who, "out motion", out.motion, (B, 3), torch.float32, dev)
+        tensor(who, "out sad", out.sad, (B, 2), torch.int32, dev)
     if model == "translation":
-        args = (descs, B, ptr(stream_ids), ptr(state), S, th, tw, int(radius), int(max_mad), ptr(out.motion), ptr(out.sad))
-        entry, tail = ("yh_motion", ()) if dev.type == "cuda" else ("yh_motion_host", (int(threads),))
+        args = (descs, B, stream_ids, state, S, th, tw, int(radius), int(max_mad), out.motion, out.sad)
+        run(who, "motion", dev, args, threads, keep=srcs)   # the sources stay alive for the queued kernels
     elif model == "similarity":
         fp = _field_params(grid, radius, max_mad, min_contrast, tol, min_blocks)
-        if field is not None and (not isinstance(field, torch.Tensor) or field.dtype != torch.int32 or field.device != dev
-                                  or tuple(field.shape) != (B, fp.grid_h * fp.grid_w, 4) or not field.is_contiguous()):
-            raise ValueError(f"{who}: field must be a contiguous (B, grid_h * grid_w, 4) int32 tensor on {dev}")
-        args = (descs, B, ptr(stream_ids), ptr(state), S, th, tw, byref(fp), ptr(out.motion), ptr(out.sad), ptr(field))
+        if field is not None:
+            tensor(who, "field", field, (B, fp.grid_h * fp.grid_w, 4), torch.int32, dev)
+        device_tail = ()
         if dev.type == "cuda":
             need = lib().yh_motion_field_workspace_bytes(B, fp.grid_h, fp.grid_w, fp.radius)
             if workspace is None:
                 workspace = torch.empty((max(need, 4),), dtype=torch.uint8, device=dev)
-            elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev
-                  or not workspace.is_contiguous() or workspace.numel() < need):
-                raise ValueError(f"{who}: workspace must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+            else:
+                tensor(who, "workspace", workspace, (None,), torch.uint8, dev)
+                if workspace.numel() < need:
+                    raise ValueError(f"{who}: workspace must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+            device_tail = (workspace, workspace.numel())
             srcs.append(workspace)
-            entry, tail = "yh_motion_field", (ptr(workspace), workspace.numel())
-        else:
-            entry, tail = "yh_motion_field_host", (int(threads),)
+        args = (descs, B, stream_ids, state, S, th, tw, byref(fp), out.motion, out.sad, field)
+        run(who, "motion_field", dev, args, threads, device_tail=device_tail, keep=srcs)
     else:
         raise ValueError(f"{who}: model is 'translation' or 'similarity'")
-    if dev.type == "cuda":
-        stream = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):
-            check(getattr(lib(), entry)(*args, *tail, c_void_p(stream.cuda_stream)), entry[3:])
-        for t in srcs:   # keep the sources alive for the queued kernels
-            t.record_stream(stream)
-    else:
-        check(getattr(lib(), entry)(*args, *tail), entry[3:])
-    del srcs
     return out
 
 
@@ -229,15 +194,8 @@ class MotionEstimator:
         self.state.zero_()
 
     def estimate(self, frames, stream_ids=None, out=None, threads=0, field=None):
-        if stream_ids is not None and not isinstance(stream_ids, torch.Tensor):
-            host = [int(v) for v in stream_ids]
-            if len(set(host)) != len(host):
-                raise ValueError("yolo_hip.MotionEstimator: stream_ids must be distinct")
-            if any(not 0 <= v < self.streams for v in host):
-                raise ValueError(f"yolo_hip.MotionEstimator: stream_ids must lie in [0, {self.streams})")
-            stream_ids = torch.tensor(host, dtype=torch.int32).to(self.device, non_blocking=True)
-        elif stream_ids is None and len(frames) > self.streams:
-            raise ValueError(f"yolo_hip.MotionEstimator: a batch of {len(frames)} frames for {self.streams} streams")
+        stream_ids = host_stream_ids("yolo_hip.MotionEstimator", stream_ids, self.streams, len(frames), self.device,
+                                     "frames")
         if self.model == "translation":
             return estimate(frames, self.state, self.thumb, self.radius, self.max_mad, stream_ids=stream_ids, out=out,
                             threads=threads)

@@ -26,7 +26,10 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from ._call import frame_descs, run, tensor
 from ._lib import YH_PIX_BGR, YH_PIX_NV12, YH_YUV_BT601, YH_YUV_BT709, YhFrame, check, lib
+
+_CROP = "yolo_hip.crop_rois"
 
 
 def _hw(size):
@@ -221,17 +224,10 @@ def letterbox_frames(frames, canvas, device=None, out=None):
     if device is None:
         device = _default_device(frames)
     device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"letterbox_frames: {device} is no cuda device (letterbox_frames_host is the host twin)")
     ch, cw = _hw(canvas)
-    srcs, descs = [], (YhFrame * max(1, len(frames)))()
-    for k, f in enumerate(frames):
-        if isinstance(f, NV12):
-            f = f.to(device, non_blocking=True)
-            srcs.extend(f.tensors())
-            descs[k] = f._desc()
-        else:
-            t = _bgr(f, "letterbox_frames").to(device, non_blocking=True)
-            srcs.append(t)
-            descs[k] = _bgr_desc(t)
+    descs, srcs = frame_descs("yolo_hip.letterbox_frames", frames, device, "letterbox_frames")
     B = len(frames)
     if out is None:
         out = torch.empty((B, 3, ch, cw), dtype=torch.uint8, device=device)
@@ -239,12 +235,8 @@ def letterbox_frames(frames, canvas, device=None, out=None):
         raise ValueError("letterbox_frames: bad out tensor")
     if B == 0:
         return out
-    stream = torch.cuda.current_stream(device)
-    with torch.cuda.device(device):
-        check(lib().yh_letterbox_frames(descs, B, ch, cw, c_void_p(out.data_ptr()), c_void_p(stream.cuda_stream)),
-              "letterbox_frames")
-    for t in srcs:   # keep the sources alive for the queued kernel
-        t.record_stream(stream)
+    # the sources stay alive for the queued kernel
+    run("yolo_hip.letterbox_frames", "letterbox_frames", device, (descs, B, ch, cw, out), 0, keep=srcs)
     return out
 
 
@@ -272,20 +264,6 @@ class Crops(NamedTuple):
         return [(self.data[i], tuple(r)) for i, r in enumerate(self.rois[:n].tolist())]
 
 
-def _check_crop(name, t, shape, dtype, device):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"yolo_hip.crop_rois: {name} must be a tensor")
-    if t.dtype != dtype:
-        raise TypeError(f"yolo_hip.crop_rois: {name} must be {dtype}, got {t.dtype}")
-    if t.device != device:
-        raise ValueError(f"yolo_hip.crop_rois: {name} is on {t.device}, expected {device}")
-    if len(shape) != t.dim() or any(w is not None and w != g for w, g in zip(shape, t.shape)):
-        want = tuple("*" if w is None else w for w in shape)
-        raise ValueError(f"yolo_hip.crop_rois: {name} has shape {tuple(t.shape)}, expected {want}")
-    if not t.is_contiguous():
-        raise ValueError(f"yolo_hip.crop_rois: {name} must be contiguous")
-
-
 def crop_rois(frames, boxes, counts, size, keep_aspect=False, pad=0.0, capacity=None, device=None, out=None,
               threads=0):
     """One fixed-size RGB crop per box, cut from the boxes' source frames: all frames of a call in
@@ -310,51 +288,20 @@ def crop_rois(frames, boxes, counts, size, keep_aspect=False, pad=0.0, capacity=
     B, M, S = boxes.shape
     if len(frames) != B:
         raise ValueError(f"yolo_hip.crop_rois: {len(frames)} frames for boxes of {B} frames")
-    _check_crop("boxes", boxes, (B, M, S), torch.float32, dev)
-    _check_crop("counts", counts, (B,), torch.int32, dev)
+    tensor(_CROP, "boxes", boxes, (B, M, S), torch.float32, dev)
+    tensor(_CROP, "counts", counts, (B,), torch.int32, dev)
     oh, ow = _hw(size)
     capacity = B * M if capacity is None else int(capacity)
-    srcs, descs = [], (YhFrame * max(1, B))()
-    for k, f in enumerate(frames):
-        if isinstance(f, NV12):
-            if dev.type == "cuda":
-                f = f.to(dev, non_blocking=True)
-            elif f.device != dev:
-                raise ValueError("yolo_hip.crop_rois: CPU boxes need host frames")
-            srcs.extend(f.tensors())
-            descs[k] = f._desc()
-        else:
-            t = _bgr(f, "crop_rois")
-            if dev.type == "cuda":
-                t = t.to(dev, non_blocking=True)
-            elif t.device != dev:
-                raise ValueError("yolo_hip.crop_rois: CPU boxes need host frames")
-            srcs.append(t)
-            descs[k] = _bgr_desc(t)
+    descs, srcs = frame_descs(_CROP, frames, dev, "crop_rois", "CPU boxes need host frames")
     if out is None:
         data = torch.empty((max(capacity, 0), 3, max(oh, 0), max(ow, 0)), dtype=torch.uint8, device=dev)
         rois = torch.empty((max(capacity, 0), 6), dtype=torch.int32, device=dev)
         total = torch.empty((1,), dtype=torch.int32, device=dev)
     else:
         data, rois, total = out
-        _check_crop("out data", data, (capacity, 3, oh, ow), torch.uint8, dev)
-        _check_crop("out rois", rois, (capacity, 6), torch.int32, dev)
-        _check_crop("out total", total, (1,), torch.int32, dev)
-
-    def ptr(t):
-        return c_void_p(t.data_ptr())
-
-    args = (descs, B, ptr(boxes), S, ptr(counts), M, oh, ow, int(keep_aspect), float(pad), capacity, ptr(data),
-            ptr(rois), ptr(total))
-    if dev.type == "cuda":
-        stream = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):
-            check(lib().yh_crop_rois(*args, c_void_p(stream.cuda_stream)), "crop_rois")
-        for t in srcs:   # keep the sources alive for the queued kernel
-            t.record_stream(stream)
-    elif dev.type == "cpu":
-        check(lib().yh_crop_rois_host(*args, int(threads)), "crop_rois_host")
-    else:
-        raise ValueError(f"yolo_hip.crop_rois: unsupported device {dev}")
-    del srcs
+        tensor(_CROP, "out data", data, (capacity, 3, oh, ow), torch.uint8, dev)
+        tensor(_CROP, "out rois", rois, (capacity, 6), torch.int32, dev)
+        tensor(_CROP, "out total", total, (1,), torch.int32, dev)
+    args = (descs, B, boxes, S, counts, M, oh, ow, int(keep_aspect), float(pad), capacity, data, rois, total)
+    run(_CROP, "crop_rois", dev, args, threads, keep=srcs)   # the sources stay alive for the queued kernel
     return Crops(data, rois, total)

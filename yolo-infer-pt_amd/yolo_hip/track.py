@@ -30,12 +30,15 @@ from typing import NamedTuple
 
 import torch
 
+from ._call import host_stream_ids, run, tensor
+
 MAX_TRACKS = 1024   # YH_TRACK_MAX_TRACKS
 MAX_DET = 1024      # YH_TRACK_MAX_DET
 REID_MAX_DIM = 2048  # YH_REID_MAX_DIM
 ASSIGN_MAX_WEIGHT = 1 << 16   # YH_ASSIGN_MAX_WEIGHT
 ASSIGN_MAX_SIZE = 1024        # YH_ASSIGN_MAX_SIZE
 ASSIGN_MODES = {"greedy": 0, "optimal": 1}   # YH_ASSIGN_GREEDY, YH_ASSIGN_OPTIMAL
+_WHO = "yolo_hip.track"
 _HDR, _FIELDS = 4, 24   # state words per stream: _HDR + _FIELDS * max_tracks (csrc/track_host.h)
 
 
@@ -70,7 +73,7 @@ def _assign_params(assign):
     return AssignParams(ASSIGN_MODES[assign])
 
 
-def _check_dim(dim, who="yolo_hip.track"):
+def _check_dim(dim, who=_WHO):
     dim = int(dim)
     if dim % 64 or not 64 <= dim <= REID_MAX_DIM:
         raise ValueError(f"{who}: the feature length must be a multiple of 64 in [64, {REID_MAX_DIM}], got {dim}")
@@ -109,35 +112,17 @@ class Tracks(NamedTuple):
         return [(self.dets[i, :k], self.ids[i, :k], self.det_index[i, :k]) for i, k in enumerate(self.counts.tolist())]
 
 
-def _check(name, t, shape, dtype, device, who="yolo_hip.track"):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{who}: {name} must be a tensor")
-    if t.dtype != dtype:
-        raise TypeError(f"{who}: {name} must be {dtype}, got {t.dtype}")
-    if t.device != device:
-        raise ValueError(f"{who}: {name} is on {t.device}, expected {device}")
-    if len(shape) != t.dim() or any(w is not None and w != g for w, g in zip(shape, t.shape)):
-        want = tuple("*" if w is None else w for w in shape)
-        raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected {want}")
-    if not t.is_contiguous():
-        raise ValueError(f"{who}: {name} must be contiguous")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _frame_args(dets, counts, state, stream_ids, max_out, out):
     """The checks `track` and `track_reid` share -> (device, B, max_det, max_out, Tracks to write)."""
     if not isinstance(dets, torch.Tensor) or dets.dim() != 3:
         raise ValueError("yolo_hip.track: dets must be a (B, max_det, 6) tensor")
     dev = dets.device
     B, md = dets.shape[0], dets.shape[1]
-    _check("dets", dets, (B, md, 6), torch.float32, dev)
-    _check("counts", counts, (B,), torch.int32, dev)
-    _check("state", state, (None, None), torch.int32, dev)
+    tensor(_WHO, "dets", dets, (B, md, 6), torch.float32, dev)
+    tensor(_WHO, "counts", counts, (B,), torch.int32, dev)
+    tensor(_WHO, "state", state, (None, None), torch.int32, dev)
     if stream_ids is not None:
-        _check("stream_ids", stream_ids, (B,), torch.int32, dev)
+        tensor(_WHO, "stream_ids", stream_ids, (B,), torch.int32, dev)
     max_out = md if max_out is None else int(max_out)
     if out is None:
         o = Tracks(torch.empty((B, max(max_out, 0), 6), dtype=torch.float32, device=dev),
@@ -146,10 +131,10 @@ def _frame_args(dets, counts, state, stream_ids, max_out, out):
                    torch.empty((B,), dtype=torch.int32, device=dev))
     else:
         o = Tracks(*out)
-        _check("out dets", o.dets, (B, max_out, 6), torch.float32, dev)
-        _check("out ids", o.ids, (B, max_out), torch.int32, dev)
-        _check("out det_index", o.det_index, (B, max_out), torch.int32, dev)
-        _check("out counts", o.counts, (B,), torch.int32, dev)
+        tensor(_WHO, "out dets", o.dets, (B, max_out, 6), torch.float32, dev)
+        tensor(_WHO, "out ids", o.ids, (B, max_out), torch.int32, dev)
+        tensor(_WHO, "out det_index", o.det_index, (B, max_out), torch.int32, dev)
+        tensor(_WHO, "out counts", o.counts, (B,), torch.int32, dev)
     return dev, B, md, max_out, o
 
 
@@ -172,27 +157,19 @@ def track(dets, counts, state, p=None, stream_ids=None, max_out=None, out=None, 
     cuda tensors run the HIP kernel (yh_track2) asynchronously on the current stream, CPU tensors
     the host twin (yh_track_host, `threads` <= 0: every hardware thread); both give the same bytes,
     state included. Frames of one stream must be submitted in order on one stream."""
-    from ._lib import check, lib
+    from ._lib import lib
     dev, B, md, max_out, o = _frame_args(dets, counts, state, stream_ids, max_out, out)
     S, words = state.shape
     if words < _HDR + _FIELDS or (words - _HDR) % _FIELDS:
         raise ValueError(f"yolo_hip.track: state has {words} words per stream, expected 4 + 24 * max_tracks")
     mt = (words - _HDR) // _FIELDS
     p = params() if p is None else p
-    ptr = _ptr
-    L = lib()
-    if mt <= MAX_TRACKS and L.yh_track_state_bytes(S, mt) != state.numel() * 4:
+    if mt <= MAX_TRACKS and lib().yh_track_state_bytes(S, mt) != state.numel() * 4:
         raise RuntimeError("yolo_hip.track: the library's state size differs from track_state's")
     ap = _assign_params(assign)
-    args = (ptr(dets), ptr(counts), B, md, ptr(stream_ids), ptr(state), S, mt, ctypes.byref(p), max_out,
-            ptr(o.dets), ptr(o.ids), ptr(o.det_index), ptr(o.counts), ctypes.byref(ap))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(L.yh_track2(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track")
-    elif dev.type == "cpu":
-        check(L.yh_track2_host(*args, int(threads)), "track_host")
-    else:
-        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+    args = (dets, counts, B, md, stream_ids, state, S, mt, ctypes.byref(p), max_out, o.dets, o.ids, o.det_index,
+            o.counts, ctypes.byref(ap))
+    run(_WHO, "track2", dev, args, threads, what="track")
     return o
 
 
@@ -204,16 +181,15 @@ def warp(state, motion, max_tracks, reid_dim=None, stream_ids=None, threads=0):
     `track`'s. A row with an id out of range, or a motion that is not finite or has s <= 0, changes
     nothing; with s == 1 only the centres change. cuda tensors run the kernel on the current stream,
     CPU tensors the host twin: the same bytes. -> state"""
-    from ._lib import check, lib
     motion = getattr(motion, "motion", motion)
     if not isinstance(motion, torch.Tensor) or motion.dim() != 2:
         raise ValueError("yolo_hip.track: motion must be a (B, 3) tensor")
     dev = motion.device
     B = motion.shape[0]
-    _check("motion", motion, (B, 3), torch.float32, dev)
-    _check("state", state, (None, None), torch.int32, dev)
+    tensor(_WHO, "motion", motion, (B, 3), torch.float32, dev)
+    tensor(_WHO, "state", state, (None, None), torch.int32, dev)
     if stream_ids is not None:
-        _check("stream_ids", stream_ids, (B,), torch.int32, dev)
+        tensor(_WHO, "stream_ids", stream_ids, (B,), torch.int32, dev)
     mt = int(max_tracks)
     dim = 0 if reid_dim is None else _check_dim(reid_dim)
     S, words = state.shape
@@ -221,15 +197,7 @@ def warp(state, motion, max_tracks, reid_dim=None, stream_ids=None, threads=0):
     if not 1 <= mt <= MAX_TRACKS or words != want:
         raise ValueError(f"yolo_hip.track: state has {words} words per stream, expected {want} for max_tracks {mt}"
                          f"{'' if not dim else f' and reid_dim {dim}'}")
-    L = lib()
-    args = (_ptr(state), S, mt, dim, _ptr(motion), _ptr(stream_ids), B)
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(L.yh_track_warp(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track_warp")
-    elif dev.type == "cpu":
-        check(L.yh_track_warp_host(*args, int(threads)), "track_warp_host")
-    else:
-        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+    run(_WHO, "track_warp", dev, (state, S, mt, dim, motion, stream_ids, B), threads)
     return state
 
 
@@ -263,7 +231,7 @@ def track_reid(dets, counts, state, embed=None, feat_counts=None, embed_total=No
 
     cuda tensors run the HIP kernels (quantise, the int8 MFMA similarity, the track kernel) on
     the current stream, CPU tensors the host twin; both give the same bytes, state included."""
-    from ._lib import check, lib
+    from ._lib import lib
     dev, B, md, max_out, o = _frame_args(dets, counts, state, stream_ids, max_out, out)
     if embed is not None:
         if not isinstance(embed, torch.Tensor) or embed.dim() != 2:
@@ -271,14 +239,14 @@ def track_reid(dets, counts, state, embed=None, feat_counts=None, embed_total=No
         if dim is not None and int(dim) != embed.shape[1]:
             raise ValueError(f"yolo_hip.track: embed has {embed.shape[1]} columns, dim is {dim}")
         dim = embed.shape[1]
-        _check("embed", embed, (None, dim), torch.float32, dev)
+        tensor(_WHO, "embed", embed, (None, dim), torch.float32, dev)
     elif dim is None:
         raise ValueError("yolo_hip.track: without embed, dim must be given")
     dim = _check_dim(dim)
     if feat_counts is not None:
-        _check("feat_counts", feat_counts, (B,), torch.int32, dev)
+        tensor(_WHO, "feat_counts", feat_counts, (B,), torch.int32, dev)
     if embed_total is not None:
-        _check("embed_total", embed_total, (1,), torch.int32, dev)
+        tensor(_WHO, "embed_total", embed_total, (1,), torch.int32, dev)
     S, words = state.shape
     per = _FIELDS + dim // 4
     if words < _HDR + per or (words - _HDR) % per:
@@ -291,21 +259,14 @@ def track_reid(dets, counts, state, embed=None, feat_counts=None, embed_total=No
     if workspace is None:
         workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
     else:
-        _check("workspace", workspace, (None,), torch.uint8, dev)
+        tensor(_WHO, "workspace", workspace, (None,), torch.uint8, dev)
     p = params() if p is None else p
     rp = ReidParams(float(reid_cos), float(reid_iou))
     ap = _assign_params(assign)
-    args = (_ptr(dets), _ptr(counts), B, md, _ptr(stream_ids), _ptr(state), S, mt, ctypes.byref(p), max_out,
-            _ptr(o.dets), _ptr(o.ids), _ptr(o.det_index), _ptr(o.counts), _ptr(embed),
-            0 if embed is None else embed.shape[0], dim, _ptr(feat_counts), _ptr(embed_total), ctypes.byref(rp),
-            _ptr(workspace), workspace.numel(), ctypes.byref(ap))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(L.yh_track_reid2(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "track_reid")
-    elif dev.type == "cpu":
-        check(L.yh_track_reid2_host(*args, int(threads)), "track_reid_host")
-    else:
-        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+    args = (dets, counts, B, md, stream_ids, state, S, mt, ctypes.byref(p), max_out, o.dets, o.ids, o.det_index,
+            o.counts, embed, 0 if embed is None else embed.shape[0], dim, feat_counts, embed_total, ctypes.byref(rp),
+            workspace, workspace.numel(), ctypes.byref(ap))
+    run(_WHO, "track_reid2", dev, args, threads, what="track_reid")
     return o
 
 
@@ -318,31 +279,22 @@ def assign(weights, t_counts=None, d_counts=None, out=None, threads=0):
     written. The matching has the largest total weight over the allowed pairs (not the largest
     size); among equal totals the one the algorithm stated in include/yolo_hip.h finds.
     cuda tensors run the kernel on the current stream, CPU tensors the host twin: the same bytes."""
-    from ._lib import check, lib
     who = "yolo_hip.assign"
     if not isinstance(weights, torch.Tensor) or weights.dim() != 3:
         raise ValueError(f"{who}: weights must be a (problems, T, D) tensor")
     dev = weights.device
     P, T, D = weights.shape
-    _check("weights", weights, (P, T, D), torch.int32, dev, who)
+    tensor(who, "weights", weights, (P, T, D), torch.int32, dev)
     if t_counts is not None:
-        _check("t_counts", t_counts, (P,), torch.int32, dev, who)
+        tensor(who, "t_counts", t_counts, (P,), torch.int32, dev)
     if d_counts is not None:
-        _check("d_counts", d_counts, (P,), torch.int32, dev, who)
+        tensor(who, "d_counts", d_counts, (P,), torch.int32, dev)
     if out is None:
         out = (torch.empty((P, T), dtype=torch.int32, device=dev), torch.empty((P, D), dtype=torch.int32, device=dev))
     else:
-        _check("out row_of_slot", out[0], (P, T), torch.int32, dev, who)
-        _check("out slot_of_row", out[1], (P, D), torch.int32, dev, who)
-    L = lib()
-    args = (_ptr(weights), P, T, D, _ptr(t_counts), _ptr(d_counts), _ptr(out[0]), _ptr(out[1]))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(L.yh_assign(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "assign")
-    elif dev.type == "cpu":
-        check(L.yh_assign_host(*args, int(threads)), "assign_host")
-    else:
-        raise ValueError(f"{who}: unsupported device {dev}")
+        tensor(who, "out row_of_slot", out[0], (P, T), torch.int32, dev)
+        tensor(who, "out slot_of_row", out[1], (P, D), torch.int32, dev)
+    run(who, "assign", dev, (weights, P, T, D, t_counts, d_counts, out[0], out[1]), threads)
     return out[0], out[1]
 
 
@@ -352,29 +304,19 @@ def embed_quantize(e, count=None, out=None, threads=0):
     feature"). count (1,) i32 or None: rows at or beyond it give zeros. dim % 64 == 0, 64 <= dim <=
     2048. cuda tensors run the kernel on the current stream, CPU tensors the host twin: the same
     bytes."""
-    from ._lib import check, lib
     if not isinstance(e, torch.Tensor) or e.dim() != 2:
         raise ValueError("yolo_hip.track: e must be a (rows, dim) tensor")
     dev = e.device
     rows, dim = e.shape
-    _check("e", e, (rows, dim), torch.float32, dev)
+    tensor(_WHO, "e", e, (rows, dim), torch.float32, dev)
     _check_dim(dim)
     if count is not None:
-        _check("count", count, (1,), torch.int32, dev)
+        tensor(_WHO, "count", count, (1,), torch.int32, dev)
     if out is None:
         out = torch.empty((rows, dim), dtype=torch.int8, device=dev)
     else:
-        _check("out", out, (rows, dim), torch.int8, dev)
-    L = lib()
-    args = (_ptr(e), rows, dim, _ptr(count), _ptr(out))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(L.yh_embed_quantize(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                  "embed_quantize")
-    elif dev.type == "cpu":
-        check(L.yh_embed_quantize_host(*args, int(threads)), "embed_quantize_host")
-    else:
-        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+        tensor(_WHO, "out", out, (rows, dim), torch.int8, dev)
+    run(_WHO, "embed_quantize", dev, (e, rows, dim, count, out), threads)
     return out
 
 
@@ -385,35 +327,25 @@ def embed_similarity(a, b, a_index=None, out=None, threads=0):
     a_index[i] (None: block i), a block out of range counts as zeros. -> (B, ra, rb) int32. Two
     `embed_quantize` rows give 16129 times their cosine. cuda tensors run the int8 MFMA kernel on
     the current stream, CPU tensors the host twin: the same numbers."""
-    from ._lib import check, lib
     if not isinstance(a, torch.Tensor) or a.dim() != 3 or not isinstance(b, torch.Tensor) or b.dim() != 3:
         raise ValueError("yolo_hip.track: a must be (nblocks, ra, dim) and b (B, rb, dim)")
     dev = a.device
     nblocks, ra, dim = a.shape
     B, rb = b.shape[0], b.shape[1]
     _check_dim(dim)
-    _check("b", b, (B, rb, dim), torch.int8, dev)
+    tensor(_WHO, "b", b, (B, rb, dim), torch.int8, dev)
     if a.dtype != torch.int8 or a.device != dev:
         raise TypeError("yolo_hip.track: a must be int8 on b's device")
     if ra > 0 and nblocks > 0 and (a.stride(2) != 1 or a.stride(1) != dim or (nblocks > 1 and a.stride(0) < ra * dim)):
         raise ValueError("yolo_hip.track: the blocks of a must be contiguous and must not overlap")
     stride = a.stride(0) if nblocks > 1 else ra * dim
     if a_index is not None:
-        _check("a_index", a_index, (B,), torch.int32, dev)
+        tensor(_WHO, "a_index", a_index, (B,), torch.int32, dev)
     if out is None:
         out = torch.empty((B, ra, rb), dtype=torch.int32, device=dev)
     else:
-        _check("out", out, (B, ra, rb), torch.int32, dev)
-    L = lib()
-    args = (_ptr(a), stride, nblocks, _ptr(a_index), _ptr(b), B, ra, rb, dim, _ptr(out))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            check(L.yh_embed_similarity(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                  "embed_similarity")
-    elif dev.type == "cpu":
-        check(L.yh_embed_similarity_host(*args, int(threads)), "embed_similarity_host")
-    else:
-        raise ValueError(f"yolo_hip.track: unsupported device {dev}")
+        tensor(_WHO, "out", out, (B, ra, rb), torch.int32, dev)
+    run(_WHO, "embed_similarity", dev, (a, stride, nblocks, a_index, b, B, ra, rb, dim, out), threads)
     return out
 
 
@@ -507,15 +439,10 @@ class Tracker:
             dets, counts = dets.dets, dets.counts
         if self.reid_dim is None and (embed is not None or feat_counts is not None or embed_total is not None):
             raise ValueError("yolo_hip.Tracker: embeddings need a Tracker made with reid_dim")
-        if stream_ids is not None and not isinstance(stream_ids, torch.Tensor):
-            host = [int(v) for v in stream_ids]
-            if len(set(host)) != len(host):
-                raise ValueError("yolo_hip.Tracker: stream_ids must be distinct")
-            if any(not 0 <= v < self.streams for v in host):
-                raise ValueError(f"yolo_hip.Tracker: stream_ids must lie in [0, {self.streams})")
-            stream_ids = torch.tensor(host, dtype=torch.int32).to(self.device, non_blocking=True)
-        elif stream_ids is None and isinstance(dets, torch.Tensor) and dets.dim() == 3 and dets.shape[0] > self.streams:
-            raise ValueError(f"yolo_hip.Tracker: a batch of {dets.shape[0]} rows for {self.streams} streams")
+        if not isinstance(stream_ids, torch.Tensor):     # a tensor goes to the kernel unread
+            batch = dets.shape[0] if isinstance(dets, torch.Tensor) and dets.dim() == 3 else 0   # `track` complains
+            if stream_ids is not None or batch > self.streams:
+                stream_ids = host_stream_ids("yolo_hip.Tracker", stream_ids, self.streams, batch, self.device, "rows")
         if motion is not None:                   # the camera's motion first, on the same stream
             warp(self.state, motion, self.max_tracks, reid_dim=self.reid_dim, stream_ids=stream_ids, threads=threads)
         if self.reid_dim is None:
