@@ -980,8 +980,11 @@ int yh_set_graph(yh_handle* h, int enable);
 /* Kernel that runs op `index` at (batch, height, width): for a dense conv of a
  * 16-bit handle the conv_mx plan the per-shape tuner picked on the first
  * yh_forward at that shape (e.g. "mxr_k3s1_na2_mb2_b1x2_nb2"; every plan is
- * bit-identical), "gemm_f32" on the fp32 handle, for the other ops the op's
- * kernel name. YH_ESTATE before that forward. */
+ * bit-identical), "gemm_f32" on the fp32 handle, for the attention the kernel
+ * the handle's switches and the map select ("psa_attention_full<8>",
+ * "psa_attention_full<16>", "psa_attention_lds+pe_add",
+ * "psa_attention_mfma+pe_add"; "psa_attention" on the fp32 handle), for the
+ * other ops the op's kernel name. YH_ESTATE before that forward. */
 int yh_op_kernel(const yh_handle* h, int index, int batch, int height, int width, const char** name);
 
 /* Force conv plan `kernel` (an index into each conv's candidate list, clamped)

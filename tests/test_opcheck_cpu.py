@@ -1,24 +1,20 @@
 """The per-op interval oracle (tests/_opcheck.py) itself, on the CPU: it accepts an fp32
 evaluation of each op (torch's own fp32 kernels, a different summation order than the
 device's) rounded like the device rounds, and it rejects a one-ulp change of a pinned
-element. Runs the oracle on the v11_n synthetic weights at small shapes."""
+element. Runs the oracle on the v11_n synthetic weights at small shapes. The fp32 evaluations
+are tests/_op_parity.py's (fp32_layer, fp32_attention), the ones the GPU edge tests take their
+over1 bar from.
+
+test_attention_oracle_rejects_an_off_by_one_key_mask documents what the small-map GPU cases
+(tests/test_gpu_op_parity_edges.py) can see: an attention that drops the last key, or counts one
+key row past the last token, leaves its intervals at T = 4, 15, 49 and 55."""
 import pytest
 import torch
-import torch.nn.functional as F
 
 import _opcheck as oc
+from _op_parity import fp32_attention
+from _op_parity import fp32_layer as _fp32_layer
 from _util import make_model
-
-
-def _fp32_layer(x, desc, params, dtype, res=None):
-    w, b = params(desc)
-    y = F.conv2d(x.float(), w.float(), b.float(), desc["s"], desc["k"] // 2, groups=desc["g"])
-    if desc["act"]:
-        y = F.silu(y)
-    y = y.to(dtype)
-    if res is not None:
-        y = (y.float() + res.float()).to(dtype)
-    return y
 
 
 def _desc(name, model, act=1, s=1):
@@ -26,6 +22,10 @@ def _desc(name, model, act=1, s=1):
     conv = getattr(m, "conv", m)
     return dict(name=name, k=conv.kernel_size[0], s=s, g=conv.groups, act=act, cin=conv.in_channels,
                 cout=conv.out_channels, bias=int(conv.bias is not None))
+
+
+# v11_n's positional DWConv (2 heads)
+PE = dict(name="net.p5.3.res_m.0.conv1.conv1", k=3, s=1, g=128, act=0, cin=128, cout=128, bias=0)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
@@ -62,20 +62,12 @@ def test_attention_and_dfl_intervals_hold_fp32_evaluations():
     model = make_model("n")
     params = oc.Params(model.state_dict(), dtype)
     g = torch.Generator().manual_seed(4)
-    heads, T, H, W = 2, 64, 8, 8
+    heads, H, W = 2, 8, 8
     qkv = torch.randn(1, heads * 128, H, W, generator=g).to(dtype)
-    pe = dict(name="net.p5.3.res_m.0.conv1.conv1", k=3, s=1, g=heads * 64, act=0, cin=heads * 64,
-              cout=heads * 64, bias=0)
+    pe = dict(PE)
     lo, hi = oc.attention_op({"in0": qkv.double()}, {"convs": [pe]}, params, dtype, heads)
     # fp32 evaluation with the softmax weights rounded to the dtype before P.V (as the device)
-    t = qkv.float().reshape(1, heads, 128, T)
-    q, k, v = t[:, :, :32], t[:, :, 32:64], t[:, :, 64:]
-    s = torch.einsum("bhcq,bhck->bhqk", q, k) * (32 ** -0.5)
-    p = torch.exp(s - s.amax(-1, keepdim=True))
-    o = torch.einsum("bhqk,bhck->bhqc", p.to(dtype).float(), v) / p.sum(-1, keepdim=True)
-    o = o.to(dtype).float().permute(0, 1, 3, 2).reshape(1, heads * 64, H, W)
-    pw, pb = params(pe)
-    y = (o + F.conv2d(v.reshape(1, heads * 64, H, W), pw.float(), pb.float(), 1, 1, groups=heads * 64)).to(dtype)
+    y = fp32_attention(qkv, pe, params, dtype, heads)
     with oc.exact_values():
         ref, _ = oc.attention_op({"in0": qkv.double()}, {"convs": [pe]}, params, dtype, heads)
     st = oc.compare(y, lo, hi, ref, dtype, "attention")
@@ -93,3 +85,41 @@ def test_attention_and_dfl_intervals_hold_fp32_evaluations():
         bref, _ = oc.dfl_box(lg.double(), lg.double(), 8, dtype)
     st = oc.compare(box, blo, bhi, bref, dtype, "dfl")
     assert st["bad"] == 0, st
+
+
+def _drop_last_key(k, v):
+    return k[..., :-1], v[..., :-1]
+
+
+def _extra_zero_key(k, v):
+    z = lambda t: torch.cat([t, torch.zeros_like(t[..., :1])], -1)
+    return z(k), z(v)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("H,W", [(2, 2), (3, 5), (7, 7), (5, 11), (17, 17)])
+def test_attention_oracle_rejects_an_off_by_one_key_mask(dtype, H, W):
+    """randn qkv, 2 heads, batch 2, T = H * W tokens: the fp32 evaluation lies inside every
+    interval; the same evaluation with the last key masked away (a key mask one short), or with
+    one all-zero key row past the last token counted (a key mask one long: score 0, value 0, as
+    the zero rows the kernels stage), does not.
+    Known limit of the oracle: at T = 289 (17 x 17) the extra zero key moves the softmax sum by
+    too little to leave the intervals (bf16: 0 of 73984 elements outside; fp16: 8, too few to
+    lean on), so only the dropped key is required to be rejected there. The effect of one key
+    shrinks like 1 / T while the proven bound does not, which is why the GPU cases lean on small T."""
+    model = make_model("n")
+    params = oc.Params(model.state_dict(), dtype)
+    heads, T = 2, H * W
+    qkv = torch.randn(2, heads * 128, H, W, generator=torch.Generator().manual_seed(100 + T)).to(dtype)
+    op = {"convs": [dict(PE)]}
+    lo, hi = oc.attention_op({"in0": qkv.double()}, op, params, dtype, heads)
+    with oc.exact_values():
+        ref, _ = oc.attention_op({"in0": qkv.double()}, op, params, dtype, heads)
+    bad = lambda keys: oc.compare(fp32_attention(qkv, PE, params, dtype, heads, keys=keys), lo, hi, ref, dtype,
+                                  f"T={T}")["bad"]
+    n_ok, n_drop, n_extra = bad(None), bad(_drop_last_key), bad(_extra_zero_key)
+    print(f"T={T} {dtype}: fp32 bad {n_ok}, last key dropped bad {n_drop}, extra zero key bad {n_extra} of {qkv.shape[0] * heads * 64 * T}")
+    assert n_ok == 0
+    assert n_drop > 0
+    if T != 289:
+        assert n_extra > 0

@@ -505,23 +505,37 @@ __global__ __launch_bounds__(256) void pe_add(const AttnArgs p, int B) {
     st_chunk(o, f_to_chunk<T>(acc));
 }
 
+// Which 16-bit kernel a map of T = Hs x Ws tokens runs on, the one place the choice is written:
+// the launcher switches on it and yh_op_kernel reports it. attn_full off: the chunked kernel +
+// pe_add where the full one applies; attn_lds off: the per-wave chunked kernel. The tests compare
+// all three bit for bit.
+enum AttnKernel { AK_FULL8, AK_FULL16, AK_LDS, AK_MFMA };
+AttnKernel attn_kernel(int T, int Hs, int Ws, int heads, int B, const LaunchCtx& ctx) {
+    const Tuning& tune = ctx.tune;
+    if (T <= AF_TMAX && Ws > 0 && Hs * Ws == T && tune.attn_full) {
+        // Every wave runs one 16-query block's serial chain over all key blocks, so the launch
+        // lasts about one chain when each wave has at most one block and every workgroup a CU
+        // of its own (one fits per CU: the K / V staging takes ~86 KB of LDS). Default: 8-wave
+        // workgroups, ceil(blocks / 8) per (image, head), when those fit the CUs in one round
+        // (v11_n, batch 32: 256 workgroups, 20 us); else 16-wave ones, two per (image, head)
+        // (27-28 us there; at one, 64 workgroups, 39 us). attn_nw (8 / 16) and attn_qs
+        // (workgroups per (image, head)) override.
+        const int nqb = (T + 15) >> 4, pairs = heads * B, q8 = (nqb + 7) / 8;
+        const int nw = tune.attn_nw ? (tune.attn_nw == 8 ? 8 : AF_NW) : (pairs * q8 <= ctx.num_cus ? 8 : AF_NW);
+        return nw == 8 ? AK_FULL8 : AK_FULL16;
+    }
+    return tune.attn_lds ? AK_LDS : AK_MFMA;
+}
+
 template <typename T>
 int launch_attention_t(const AttnArgs& a, int B, const LaunchCtx& ctx, hipStream_t s) {
     if (a.dk != DK || a.dh != DH) return (int)hipErrorInvalidValue;
     const Tuning& tune = ctx.tune;
     if constexpr (sizeof(T) == 2) {
-        // attn_full off: the chunked kernel + pe_add where the full one applies; attn_lds off: the
-        // per-wave chunked kernel. The tests compare all three bit for bit.
-        if (a.T <= AF_TMAX && a.Ws > 0 && a.Hs * a.Ws == a.T && tune.attn_full) {
-            // Every wave runs one 16-query block's serial chain over all key blocks, so the launch
-            // lasts about one chain when each wave has at most one block and every workgroup a CU
-            // of its own (one fits per CU: the K / V staging takes ~86 KB of LDS). Default: 8-wave
-            // workgroups, ceil(blocks / 8) per (image, head), when those fit the CUs in one round
-            // (v11_n, batch 32: 256 workgroups, 20 us); else 16-wave ones, two per (image, head)
-            // (27-28 us there; at one, 64 workgroups, 39 us). attn_nw (8 / 16) and attn_qs
-            // (workgroups per (image, head)) override.
-            const int nqb = (a.T + 15) >> 4, pairs = a.heads * B, q8 = (nqb + 7) / 8;
-            const int nw = tune.attn_nw ? (tune.attn_nw == 8 ? 8 : AF_NW) : (pairs * q8 <= ctx.num_cus ? 8 : AF_NW);
+        const AttnKernel ak = attn_kernel(a.T, a.Hs, a.Ws, a.heads, B, ctx);
+        if (ak == AK_FULL8 || ak == AK_FULL16) {
+            const int nqb = (a.T + 15) >> 4, q8 = (nqb + 7) / 8;
+            const int nw = ak == AK_FULL8 ? 8 : AF_NW;
             const int qs = std::max(1, std::min(tune.attn_qs > 0 ? tune.attn_qs : (nw == 8 ? q8 : 2), (nqb + nw - 1) / nw));
             const void* k = nw == 8 ? reinterpret_cast<const void*>(&psa_attention_full<T, 8>)
                                     : reinterpret_cast<const void*>(&psa_attention_full<T, AF_NW>);
@@ -534,7 +548,7 @@ int launch_attention_t(const AttnArgs& a, int B, const LaunchCtx& ctx, hipStream
                                    af_lds_bytes(a.T), s, a, B);
             return (int)hipGetLastError();
         }
-        if (!tune.attn_lds) {
+        if (ak == AK_MFMA) {
             const dim3 g((a.T + 63) / 64, a.heads, B);
             hipLaunchKernelGGL((psa_attention_mfma<T>), g, dim3(256), 0, s, a);
         } else {
@@ -559,6 +573,17 @@ int launch_attention(int dtype, const AttnArgs& a, int B, const LaunchCtx& ctx, 
         case BF16: return launch_attention_t<__bf16>(a, B, ctx, s);
     }
     return (int)hipErrorInvalidValue;
+}
+
+const char* attention_kernel_name(int dtype, int T, int Hs, int Ws, int heads, int B, const LaunchCtx& ctx) {
+    if (dtype == F32) return "psa_attention";
+    switch (attn_kernel(T, Hs, Ws, heads, B, ctx)) {
+        case AK_FULL8: return "psa_attention_full<8>";
+        case AK_FULL16: return "psa_attention_full<16>";
+        case AK_LDS: return "psa_attention_lds+pe_add";
+        case AK_MFMA: return "psa_attention_mfma+pe_add";
+    }
+    return "attention";
 }
 
 }  // namespace yh

@@ -429,6 +429,8 @@ int launch_dwconv(int dtype, const DwArgs& a, hipStream_t s);
 int launch_silu_pairs(int dtype, const float* x, unsigned* ys, unsigned* yp, size_t n, hipStream_t s);
 int launch_sppf(int dtype, const PoolArgs& a, const LaunchCtx& ctx, hipStream_t s);
 int launch_attention(int dtype, const AttnArgs& a, int B, const LaunchCtx& ctx, hipStream_t s);
+// the kernel(s) launch_attention runs for a map of T = Hs x Ws tokens (yh_op_kernel)
+const char* attention_kernel_name(int dtype, int T, int Hs, int Ws, int heads, int B, const LaunchCtx& ctx);
 int launch_decode(int dtype, const DecodeArgs& a, hipStream_t s);
 int launch_set_io(void** io, const void* x, void* y, hipStream_t s);
 int launch_nms(int dtype, const NmsArgs& a, hipStream_t s);

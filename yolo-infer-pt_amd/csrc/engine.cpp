@@ -243,6 +243,10 @@ int yh_op_kernel(const yh_handle* h, int index, int batch, int height, int width
             if (name) *name = yh::op_kind_name(op.kind);
             auto cp = n.csp_plan.find({yh::GraphKey{batch, height, width}, index});
             if (name && cp != n.csp_plan.end()) *name = cp->second.c_str();
+            if (name && op.kind == yh::OP_ATTN) {
+                const int lv = n.tensors[op.in[0].v.t].level, hs = height >> lv, ws = width >> lv;
+                *name = yh::attention_kernel_name(n.dtype, hs * ws, hs, ws, op.heads, batch, n.ctx());
+            }
             return;
         }
         if (n.dtype == yh::F32) {
