@@ -17,14 +17,14 @@ NET := engine net_build net_weights net_forward net_launch net_debug
 HOSTHIP := post_abi nms_host
 # kernels; the NOFMA ones promise bit-exact arithmetic against host code: no FMA contraction
 KERNELS := conv sppf attn decode conv_mx conv_rw head c3k2 c3k pwchain cls
-KERNELS_NOFMA := preprocess nms match merge track reid gallery assign motion
+KERNELS_NOFMA := preprocess nms match merge fuse track reid gallery assign motion
 # HIP-free translation units: plain C++, no device pass, no FMA contraction
-HOSTCXX := match_host merge_host track_host gallery_host assign_host motion_host
+HOSTCXX := match_host merge_host fuse_host track_host gallery_host assign_host motion_host
 
 objs = $(patsubst %,$(OBJDIR)/%.o,$(1))
 OBJS := $(call objs,$(NET) $(HOSTHIP) $(KERNELS) $(KERNELS_NOFMA) $(HOSTCXX))
 HOST_H := $(SRC)/host_util.h $(SRC)/host_parallel.h $(SRC)/box_math.h \
-          $(SRC)/match_host.h $(SRC)/merge_host.h $(SRC)/track_host.h $(SRC)/gallery_host.h \
+          $(SRC)/match_host.h $(SRC)/merge_host.h $(SRC)/fuse_host.h $(SRC)/track_host.h $(SRC)/gallery_host.h \
           $(SRC)/assign_host.h $(SRC)/motion_host.h
 
 all: $(OUT)
@@ -51,7 +51,7 @@ $(call objs,$(HOSTCXX)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/%.h $(SRC)/box_math.
 # the decode's value arithmetic, shared by its kernels and the fused head's
 $(call objs,decode head): $(SRC)/head_math.h
 # each shares its arithmetic with its host twin through box_math.h and the twin's header
-$(call objs,match merge track motion): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
+$(call objs,match merge fuse track motion): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
 # the appearance kernels share the tracker's header: the twins live in track_host.cpp
 $(OBJDIR)/reid.o: $(SRC)/track_host.h $(SRC)/box_math.h
 # the int8 MFMA kernels share their fragment loads and lane map; the search shares its candidate
@@ -67,7 +67,8 @@ $(OBJDIR)/track_host.o: $(SRC)/assign_host.h
 # the motion estimates promise the host twins' bytes down to the last fp32 operations; the compiler
 # pairs those into packed fp32 instructions (v_pk_mul_f32, v_pk_add_f32) when left to itself, and the
 # file is built without them: scalar fp32 only, one rounding per operation as the rules say
-$(OBJDIR)/motion.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# (the fusion's sums and quotients make the same promise)
+$(call objs,motion fuse): HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # reports its argument errors through host_util.h's guarded(); its host functions use the pool
 $(OBJDIR)/preprocess.o: $(SRC)/host_util.h $(SRC)/host_parallel.h
 

@@ -23,6 +23,9 @@
  *                       has no tiled inference): the inverse of the letterbox of utils/dataset.py:95-103,
  *                       292-313 per tile, plus a cross-tile greedy NMS under the torchvision.ops.nms contract
  *   yh_merge_host       the same in host memory
+ *   yh_fuse             no reference counterpart (the reference runs one pass of one model): weighted
+ *                       boxes fusion of the passes of test-time augmentation or of an ensemble
+ *   yh_fuse_host        the same in host memory
  *   yh_letterbox        utils/dataset.py:95-103, 292-313, 86-88: eval-mode load_image resize
  *                       (cv2 INTER_LINEAR) + zero border + HWC->CHW, BGR->RGB, on the device
  *   yh_letterbox_host   the same on the host (Dataset.__getitem__ in the loader workers)
@@ -326,6 +329,69 @@ int yh_merge_host(const float* dets, const int* counts, int tiles, int max_det,
                   const float* tile_xf, const int* tile_offsets, const float* image_wh,
                   int images, int max_tiles, double iou_threshold, int max_out,
                   float* out, int* out_counts, int threads);
+
+/* Largest max_groups * max_det yh_fuse / yh_fuse_host accept: the candidates of one image. The
+ * kernel keeps an 8-byte sort key and six running sums (24 bytes) per candidate slot in LDS: 128 KiB
+ * of the 160 KiB of a CU at 4096, which covers eight passes of 300 rows (2400). */
+#define YH_FUSE_MAX_CAND 4096
+
+/* Weighted boxes fusion (Solovyev, Wang, Gabruseva 2021) of several looks at the same images - the
+ * passes of test-time augmentation (mirror, other scales) or the models of an ensemble - in one
+ * launch. A group is the NMS output of one pass (or model) for one image; where yh_merge keeps the
+ * best-scored box of a set of duplicates, this averages them with their confidences as weights and
+ * lowers the confidence of a box that few groups found.
+ *   dets (groups, max_det, 6), counts (groups): as yh_nms writes them. counts is clamped to
+ *       [0, max_det]; rows at or beyond counts[g] may be uninitialised and are never read.
+ *   group_xf (groups, 6) f32: sx, sy, px, py, ox, oy of each group, as yh_merge's tile_xf; sx < 0
+ *       (sy < 0) is a mirrored pass.
+ *   group_weight (groups) f32, each > 0: the weight of the pass or model.
+ *   group_offsets (images + 1) int32 ascending: image i owns groups group_offsets[i] ..
+ *       group_offsets[i + 1]. Groups beyond the last offset (padding) are never visited. Each range
+ *       is clamped to [0, groups] and to max_groups groups.
+ *   image_wh (images, 2) f32: W, H of the source image.
+ *   max_groups: the caller's bound on groups per image; max_groups * max_det <= YH_FUSE_MAX_CAND.
+ *   out (images, max_out, 6) f32 = x1, y1, x2, y2, score, class in source pixels; out_counts (images)
+ *       int32. Every byte of both is written; rows beyond an image's count are 0; an image with no
+ *       groups has count 0.
+ * Per image, identical on device and host bit for bit; all arithmetic is fp32, one rounding per
+ * operation, no FMA:
+ *   1. candidates: every valid row of every group of the image, at position (group, row) in input
+ *      order. The box is mapped as in yh_merge step 2 (t = x - px; t = t * sx; X = t + ox; y alike);
+ *      if the mapped X2 < X1 the two are swapped, likewise Y; then it is clipped to [0, W] / [0, H]
+ *      and a box with x2 <= x1 or y2 <= y1 is dropped. The class must be an index as yh_nms writes
+ *      it, an integral value in [0, 1048575): other rows are dropped. s = score * group_weight[g]; a
+ *      candidate with s < skip_score is dropped;
+ *   2. order: classes are independent; within a class candidates are taken by s descending, ties to
+ *      the lower position;
+ *   3. clustering, sequential within a class: cluster k keeps S = sum s_i, Sx1 = sum s_i * x1_i
+ *      (Sy1, Sx2, Sy2 alike; each product rounded, then added, in arrival order) and its member
+ *      count n. Its fused box is F = (Sx1 / S, Sy1 / S, Sx2 / S, Sy2 / S), correctly rounded. A
+ *      candidate b is compared with every cluster of its class by yh_merge's IoU,
+ *      inter / (area_F + area_b - inter) (0 when inter is 0); the largest wins, ties to the lowest k.
+ *      If that IoU is, as a double, > iou_threshold the candidate joins the cluster - sums and F are
+ *      updated - else it opens a new cluster. Several rows of one group may join one cluster;
+ *   4. a cluster's box is F, its class the class of its members, its score
+ *      ((S / n) * min(n, Wtot)) / Wtot with Wtot the fp32 sum of the image's group weights in group
+ *      order and n, min in fp32: a box only one of three equal passes found keeps a third;
+ *   5. the clusters of all classes are written by score descending, ties to the lower class and
+ *      then the earlier cluster; the first max_out are written.
+ * Boxes must be finite and scores finite and positive.
+ * yh_fuse: device pointers, one workgroup per image, asynchronous on `stream`, allocates nothing,
+ * never synchronises. yh_fuse_host: the same for host pointers, images in parallel over `threads`
+ * (<= 0: all hardware threads), synchronous.
+ * YH_EINVAL (message in yh_last_error()): a negative size, max_groups < 1, max_groups * max_det above
+ * YH_FUSE_MAX_CAND, a NULL required pointer; in yh_fuse_host also a weight that is not > 0 in a
+ * group some image owns (on the device the weights are the caller's contract: nothing is read back). */
+int yh_fuse(const float* dets, const int* counts, int groups, int max_det,
+            const float* group_xf, const float* group_weight, const int* group_offsets,
+            const float* image_wh, int images, int max_groups,
+            double iou_threshold, float skip_score, int max_out,
+            float* out, int* out_counts, void* stream);
+int yh_fuse_host(const float* dets, const int* counts, int groups, int max_det,
+                 const float* group_xf, const float* group_weight, const int* group_offsets,
+                 const float* image_wh, int images, int max_groups,
+                 double iou_threshold, float skip_score, int max_out,
+                 float* out, int* out_counts, int threads);
 
 /* Multi-object tracking over video streams, one launch per frame for all streams of a batch
  * (no reference counterpart: the rules below are the specification; tests/_track_cases.py

@@ -442,6 +442,10 @@ int launch_match(const float* dets, const int* counts, int batch, int max_det, c
 int launch_merge(const float* dets, const int* counts, int tiles, int max_det, const float* tile_xf,
                  const int* tile_offsets, const float* image_wh, int images, int max_tiles, double iou_threshold,
                  int max_out, float* out, int* out_counts, hipStream_t s);
+// fuse.hip: the NMS outputs of several passes over the same images -> one fused box per cluster (yh_fuse)
+int launch_fuse(const float* dets, const int* counts, int groups, int max_det, const float* group_xf,
+                const float* group_weight, const int* group_offsets, const float* image_wh, int images, int max_groups,
+                double iou_threshold, float skip_score, int max_out, float* out, int* out_counts, hipStream_t s);
 // track.hip: one frame of every stream of a batch through its track table (yh_track); p by value;
 // optimal: the associations solve an assignment instead of walking greedily (yh_track2)
 int launch_track(const float* dets, const int* counts, int batch, int max_det, const int* stream_ids, void* state,

@@ -1,4 +1,4 @@
-// C ABI of the stages after the forward, none of which needs a handle: yh_nms, yh_match, yh_merge, yh_track, yh_embed_quantize, yh_embed_similarity,
+// C ABI of the stages after the forward, none of which needs a handle: yh_nms, yh_match, yh_merge, yh_fuse, yh_track, yh_embed_quantize, yh_embed_similarity,
 // yh_track_reid, yh_gallery_search, yh_gallery_enrol, yh_assign, yh_track2, yh_track_reid2, yh_motion, yh_track_warp
 // and their *_host twins.
 #include <algorithm>
@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "assign_host.h"
+#include "fuse_host.h"
 #include "gallery_host.h"
 #include "host_util.h"
 #include "match_host.h"
@@ -126,6 +127,32 @@ int yh_merge_host(const float* dets, const int* counts, int tiles, int max_det, 
                                max_tiles, max_out, out, out_counts));
         yh_merge_host_run(dets, counts, tiles, max_det, tile_xf, tile_offsets, image_wh, images, max_tiles,
                           iou_threshold, max_out, out, out_counts, threads);
+    });
+}
+
+int yh_fuse(const float* dets, const int* counts, int groups, int max_det, const float* group_xf,
+            const float* group_weight, const int* group_offsets, const float* image_wh, int images, int max_groups,
+            double iou_threshold, float skip_score, int max_out, float* out, int* out_counts, void* stream) {
+    return guarded([&] {
+        checked(yh_fuse_check(dets, counts, groups, max_det, group_xf, group_weight, group_offsets, image_wh, images,
+                              max_groups, max_out, out, out_counts));
+        const int rc = yh::launch_fuse(dets, counts, groups, max_det, group_xf, group_weight, group_offsets, image_wh,
+                                       images, max_groups, iou_threshold, skip_score, max_out, out, out_counts,
+                                       (hipStream_t)stream);
+        yh::launched("fuse", rc);
+    });
+}
+
+int yh_fuse_host(const float* dets, const int* counts, int groups, int max_det, const float* group_xf,
+                 const float* group_weight, const int* group_offsets, const float* image_wh, int images,
+                 int max_groups, double iou_threshold, float skip_score, int max_out, float* out, int* out_counts,
+                 int threads) {
+    return guarded([&] {
+        checked(yh_fuse_check(dets, counts, groups, max_det, group_xf, group_weight, group_offsets, image_wh, images,
+                              max_groups, max_out, out, out_counts));
+        checked(yh_fuse_check_weights(group_weight, group_offsets, images, groups, max_groups));
+        yh_fuse_host_run(dets, counts, groups, max_det, group_xf, group_weight, group_offsets, image_wh, images,
+                         max_groups, iou_threshold, skip_score, max_out, out, out_counts, threads);
     });
 }
 

@@ -3,7 +3,8 @@
 `Engine` wraps one yh_handle (include/yolo_hip.h); `nms` is the on-device
 non_max_suppression; `Evaluator` (yolo_hip.evaluate) is the batched mAP
 evaluation over those detections; `Detector` (yolo_hip.detect) returns detections in
-source-image pixels, optionally from tiled inference (`tiles`, `tile_transform`, `merge`),
+source-image pixels, optionally from tiled inference (`tiles`, `tile_transform`, `merge`) or from
+test-time augmentation (`Detector(tta=...)`; `fuse_boxes` is the weighted boxes fusion alone, for ensembles),
 from BGR or `NV12` video frames on a square or rectangular canvas (`letterbox_frames`,
 `rect_canvas`; yolo_hip.preprocess), and `crop_rois` cuts one fixed-size crop per detection from
 those frames for a second-stage model (`Crops`);
@@ -32,7 +33,7 @@ def __getattr__(name):
     if name in ("Detector", "Detections", "merge"):
         from . import detect
         return getattr(detect, name)
-    if name in ("tiles", "tile_transform"):
+    if name in ("tiles", "tile_transform", "fuse_boxes", "pass_transform"):
         from . import detect
         return getattr(detect, name)
     if name in ("NV12", "letterbox_frames", "rect_canvas", "crop_rois", "Crops"):

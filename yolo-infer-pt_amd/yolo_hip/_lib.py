@@ -20,6 +20,7 @@ ABI_VERSION = 7
 YH_PIX_BGR, YH_PIX_NV12 = 0, 1
 YH_YUV_BT601, YH_YUV_BT709 = 0, 1
 MERGE_MAX_CAND = 8192   # YH_MERGE_MAX_CAND: candidates (max_tiles * max_det) per image of yh_merge
+FUSE_MAX_CAND = 4096    # YH_FUSE_MAX_CAND: candidates (max_groups * max_det) per image of yh_fuse
 
 
 class YhVariant(ctypes.Structure):
@@ -94,6 +95,8 @@ _PROTOS = {
                          c_void_p),
     **_twins("yh_merge", c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
                          c_int, c_void_p, c_void_p),
+    **_twins("yh_fuse", c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                        c_float, c_int, c_void_p, c_void_p),
     "yh_track_state_bytes": (c_size_t, [c_int, c_int]),
     **_twins("yh_track", c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                          c_void_p, c_void_p, c_void_p, c_void_p),

@@ -8,8 +8,12 @@ coordinates of the square network canvas. This module closes the loop:
   merge           yh_merge / yh_merge_host: map the tile detections back and, for images of two
                   or more tiles, drop duplicates across tile borders with a second greedy NMS -
                   one launch for all images of a call
+  fuse_boxes      yh_fuse / yh_fuse_host: weighted boxes fusion of several looks at the same images
+                  (the passes of test-time augmentation, the models of an ensemble) - one launch
+  pass_transform  the six floats of a test-time-augmentation pass: the inverse letterbox, mirrored
   Detector        images in, source-pixel detections out: crops as views of the device-resident
-                  image, letterbox, DetectPipeline (yh_forward_u8 + yh_nms), one merge
+                  image, letterbox, DetectPipeline (yh_forward_u8 + yh_nms), one merge - or, with
+                  tta=, several whole-image passes and one fusion
 
 There is no counterpart in the reference (it never leaves the canvas: main.py moves the labels
 into canvas space instead, and it has no tiled inference); the semantics are those stated in
@@ -24,9 +28,10 @@ import numpy as np
 import torch
 
 from ._call import run, tensor
-from ._lib import MERGE_MAX_CAND
+from ._lib import FUSE_MAX_CAND, MERGE_MAX_CAND
 
 _WHO = "yolo_hip.merge"
+_FUSE = "yolo_hip.fuse_boxes"
 
 
 def _starts(length, tile, step):
@@ -115,6 +120,64 @@ def merge(dets, counts, tile_xf, tile_offsets, image_wh, max_tiles, iou=0.65, ma
     return o, oc
 
 
+def pass_transform(height, width, canvas, mirror=False):
+    """(sx, sy, px, py, ox, oy) as np.float32 of one test-time-augmentation pass over a whole height x
+    width frame letterboxed to canvas = (H, W): `tile_transform` of the whole frame, and for a pass
+    that was flipped left-right after the letterbox the same composed with x -> W - x: sx is negated
+    and px becomes W - left, so that X = (x - px) * sx + ox lands in source pixels (x2 maps left of
+    x1; yh_fuse swaps them)."""
+    sx, sy, px, py, ox, oy = tile_transform((0, 0, width, height), canvas)
+    if mirror:
+        sx, px = -sx, np.float32(int(canvas[1])) - px
+    return sx, sy, px, py, ox, oy
+
+
+def fuse_boxes(dets, counts, group_xf, group_weight, group_offsets, image_wh, max_groups, iou=0.55, skip_score=0.0,
+               max_out=300, out=None, threads=0):
+    """Weighted boxes fusion of several looks at the same images, all images of a call in one launch.
+
+    A group is the `nms` output of one pass or one model for one image: dets (G, max_det, 6) f32 and
+    counts (G,) i32 (rows at or beyond counts[g] are never read); group_xf (G, 6) f32 rows of
+    `pass_transform` / `tile_transform` (identity: 1, 1, 0, 0, 0, 0); group_weight (G,) f32 > 0;
+    group_offsets (N + 1,) i32 ascending - image i owns groups group_offsets[i]:group_offsets[i + 1],
+    groups beyond the last offset are never visited; image_wh (N, 2) f32 (W, H); max_groups: a bound
+    on the groups of one image, max_groups * max_det <= FUSE_MAX_CAND. All on one device, contiguous.
+    -> (out (N, max_out, 6) f32, out_counts (N,) i32); out=(out, out_counts) reuses buffers. Every
+    byte is written, rows beyond the count are 0.
+
+    Per class, boxes are clustered by IoU > `iou` against each cluster's confidence-weighted mean box;
+    a cluster comes out once with that box and the mean weighted confidence of its members, scaled
+    by min(members, sum of weights) / sum of weights (include/yolo_hip.h). For an ensemble, stack the
+    models' `nms` outputs image by image. cuda tensors run the HIP kernel (yh_fuse) asynchronously on
+    the current stream, CPU tensors the host twin (yh_fuse_host, `threads` <= 0: every hardware
+    thread)."""
+    if not isinstance(dets, torch.Tensor) or dets.dim() != 3:
+        raise ValueError("yolo_hip.fuse_boxes: dets must be a (G, max_det, 6) tensor")
+    dev = dets.device
+    G, md = dets.shape[0], dets.shape[1]
+    tensor(_FUSE, "dets", dets, (G, md, 6), torch.float32, dev)
+    tensor(_FUSE, "counts", counts, (G,), torch.int32, dev)
+    tensor(_FUSE, "group_xf", group_xf, (G, 6), torch.float32, dev)
+    tensor(_FUSE, "group_weight", group_weight, (G,), torch.float32, dev)
+    tensor(_FUSE, "group_offsets", group_offsets, (None,), torch.int32, dev)
+    if group_offsets.shape[0] < 1:
+        raise ValueError("yolo_hip.fuse_boxes: group_offsets must hold images + 1 entries")
+    N = group_offsets.shape[0] - 1
+    tensor(_FUSE, "image_wh", image_wh, (N, 2), torch.float32, dev)
+    max_out = int(max_out)
+    if out is None:
+        o = torch.empty((N, max(max_out, 0), 6), dtype=torch.float32, device=dev)
+        oc = torch.empty((N,), dtype=torch.int32, device=dev)
+    else:
+        o, oc = out
+        tensor(_FUSE, "out", o, (N, max_out, 6), torch.float32, dev)
+        tensor(_FUSE, "out_counts", oc, (N,), torch.int32, dev)
+    args = (dets, counts, G, md, group_xf, group_weight, group_offsets, image_wh, N, int(max_groups),
+            ctypes.c_double(iou), ctypes.c_float(skip_score), max_out, o, oc)
+    run(_FUSE, "fuse", dev, args, threads)
+    return o, oc
+
+
 class Detections:
     """Result of Detector.predict: dets (n, max_det, 6) f32 = x1, y1, x2, y2, score, class in source
     pixels and counts (n,) i32, both on the device; rows beyond an image's count are 0. frames:
@@ -152,6 +215,16 @@ class Detector:
     also takes preprocess.NV12 frames (image height and width are the planes'); they cannot be
     tiled (crops at odd offsets are out of scope): with `tile` set they raise ValueError.
 
+    tta=((scale, mirror), ...) is test-time augmentation: every pass letterboxes the whole source
+    frame onto a canvas of its own - the canvas sides times `scale`, rounded up to multiples of 32
+    - flips the letterboxed batch left-right when `mirror` is set, and runs it through a
+    DetectPipeline of that shape (one per distinct shape, sharing the engines and their streams);
+    the passes' detections are then fused by `fuse_boxes` at fuse_iou (default 0.55) with
+    tta_weights (default 1 per pass) - confidence-weighted mean boxes, and less confidence for a
+    box that few passes found - in one launch where the merge would run. Each pass keeps
+    min(max_det, FUSE_MAX_CAND // passes) rows. `tile` must be None: fusing partial boxes across
+    tile edges is out of scope. tta=None is the path above, unchanged.
+
     predict() never reads a device value on the host: sizes, tile lists and transforms come from
     the images' shapes. Stream safety, as yolo_hip.evaluate.Evaluator documents its own: the
     tile batches are forwarded on the pipeline's streams; predict() makes the caller's stream
@@ -162,7 +235,8 @@ class Detector:
     """
 
     def __init__(self, engines, size=640, batch=32, tile=None, overlap=0.2, full_image=False, conf=0.001, iou=0.65,
-                 merge_iou=None, max_det=300, tile_max_det=None, canvas=None):
+                 merge_iou=None, max_det=300, tile_max_det=None, canvas=None, tta=None, tta_weights=None,
+                 fuse_iou=0.55):
         from .pipeline import DetectPipeline
         self.size, self.batch = int(size), int(batch)
         self.tile = None if tile is None else int(tile)
@@ -183,6 +257,32 @@ class Detector:
             self.canvas = (ch, cw)
         self.pipe = DetectPipeline(engines, self.batch, ch, cw)
         self.device = self.pipe.eng.device
+        self.tta = None
+        if tta is not None:
+            self._init_tta(engines, tta, tta_weights, fuse_iou, ch, cw)
+
+    def _init_tta(self, engines, tta, weights, fuse_iou, ch, cw):
+        from .pipeline import DetectPipeline
+        if self.tile is not None:
+            raise ValueError("yolo_hip.Detector: tta needs tile=None (tiles are merged, not fused)")
+        passes = [(float(s), bool(m)) for s, m in tta]
+        if not passes or any(not s > 0.0 for s, _ in passes):
+            raise ValueError("yolo_hip.Detector: tta must hold (scale > 0, mirror) passes")
+        weights = [1.0] * len(passes) if weights is None else [float(w) for w in weights]
+        if len(weights) != len(passes) or any(not w > 0.0 for w in weights):
+            raise ValueError("yolo_hip.Detector: tta_weights must hold one weight > 0 per pass")
+        self.pass_max_det = min(self.max_det, FUSE_MAX_CAND // len(passes))
+        if self.pass_max_det < 1:
+            raise ValueError(f"yolo_hip.Detector: {len(passes)} passes do not fit FUSE_MAX_CAND = {FUSE_MAX_CAND}")
+        self.tta, self.tta_weights, self.fuse_iou = passes, weights, float(fuse_iou)
+        # one pipeline per distinct canvas shape. They share the engines, so they share the streams
+        # too: an engine's forwards stay on one stream whatever the shape, in submission order
+        self.pass_canvas = [tuple(max(1, -(-int(np.ceil(side * s)) // 32)) * 32 for side in (ch, cw)) for s, _ in passes]
+        self.pass_pipes = {(ch, cw): self.pipe}
+        for shape in self.pass_canvas:
+            if shape not in self.pass_pipes:
+                p = self.pass_pipes[shape] = DetectPipeline(engines, self.batch, *shape)
+                p.lane_streams, p.nms_stream = self.pipe.lane_streams, self.pipe.nms_stream
 
     def plan(self, shapes):
         """[(height, width), ...] -> (crops per image, tile_max_det, max_tiles): what predict() does
@@ -224,6 +324,8 @@ class Detector:
         if n == 0:
             return Detections(torch.zeros((0, self.max_det, 6), dtype=torch.float32, device=dev),
                               torch.zeros((0,), dtype=torch.int32, device=dev), [] if keep_frames else None)
+        if self.tta is not None:
+            return self._predict_tta(srcs, shapes, keep_frames)
         canvas = ch, cw = self.canvas or (self.size, self.size)
         # host-side geometry of every tile, uploaded as one pinned block (below):
         # [xf (padded tile axis) x 6 | wh n x 2 | offsets n + 1 (i32)]
@@ -271,4 +373,52 @@ class Detector:
                 pipe.wait(e)
             out = merge(tdets, tcounts, tile_xf, tile_offsets, image_wh, max_tiles, iou=self.merge_iou,
                         max_out=self.max_det)
+        return Detections(*out, srcs if keep_frames else None)
+
+    def _predict_tta(self, srcs, shapes, keep_frames):
+        """predict() with tta: every pass over every image is one group of one yh_fuse launch."""
+        from .preprocess import letterbox_frames
+        dev, n, P, B, md = self.device, len(srcs), len(self.tta), self.batch, self.pass_max_det
+        nb = (n + B - 1) // B
+        NP = nb * B                              # the image axis of a pass, padded to whole batches
+        # host-side geometry, uploaded as one pinned block: [xf n x P x 6 | weight n x P | wh n x 2 | offsets n + 1 (i32)]
+        xf = np.asarray([pass_transform(h, w, self.pass_canvas[p], self.tta[p][1]) for h, w in shapes for p in range(P)],
+                        dtype=np.float32)
+        G = n * P
+        stage = torch.zeros(6 * G + G + 2 * n + n + 1, dtype=torch.float32, pin_memory=True)
+        stage[:6 * G].view(G, 6).copy_(torch.from_numpy(xf.reshape(G, 6)))
+        stage[6 * G:7 * G].view(n, P).copy_(torch.tensor(self.tta_weights, dtype=torch.float32))
+        stage[7 * G:7 * G + 2 * n].view(n, 2).copy_(torch.tensor([[w, h] for h, w in shapes], dtype=torch.float32))
+        stage[7 * G + 2 * n:].view(torch.int32).copy_(torch.arange(0, G + 1, P, dtype=torch.int32))
+        on = stage.to(dev, non_blocking=True)
+        group_xf, weight = on[:6 * G].view(G, 6), on[6 * G:7 * G]
+        image_wh, offsets = on[7 * G:7 * G + 2 * n].view(n, 2), on[7 * G + 2 * n:].view(torch.int32)
+
+        # the pipelines write pass-major (whole batches of one pass); the pad images are blank canvases
+        pdets = torch.empty((P, NP, md, 6), dtype=torch.float32, device=dev)
+        pcounts = torch.empty((P, NP), dtype=torch.int32, device=dev)
+        if self.pipe.nms_stream is not None:     # written there, allocated (and fused) here
+            pdets.record_stream(self.pipe.nms_stream)
+            pcounts.record_stream(self.pipe.nms_stream)
+        with torch.cuda.device(dev):
+            done = []
+            for p, (shape, (_, mirror)) in enumerate(zip(self.pass_canvas, self.tta)):
+                pipe = self.pass_pipes[shape]
+                pipe.nms_kwargs = dict(confidence_threshold=self.conf, iou_threshold=self.iou, max_det=md)
+                for b in range(nb):
+                    part = srcs[b * B:(b + 1) * B]
+                    x = torch.empty((B, 3, *shape), dtype=torch.uint8, device=dev)
+                    letterbox_frames(part, shape, device=dev, out=x[:len(part)])
+                    if len(part) < B:
+                        x[len(part):].zero_()
+                    if mirror:
+                        x = torch.flip(x, dims=(3,))
+                    done.append(pipe.submit(x, out=(pdets[p, b * B:(b + 1) * B], pcounts[p, b * B:(b + 1) * B]))[3])
+            for e in done:
+                self.pipe.wait(e)
+            # image-major for the fusion: image i owns groups i * P .. (i + 1) * P (a copy, on this stream)
+            gdets = pdets[:, :n].transpose(0, 1).contiguous().view(G, md, 6)
+            gcounts = pcounts[:, :n].t().contiguous().view(G)
+            out = fuse_boxes(gdets, gcounts, group_xf, weight, offsets, image_wh, P, iou=self.fuse_iou,
+                             max_out=self.max_det)
         return Detections(*out, srcs if keep_frames else None)
