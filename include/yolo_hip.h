@@ -63,6 +63,10 @@
  *   yh_motion_field     no reference counterpart: translation plus zoom from a per-block motion field
  *                       on the same state, for cameras that zoom, climb or descend
  *   yh_motion_host, yh_motion_field_host, yh_track_warp_host   the same in host memory
+ *   yh_propagate_remember,
+ *   yh_propagate        no reference counterpart: a stream's tracks carried over the frames the detector
+ *                       skips, by a template search per track in the full-resolution frame
+ *   yh_propagate_remember_host, yh_propagate_host   the same in host memory
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -989,6 +993,94 @@ int yh_motion_field(const yh_frame* frames, int batch, const int* stream_ids, vo
 int yh_motion_field_host(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
                          int thumb_h, int thumb_w, const yh_motion_field_params* p, float* motion, int32_t* sad,
                          int32_t* field, int threads);
+
+/* Track propagation over the frames the detector skips (no reference counterpart: the rules below are
+ * the specification; tests/_propagate_cases.py restates them in numpy). A stack that runs the network
+ * on every N-th frame calls yh_propagate_remember on those frames, with the tracker's output rows, and
+ * yh_propagate on the frames in between: each remembered track is searched for in the new frame, at
+ * its own scale, and the rows that come out - in detection format - feed the unchanged yh_track*. It
+ * is a measurement from the frame per track, where yh_motion measures the camera. Everything up to
+ * the last few fp32 operations is integer arithmetic: the device and the host compute the same bytes.
+ * P = YH_PROPAGATE_P = 32 is the template side in cells, R = radius the search radius in cells,
+ * CMAX = YH_PROPAGATE_CMAX = 32 the largest cell side in source pixels.
+ *
+ *   frames, stream_ids: as for yh_motion (BGR or NV12, mixed, any sizes up to 2^20 a side, strided
+ *               rows; row b is a frame of stream stream_ids[b], NULL: of stream b; distinct ids).
+ *   state:      yh_propagate_state_bytes(streams, max_tracks) bytes, all-zero = no entries. Per stream
+ *               a 16-byte header (word 0 is the number of entries n, the other words are 0), then
+ *               max_tracks entries of 1088 bytes: int32 id; f32 box0[4], score, class (the remembered
+ *               row); int32 cw, ch (the cell size); int32 ox0, oy0 (the origin when remembered);
+ *               int32 ox, oy (the origin now); 12 zero bytes; the template, P * P luma bytes, row
+ *               major. Slots at or beyond n are never read. No pointers, the same bytes on host and
+ *               device: the state can be copied between them in the middle of a sequence.
+ *
+ * 1. Luma: rule 1 of yh_motion.
+ * 2. Geometry of a box (x1, y1, x2, y2). Each coordinate is first brought into [-2^20, 2^20] (NaN
+ *    counts as -2^20). bx0 = (int)floorf(x1), bx1 = (int)ceilf(x2), bw = max(1, bx1 - bx0),
+ *    cw = clamp((bw + 16) / 32, 1, CMAX), cx = (bx0 + bx1) >> 1 (arithmetic shift), ox = cx - 16 cw; ch
+ *    and oy likewise from y. Cell (i, j) relative to an origin (oy, ox) covers the source rows
+ *    oy + i ch .. oy + (i + 1) ch and the columns ox + j cw .. ox + (j + 1) cw (the end exclusive), each
+ *    pixel coordinate clamped into the frame (edge replicate); its value is (sum + n / 2) / n over its
+ *    n = cw ch luma bytes, unsigned and exact.
+ * 3. yh_propagate_remember, on a frame the detector ran on. For batch row b of stream s the rows
+ *    r < min(counts[b], max_det, max_tracks) of dets (batch, max_det, 6) / ids (batch, max_det) - a
+ *    yh_track* output - replace the stream's table: entry r gets the id, the box, score and class,
+ *    the geometry, (ox, oy) = (ox0, oy0) and the template of the cells (i, j) in [0, P)^2; n is that row
+ *    count (a negative count is 0). Slots at or beyond n keep their bytes. A row whose id is outside
+ *    [0, streams) touches nothing.
+ * 4. yh_propagate, on a skipped frame, per entry. With Wn the cells (i, j) in [-R, P + R)^2 of the
+ *    current frame relative to (oy, ox) and T the template, for every (dy, dx) in [-R, R]^2:
+ *    SAD(dy, dx) = sum |Wn[i + dy][j + dx] - T[i][j]| over [0, P)^2. The best shift minimises
+ *    (SAD, |dy| + |dx|, dy, dx) lexicographically, s0 is its SAD, and fx, fy are the fractions of
+ *    yh_motion's rule 4 (fp32, one rounding per operation, no FMA; 0 on an axis where the shift is
+ *    +-R). Then ox' = ox + dx cw, oy' = oy + dy ch, and in fp32, one rounding per operation, no FMA:
+ *      mx = (float)(ox' - ox0) + fx * (float)cw;  my = (float)(oy' - oy0) + fy * (float)ch;
+ *      box = (box0.x1 + mx, box0.y1 + my, box0.x2 + mx, box0.y2 + my);
+ *      cx = 0.5f * (box.x1 + box.x2);  cy = 0.5f * (box.y1 + box.y2).
+ *    Gate: the entry is dropped - no output row, removed from the table - when max_mad >= 0 and
+ *    s0 > max_mad * P * P, or unless 0 <= cx < W and 0 <= cy < H (a NaN fails). Otherwise (ox, oy)
+ *    becomes (ox', oy'). The fraction is never accumulated - a static object's box cannot creep - and
+ *    the template is not refreshed before the next yh_propagate_remember: nothing drifts into the
+ *    background.
+ * 5. Output. Per batch row the surviving entries in table order, compacted: dets (batch, max_out, 6)
+ *    f32 (box, remembered score, class), ids (batch, max_out) int32, sad (batch, max_out) int32 (s0),
+ *    counts (batch) = min(survivors, max_out); survivors beyond max_out stay in the table without a
+ *    row. The table is compacted the same way, the vacated slots are zeroed, n is the number of
+ *    survivors. Every output byte is written; rows beyond a count are 0. A row whose id is outside
+ *    [0, streams) has count 0 and touches no state.
+ * Limits of the model: translation only per object, at most R cells (R cw by R ch source pixels) per
+ * frame; no scale change, and no deformation beyond what the SAD gate tolerates. An object larger
+ * than 32 CMAX = 1024 pixels a side is matched by its central 1024 pixels.
+ *
+ * yh_propagate_remember, yh_propagate: asynchronous on `stream`, allocate nothing, never synchronise,
+ * use no atomics; one launch (remember), two launches (a search workgroup per entry, an emit workgroup
+ * per row) per 32 frames; state and workspace 4-byte aligned. workspace: caller-owned device memory of
+ * yh_propagate_workspace_bytes(batch, max_tracks) bytes (0 for illegal arguments), contents undefined
+ * before and after. The *_host twins: the same bytes for host pointers, rows in parallel over
+ * `threads` (<= 0: all hardware threads), synchronous.
+ * YH_EINVAL (message in yh_last_error()), nothing launched or written: a frame yh_letterbox_frames'
+ * validation rejects, or with a side above 2^20; radius outside [1, YH_PROPAGATE_MAX_RADIUS];
+ * max_tracks outside [1, YH_PROPAGATE_MAX_TRACKS]; a negative size; a NULL required pointer; a
+ * workspace that is too small (device entry). */
+#define YH_PROPAGATE_P 32
+#define YH_PROPAGATE_CMAX 32
+#define YH_PROPAGATE_MAX_RADIUS 16
+#define YH_PROPAGATE_MAX_TRACKS 256
+size_t yh_propagate_state_bytes(int streams, int max_tracks);
+size_t yh_propagate_workspace_bytes(int batch, int max_tracks);
+int yh_propagate_remember(const yh_frame* frames, int batch, const int* stream_ids,
+                          const float* dets /* (batch, max_det, 6) */, const int32_t* ids /* (batch, max_det) */,
+                          const int* counts, int max_det, void* state, int streams, int max_tracks, void* stream);
+int yh_propagate_remember_host(const yh_frame* frames, int batch, const int* stream_ids, const float* dets,
+                               const int32_t* ids, const int* counts, int max_det, void* state, int streams,
+                               int max_tracks, int threads);
+int yh_propagate(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams, int max_tracks,
+                 int radius, int max_mad, int max_out, float* dets /* (batch, max_out, 6) */,
+                 int32_t* ids /* (batch, max_out) */, int32_t* sad /* (batch, max_out) */, int* counts,
+                 void* workspace, size_t workspace_bytes, void* stream);
+int yh_propagate_host(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
+                      int max_tracks, int radius, int max_mad, int max_out, float* dets, int32_t* ids, int32_t* sad,
+                      int* counts, int threads);
 
 /* Apply a motion to the tracks of a batch's streams before the frame's yh_track* call (no reference
  * counterpart; tests/_motion_cases.py restates the rule). state: yh_track's (reid_dim 0; a stream's

@@ -477,6 +477,14 @@ int launch_motion(const ::yh_motion_src* src, int batch, const int* stream_ids, 
 int launch_motion_field(const ::yh_motion_src* src, int batch, const int* stream_ids, void* state, int streams,
                         int thumb_h, int thumb_w, const ::yh_motion_field_params& p, float* motion, int32_t* sad,
                         int32_t* field, void* workspace, hipStream_t s);
+// propagate.hip: yh_propagate_remember (one launch per 32 rows) and yh_propagate (a search and an
+// emit launch per 32 rows); src from csrc/propagate_host.h's checks
+int launch_propagate_remember(const ::yh_motion_src* src, int batch, const int* stream_ids, const float* dets,
+                              const int32_t* ids, const int* counts, int max_det, void* state, int streams,
+                              int max_tracks, hipStream_t s);
+int launch_propagate(const ::yh_motion_src* src, int batch, const int* stream_ids, void* state, int streams,
+                     int max_tracks, int radius, int max_mad, int max_out, float* dets, int32_t* ids, int32_t* sad,
+                     int* counts, void* workspace, hipStream_t s);
 // assign.hip: yh_assign, one wave per problem; the tracker's `optimal` instances above run the same solver
 int launch_assign(const int* weights, int problems, int T, int D, const int* t_counts, const int* d_counts,
                   int* row_of_slot, int* slot_of_row, hipStream_t s);

@@ -63,6 +63,8 @@ void thumbnail(const yh_motion_src& f, int th, int tw, unsigned char* out) {
 
 }  // namespace
 
+const char* yh_motion_describe(const yh_frame& f, yh_motion_src& s) { return describe(f, s); }
+
 const char* yh_motion_check(const yh_frame* frames, int batch, const void* state, int streams, int thumb_h,
                             int thumb_w, int radius, const void* motion, const void* sad, yh_motion_src* src) {
     if (batch < 0) return "motion: batch must be >= 0";

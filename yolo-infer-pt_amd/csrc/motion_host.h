@@ -194,6 +194,10 @@ int yh_motion_field_host_run(const yh_motion_src* src, int batch, const int* str
                              int thumb_h, int thumb_w, const yh_motion_field_params* p, float* motion, int32_t* sad,
                              int32_t* field, int threads);
 
+// The frame rules of yh_letterbox_frames alone: NULL and s filled, or the complaint (yh_propagate's
+// check shares them).
+const char* yh_motion_describe(const yh_frame& f, yh_motion_src& s);
+
 // NULL when the arguments are acceptable, else the message for yh_last_error() (YH_EINVAL). On
 // success src[k] describes frames[k] (src: batch entries, may be NULL for batch == 0).
 const char* yh_motion_check(const yh_frame* frames, int batch, const void* state, int streams, int thumb_h,

@@ -1,5 +1,6 @@
 // C ABI of the stages after the forward, none of which needs a handle: yh_nms, yh_match, yh_merge, yh_fuse, yh_track, yh_embed_quantize, yh_embed_similarity,
-// yh_track_reid, yh_gallery_search, yh_gallery_enrol, yh_assign, yh_track2, yh_track_reid2, yh_motion, yh_track_warp
+// yh_track_reid, yh_gallery_search, yh_gallery_enrol, yh_assign, yh_track2, yh_track_reid2, yh_motion, yh_track_warp,
+// yh_propagate_remember, yh_propagate
 // and their *_host twins.
 #include <algorithm>
 #include <vector>
@@ -12,6 +13,7 @@
 #include "match_host.h"
 #include "merge_host.h"
 #include "motion_host.h"
+#include "propagate_host.h"
 #include "track_host.h"
 
 using yh::Fail;
@@ -283,6 +285,69 @@ int yh_motion_field_host(const yh_frame* frames, int batch, const int* stream_id
         checked(yh_motion_field_check(p, thumb_h, thumb_w));
         yh_motion_field_host_run(src.data(), batch, stream_ids, state, streams, thumb_h, thumb_w, p, motion, sad, field,
                                  threads);
+    });
+}
+
+size_t yh_propagate_state_bytes(int streams, int max_tracks) {
+    if (streams < 0 || max_tracks < 1 || max_tracks > YH_PROPAGATE_MAX_TRACKS) return 0;
+    return (size_t)streams * yh_prop_stream_bytes(max_tracks);
+}
+
+size_t yh_propagate_workspace_bytes(int batch, int max_tracks) {
+    if (batch < 0 || max_tracks < 1 || max_tracks > YH_PROPAGATE_MAX_TRACKS) return 0;
+    return (size_t)std::min(batch, (int)YH_PROP_LAUNCH) * max_tracks * YH_PROP_REC;
+}
+
+int yh_propagate_remember(const yh_frame* frames, int batch, const int* stream_ids, const float* dets,
+                          const int32_t* ids, const int* counts, int max_det, void* state, int streams, int max_tracks,
+                          void* stream) {
+    return guarded([&] {
+        std::vector<yh_motion_src> src((size_t)std::max(batch, 0));
+        checked(yh_propagate_remember_check(frames, batch, dets, ids, counts, max_det, state, streams, max_tracks, src.data()));
+        yh::require((uintptr_t)state % 4 == 0, "propagate: state must be 4-byte aligned on the device");
+        const int rc = yh::launch_propagate_remember(src.data(), batch, stream_ids, dets, ids, counts, max_det, state,
+                                                     streams, max_tracks, (hipStream_t)stream);
+        yh::launched("propagate_remember", rc);
+    });
+}
+
+int yh_propagate_remember_host(const yh_frame* frames, int batch, const int* stream_ids, const float* dets,
+                               const int32_t* ids, const int* counts, int max_det, void* state, int streams,
+                               int max_tracks, int threads) {
+    return guarded([&] {
+        std::vector<yh_motion_src> src((size_t)std::max(batch, 0));
+        checked(yh_propagate_remember_check(frames, batch, dets, ids, counts, max_det, state, streams, max_tracks, src.data()));
+        yh_propagate_remember_host_run(src.data(), batch, stream_ids, dets, ids, counts, max_det, state, streams, max_tracks,
+                                       threads);
+    });
+}
+
+int yh_propagate(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams, int max_tracks,
+                 int radius, int max_mad, int max_out, float* dets, int32_t* ids, int32_t* sad, int* counts,
+                 void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        std::vector<yh_motion_src> src((size_t)std::max(batch, 0));
+        checked(yh_propagate_check(frames, batch, state, streams, max_tracks, radius, max_out, dets, ids, sad, counts,
+                                   src.data()));
+        yh::require(batch == 0 || workspace, "propagate: null workspace");
+        yh::require(workspace_bytes >= yh_propagate_workspace_bytes(batch, max_tracks), "propagate: workspace too small");
+        yh::require(((uintptr_t)state | (uintptr_t)workspace) % 4 == 0,
+                    "propagate: state and workspace must be 4-byte aligned on the device");
+        const int rc = yh::launch_propagate(src.data(), batch, stream_ids, state, streams, max_tracks, radius, max_mad,
+                                            max_out, dets, ids, sad, counts, workspace, (hipStream_t)stream);
+        yh::launched("propagate", rc);
+    });
+}
+
+int yh_propagate_host(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
+                      int max_tracks, int radius, int max_mad, int max_out, float* dets, int32_t* ids, int32_t* sad,
+                      int* counts, int threads) {
+    return guarded([&] {
+        std::vector<yh_motion_src> src((size_t)std::max(batch, 0));
+        checked(yh_propagate_check(frames, batch, state, streams, max_tracks, radius, max_out, dets, ids, sad, counts,
+                                   src.data()));
+        yh_propagate_host_run(src.data(), batch, stream_ids, state, streams, max_tracks, radius, max_mad, max_out, dets,
+                              ids, sad, counts, threads);
     });
 }
 

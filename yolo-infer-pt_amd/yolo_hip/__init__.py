@@ -14,7 +14,9 @@ embeddings (`track_reid`, `embed_quantize`, `embed_similarity`), and with an opt
 place of the greedy association on request (`assign="optimal"`; `assign` is the batched solver alone), and
 with camera-motion compensation (`MotionEstimator`, yolo_hip.motion: the translation between consecutive
 frames from their luma, or with model="similarity" translation plus zoom from a per-block motion field;
-`warp` / `Tracker.update(motion=...)` moves the tracks by it); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
+`warp` / `Tracker.update(motion=...)` moves the tracks by it), and `Propagator` (yolo_hip.propagate) carries the tracks over
+the frames a detector that runs on every N-th frame skips (`Propagated`, `propagate_state`: a template search per track in the
+full-resolution frame, rows in detection format for the unchanged tracker); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
 those crops (`Classified`: class, confidence and embedding per detection); `Gallery` (yolo_hip.gallery)
 turns those embeddings into identities across streams and time (`gallery_search`, `gallery_enrol`,
 `gallery_workspace`: the k best rows of a large int8 gallery per query on the int8 MFMA). The drop-in module API lives in `nets.nn` / `utils.util`.
@@ -45,6 +47,9 @@ def __getattr__(name):
     if name in ("MotionEstimator", "Motion", "motion_state", "field_workspace"):
         from . import motion
         return getattr(motion, name)
+    if name in ("Propagator", "Propagated", "propagate_state"):
+        from . import propagate
+        return getattr(propagate, name)
     if name in ("Tracker", "Tracks", "track", "track_state", "track_reid", "embed_quantize", "embed_similarity",
                 "assign", "warp"):
         # the function shares its name with its module, and importing the module binds the name

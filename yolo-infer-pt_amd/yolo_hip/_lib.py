@@ -111,6 +111,14 @@ _PROTOS = {
                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "yh_motion_field_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_int]),
+    "yh_propagate_state_bytes": (c_size_t, [c_int, c_int]),
+    "yh_propagate_workspace_bytes": (c_size_t, [c_int, c_int]),
+    **_twins("yh_propagate_remember", POINTER(YhFrame), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                      c_int, c_int),
+    "yh_propagate": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "yh_propagate_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     **_twins("yh_assign", c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p),
     **_twins("yh_embed_quantize", c_void_p, c_int, c_int, c_void_p, c_void_p),
     **_twins("yh_embed_similarity", c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
