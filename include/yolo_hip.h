@@ -67,6 +67,9 @@
  *   yh_propagate        no reference counterpart: a stream's tracks carried over the frames the detector
  *                       skips, by a template search per track in the full-resolution frame
  *   yh_propagate_remember_host, yh_propagate_host   the same in host memory
+ *   yh_mot_eval         no reference counterpart: the CLEAR-MOT counts and IDF1 of tracked sequences
+ *                       against ground truth, a batch of sequences and thresholds per launch
+ *   yh_mot_eval_host    the same in host memory
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -1081,6 +1084,70 @@ int yh_propagate(const yh_frame* frames, int batch, const int* stream_ids, void*
 int yh_propagate_host(const yh_frame* frames, int batch, const int* stream_ids, void* state, int streams,
                       int max_tracks, int radius, int max_mad, int max_out, float* dets, int32_t* ids, int32_t* sad,
                       int* counts, int threads);
+
+/* Tracking evaluation: the CLEAR-MOT counts and IDF1 of S sequences of F frames at num_thr IoU
+ * thresholds, in one launch, from the tensors yh_track writes (no reference counterpart;
+ * tests/_mot_cases.py restates the rules in numpy). Dense, padded inputs, frame-major per sequence:
+ *   tr (S, F, max_out, 6) f32, tr_ids (S, F, max_out) i32, tr_counts (S, F) i32   the hypotheses
+ *   gt (S, F, max_gt, 5) f32 = x1, y1, x2, y2, class, gt_ids (S, F, max_gt) i32, gt_counts (S, F) i32
+ *   frames (S) i32 or NULL: the live frames of a sequence, clamped to [0, F] (NULL: F)
+ *   thr (num_thr) f32, 1 <= num_thr <= YH_MOT_MAX_THR;  class_aware 0 or 1
+ * Counts are clamped to [0, max_*] and rows beyond a count are never read. A row whose id is outside
+ * [0, n_gt_ids) / [0, n_tr_ids) takes part in nothing and is counted in `ignored`. The ids of one
+ * frame must be distinct on each side (the caller's contract; equal ids give undefined counts).
+ *
+ * Rules, per sequence and threshold a, over the live frames in order:
+ * 1. Pairs. iou of a ground-truth row and a hypothesis row is fp32, one rounding per operation:
+ *    inter / ((area_g + area_t) - inter), and 0 when inter == 0 (inter: the product of the clamped
+ *    overlaps of the sides). w = 1 + (int)(iou * 65535.0f) clamped to [1, YH_ASSIGN_MAX_WEIGHT],
+ *    YH_ASSIGN_OPTIMAL's weight. The pair is allowed iff (class_aware == 0 or the classes are equal
+ *    as floats) and iou >= a.
+ * 2. Carry. A ground-truth id that was matched in the previous live frame to track id h, with both
+ *    present in this frame and the pair allowed, is matched to h again; both rows leave step 3.
+ * 3. Assignment. The remaining ground-truth rows are the slots and the remaining hypothesis rows the
+ *    columns, both in ascending row order; they are matched by yh_assign's algorithm on w (0 for a
+ *    pair that is not allowed). That algorithm is deterministic, so the matching is unique.
+ * 4. Counts. TP += matches; FN += unmatched ground-truth rows; FP += unmatched hypothesis rows;
+ *    IDSW += matched ground-truth ids whose last matched track id (in any earlier frame) exists and
+ *    differs; SIOU += w - 1 over the matches (an integer sum: no order to fix).
+ * 5. Identities. C[g][t] += 1 for every allowed pair of a frame, whatever was matched. After the last
+ *    frame IDTP is the sum of C over yh_assign's matching on min(C, YH_ASSIGN_MAX_WEIGHT) with the
+ *    n_gt_ids ground-truth ids as slots and the n_tr_ids track ids as columns.
+ * out (S, num_thr, 8) int64: TP, FP, FN, IDSW, SIOU, IDTP, ground-truth rows, hypothesis rows (the rows
+ * that take part). ignored (S, 2) i32: ground-truth and hypothesis rows with an id out of range. Every
+ * byte of both is written. The ratios are the caller's: MOTA = 1 - (FN + FP + IDSW) / GT, MOTP =
+ * SIOU / (65535 TP), IDF1 = 2 IDTP / (GT + HYP) (IDFN = GT - IDTP, IDFP = HYP - IDTP).
+ *
+ * yh_mot_eval: device pointers, one workgroup per sequence and one wave per threshold, asynchronous
+ * on `stream`, allocates nothing, never synchronises, uses no atomics. workspace: caller-owned device
+ * memory, 16-byte aligned, of yh_mot_workspace_bytes(sequences, num_thr, n_gt_ids, n_tr_ids) bytes
+ * (0 for illegal arguments), contents undefined before and after: it holds C as uint16, which is why
+ * F is at most YH_MOT_MAX_FRAMES. LDS at the caps (256 rows a side, 1024 ids a side, 16 thresholds):
+ * 2 x 14336 bytes of staged frames (boxes, ids, a byte map track id -> row) and 16 x 8192 bytes of
+ * per-wave words (5120 the solver's, 2048 the last matched ids, 512 the previous frame's matches, 512
+ * the slot and column lists) = YH_MOT_LDS_AT_CAPS = 159744 of the 163840 a workgroup may ask for; the
+ * closing assignments (16384 bytes each at the caps) reuse it, 9 side by side.
+ * yh_mot_eval_host: the same bytes for host pointers, synchronous, (sequence, threshold) pairs in
+ * parallel over `threads` (<= 0: all hardware threads); it needs no workspace.
+ * YH_EINVAL (message in yh_last_error()), nothing launched or written: max_out or max_gt above
+ * YH_MOT_MAX_ROWS, n_gt_ids or n_tr_ids above YH_MOT_MAX_IDS, F above YH_MOT_MAX_FRAMES, num_thr
+ * outside [1, YH_MOT_MAX_THR], class_aware neither 0 nor 1, a negative size, a NULL required pointer,
+ * a workspace that is too small or misaligned (device entry). */
+#define YH_MOT_MAX_ROWS 256
+#define YH_MOT_MAX_IDS YH_ASSIGN_MAX_SIZE
+#define YH_MOT_MAX_THR 16
+#define YH_MOT_MAX_FRAMES 65535
+#define YH_MOT_LDS_AT_CAPS 159744
+size_t yh_mot_workspace_bytes(int sequences, int num_thr, int n_gt_ids, int n_tr_ids);
+int yh_mot_eval(const float* tr, const int32_t* tr_ids, const int32_t* tr_counts, int max_out, const float* gt,
+                const int32_t* gt_ids, const int32_t* gt_counts, int max_gt, int sequences, int F,
+                const int32_t* frames, const float* thr, int num_thr, int n_gt_ids, int n_tr_ids, int class_aware,
+                int64_t* out /* (S, num_thr, 8) */, int32_t* ignored /* (S, 2) */, void* workspace,
+                size_t workspace_bytes, void* stream);
+int yh_mot_eval_host(const float* tr, const int32_t* tr_ids, const int32_t* tr_counts, int max_out, const float* gt,
+                     const int32_t* gt_ids, const int32_t* gt_counts, int max_gt, int sequences, int F,
+                     const int32_t* frames, const float* thr, int num_thr, int n_gt_ids, int n_tr_ids,
+                     int class_aware, int64_t* out, int32_t* ignored, int threads);
 
 /* Apply a motion to the tracks of a batch's streams before the frame's yh_track* call (no reference
  * counterpart; tests/_motion_cases.py restates the rule). state: yh_track's (reid_dim 0; a stream's

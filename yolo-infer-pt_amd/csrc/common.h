@@ -485,6 +485,24 @@ int launch_propagate_remember(const ::yh_motion_src* src, int batch, const int* 
 int launch_propagate(const ::yh_motion_src* src, int batch, const int* stream_ids, void* state, int streams,
                      int max_tracks, int radius, int max_mad, int max_out, float* dets, int32_t* ids, int32_t* sad,
                      int* counts, void* workspace, hipStream_t s);
+// mot.hip: yh_mot_eval, one workgroup per sequence and one wave per threshold; C: the workspace
+struct MotEval {
+    const float* tr;
+    const int* tr_ids;
+    const int* tr_counts;
+    int max_out;
+    const float* gt;
+    const int* gt_ids;
+    const int* gt_counts;
+    int max_gt, sequences, F;
+    const int* frames;
+    const float* thr;
+    int num_thr, n_gt_ids, n_tr_ids, class_aware;
+    long long* out;
+    int* ignored;
+    char* C;
+};
+int launch_mot_eval(const MotEval& p, hipStream_t s);
 // assign.hip: yh_assign, one wave per problem; the tracker's `optimal` instances above run the same solver
 int launch_assign(const int* weights, int problems, int T, int D, const int* t_counts, const int* d_counts,
                   int* row_of_slot, int* slot_of_row, hipStream_t s);

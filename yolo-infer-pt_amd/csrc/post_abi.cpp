@@ -1,6 +1,6 @@
 // C ABI of the stages after the forward, none of which needs a handle: yh_nms, yh_match, yh_merge, yh_fuse, yh_track, yh_embed_quantize, yh_embed_similarity,
 // yh_track_reid, yh_gallery_search, yh_gallery_enrol, yh_assign, yh_track2, yh_track_reid2, yh_motion, yh_track_warp,
-// yh_propagate_remember, yh_propagate
+// yh_propagate_remember, yh_propagate, yh_mot_eval
 // and their *_host twins.
 #include <algorithm>
 #include <vector>
@@ -12,6 +12,7 @@
 #include "host_util.h"
 #include "match_host.h"
 #include "merge_host.h"
+#include "mot_host.h"
 #include "motion_host.h"
 #include "propagate_host.h"
 #include "track_host.h"
@@ -348,6 +349,45 @@ int yh_propagate_host(const yh_frame* frames, int batch, const int* stream_ids, 
                                    src.data()));
         yh_propagate_host_run(src.data(), batch, stream_ids, state, streams, max_tracks, radius, max_mad, max_out, dets,
                               ids, sad, counts, threads);
+    });
+}
+
+size_t yh_mot_workspace_bytes(int sequences, int num_thr, int n_gt_ids, int n_tr_ids) {
+    if (sequences < 0 || num_thr < 1 || num_thr > YH_MOT_MAX_THR || n_gt_ids < 0 || n_gt_ids > YH_MOT_MAX_IDS ||
+        n_tr_ids < 0 || n_tr_ids > YH_MOT_MAX_IDS)
+        return 0;
+    return (size_t)sequences * num_thr * yh_mot_c_bytes(n_gt_ids, n_tr_ids);
+}
+
+int yh_mot_eval(const float* tr, const int32_t* tr_ids, const int32_t* tr_counts, int max_out, const float* gt,
+                const int32_t* gt_ids, const int32_t* gt_counts, int max_gt, int sequences, int F,
+                const int32_t* frames, const float* thr, int num_thr, int n_gt_ids, int n_tr_ids, int class_aware,
+                int64_t* out, int32_t* ignored, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        checked(yh_mot_check(tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, sequences, F, thr, num_thr,
+                             n_gt_ids, n_tr_ids, class_aware, out, ignored));
+        const size_t need = yh_mot_workspace_bytes(sequences, num_thr, n_gt_ids, n_tr_ids);
+        yh::require(need == 0 || workspace, "mot_eval: null workspace");
+        yh::require(workspace_bytes >= need, "mot_eval: workspace too small");
+        yh::require((uintptr_t)workspace % 16 == 0, "mot_eval: workspace must be 16-byte aligned");
+        yh::require(((uintptr_t)tr | (uintptr_t)gt | (uintptr_t)tr_ids | (uintptr_t)gt_ids) % 4 == 0 && (uintptr_t)out % 8 == 0,
+                    "mot_eval: inputs must be 4-byte and out 8-byte aligned on the device");
+        const yh::MotEval a{tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, sequences, F, frames, thr,
+                            num_thr, n_gt_ids, n_tr_ids, class_aware, (long long*)out, ignored, (char*)workspace};
+        const int rc = yh::launch_mot_eval(a, (hipStream_t)stream);
+        yh::launched("mot_eval", rc);
+    });
+}
+
+int yh_mot_eval_host(const float* tr, const int32_t* tr_ids, const int32_t* tr_counts, int max_out, const float* gt,
+                     const int32_t* gt_ids, const int32_t* gt_counts, int max_gt, int sequences, int F,
+                     const int32_t* frames, const float* thr, int num_thr, int n_gt_ids, int n_tr_ids,
+                     int class_aware, int64_t* out, int32_t* ignored, int threads) {
+    return guarded([&] {
+        checked(yh_mot_check(tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, sequences, F, thr, num_thr,
+                             n_gt_ids, n_tr_ids, class_aware, out, ignored));
+        yh_mot_eval_host_run(tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, sequences, F, frames, thr,
+                             num_thr, n_gt_ids, n_tr_ids, class_aware, out, ignored, threads);
     });
 }
 

@@ -16,7 +16,9 @@ with camera-motion compensation (`MotionEstimator`, yolo_hip.motion: the transla
 frames from their luma, or with model="similarity" translation plus zoom from a per-block motion field;
 `warp` / `Tracker.update(motion=...)` moves the tracks by it), and `Propagator` (yolo_hip.propagate) carries the tracks over
 the frames a detector that runs on every N-th frame skips (`Propagated`, `propagate_state`: a template search per track in the
-full-resolution frame, rows in detection format for the unchanged tracker); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
+full-resolution frame, rows in detection format for the unchanged tracker), and `TrackEvaluator` (yolo_hip.mot) scores the
+tracks against ground truth on the device (`mot_eval`, `mot_workspace`: CLEAR-MOT counts and IDF1 of a batch of
+sequences at a list of IoU thresholds in one launch); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
 those crops (`Classified`: class, confidence and embedding per detection); `Gallery` (yolo_hip.gallery)
 turns those embeddings into identities across streams and time (`gallery_search`, `gallery_enrol`,
 `gallery_workspace`: the k best rows of a large int8 gallery per query on the int8 MFMA). The drop-in module API lives in `nets.nn` / `utils.util`.
@@ -57,6 +59,9 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module(".track", __name__)
         return mod if name == "track" else getattr(mod, name)
+    if name in ("TrackEvaluator", "mot_eval", "mot_workspace"):
+        from . import mot
+        return getattr(mot, name)
     if name in ("Gallery", "gallery_search", "gallery_enrol", "gallery_workspace"):
         from . import gallery
         return getattr(gallery, name)

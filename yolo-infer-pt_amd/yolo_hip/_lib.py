@@ -120,6 +120,12 @@ _PROTOS = {
     "yh_propagate_host": (c_int, [POINTER(YhFrame), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     **_twins("yh_assign", c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p),
+    "yh_mot_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "yh_mot_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                            c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                            c_void_p]),
+    "yh_mot_eval_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
     **_twins("yh_embed_quantize", c_void_p, c_int, c_int, c_void_p, c_void_p),
     **_twins("yh_embed_similarity", c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_void_p),
