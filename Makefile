@@ -17,15 +17,15 @@ NET := engine net_build net_weights net_forward net_launch net_debug
 HOSTHIP := post_abi nms_host
 # kernels; the NOFMA ones promise bit-exact arithmetic against host code: no FMA contraction
 KERNELS := conv sppf attn decode conv_mx conv_rw head c3k2 c3k pwchain cls
-KERNELS_NOFMA := preprocess nms match merge fuse track reid gallery assign motion propagate mot
+KERNELS_NOFMA := preprocess nms match merge fuse track reid gallery assign motion propagate mot hota
 # HIP-free translation units: plain C++, no device pass, no FMA contraction
-HOSTCXX := match_host merge_host fuse_host track_host gallery_host assign_host motion_host propagate_host mot_host
+HOSTCXX := match_host merge_host fuse_host track_host gallery_host assign_host motion_host propagate_host mot_host hota_host
 
 objs = $(patsubst %,$(OBJDIR)/%.o,$(1))
 OBJS := $(call objs,$(NET) $(HOSTHIP) $(KERNELS) $(KERNELS_NOFMA) $(HOSTCXX))
 HOST_H := $(SRC)/host_util.h $(SRC)/host_parallel.h $(SRC)/box_math.h \
           $(SRC)/match_host.h $(SRC)/merge_host.h $(SRC)/fuse_host.h $(SRC)/track_host.h $(SRC)/gallery_host.h \
-          $(SRC)/assign_host.h $(SRC)/motion_host.h $(SRC)/propagate_host.h $(SRC)/mot_host.h
+          $(SRC)/assign_host.h $(SRC)/motion_host.h $(SRC)/propagate_host.h $(SRC)/mot_host.h $(SRC)/hota_host.h
 
 all: $(OUT)
 
@@ -51,7 +51,7 @@ $(call objs,$(HOSTCXX)): $(OBJDIR)/%.o: $(SRC)/%.cpp $(SRC)/%.h $(SRC)/box_math.
 # the decode's value arithmetic, shared by its kernels and the fused head's
 $(call objs,decode head): $(SRC)/head_math.h
 # each shares its arithmetic with its host twin through box_math.h and the twin's header
-$(call objs,match merge fuse track motion propagate mot): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
+$(call objs,match merge fuse track motion propagate mot hota): $(OBJDIR)/%.o: $(SRC)/%_host.h $(SRC)/box_math.h
 # the appearance kernels share the tracker's header: the twins live in track_host.cpp
 $(OBJDIR)/reid.o: $(SRC)/track_host.h $(SRC)/box_math.h
 # the int8 MFMA kernels share their fragment loads and lane map; the search shares its candidate
@@ -67,6 +67,9 @@ $(OBJDIR)/track_host.o: $(SRC)/assign_host.h
 # the tracking evaluation runs that solver per frame and once more on the identity overlaps
 $(OBJDIR)/mot.o: $(SRC)/assign.h $(SRC)/assign_host.h
 $(OBJDIR)/mot_host.o: $(SRC)/assign_host.h
+# HOTA runs it per frame on weights aligned over the whole sequence
+$(OBJDIR)/hota.o: $(SRC)/assign.h $(SRC)/assign_host.h
+$(OBJDIR)/hota_host.o: $(SRC)/assign_host.h
 # the motion estimates promise the host twins' bytes down to the last fp32 operations; the compiler
 # pairs those into packed fp32 instructions (v_pk_mul_f32, v_pk_add_f32) when left to itself, and the
 # file is built without them: scalar fp32 only, one rounding per operation as the rules say
@@ -112,7 +115,17 @@ build/mot_host_check: tools/mot_host_check.cpp $(SRC)/mot_host.cpp $(SRC)/mot_ho
 mot_host_check: build/mot_host_check
 	build/mot_host_check
 
+# yh_hota_eval's host twin under the same sanitizers
+build/hota_host_check: tools/hota_host_check.cpp $(SRC)/hota_host.cpp $(SRC)/hota_host.h $(SRC)/assign_host.h \
+                       $(SRC)/box_math.h $(SRC)/host_parallel.h include/yolo_hip.h
+	mkdir -p build
+	$(HOSTCC) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off \
+	    -Iinclude -I$(SRC) tools/hota_host_check.cpp $(SRC)/hota_host.cpp -lpthread -o $@
+
+hota_host_check: build/hota_host_check
+	build/hota_host_check
+
 clean:
 	rm -rf build $(OUT)
 
-.PHONY: all clean motion_field_host_check propagate_host_check mot_host_check
+.PHONY: all clean motion_field_host_check propagate_host_check mot_host_check hota_host_check

@@ -70,6 +70,9 @@
  *   yh_mot_eval         no reference counterpart: the CLEAR-MOT counts and IDF1 of tracked sequences
  *                       against ground truth, a batch of sequences and thresholds per launch
  *   yh_mot_eval_host    the same in host memory
+ *   yh_hota_eval        no reference counterpart: the HOTA counts (detection, association, localisation)
+ *                       of tracked sequences, frames in parallel, every sum an integer
+ *   yh_hota_eval_host   the same in host memory
  *
  * Conventions
  *   - Every function returns 0 on success and a negative YH_E* code on failure;
@@ -1148,6 +1151,65 @@ int yh_mot_eval_host(const float* tr, const int32_t* tr_ids, const int32_t* tr_c
                      const int32_t* gt_ids, const int32_t* gt_counts, int max_gt, int sequences, int F,
                      const int32_t* frames, const float* thr, int num_thr, int n_gt_ids, int n_tr_ids,
                      int class_aware, int64_t* out, int32_t* ignored, int threads);
+
+/* HOTA (Luiten et al. 2021) of S sequences of F frames at num_thr IoU thresholds, on yh_mot_eval's
+ * tensors (no reference counterpart; tests/_hota_cases.py holds the float64 formulas it is measured
+ * against). tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, frames, n_gt_ids, n_tr_ids,
+ * class_aware: as for yh_mot_eval - the same clamping of counts and of `frames`, rows whose id is out
+ * of range take part in nothing and are counted in `ignored`, ids distinct within a frame and side.
+ * thr (num_thr) f32 in any order, 1 <= num_thr <= YH_HOTA_MAX_THR. F is at most YH_HOTA_MAX_FRAMES.
+ *
+ * HOTA has no carry between frames, and here every accumulated quantity is an integer, so the order
+ * of frames, threads and atomic additions cannot change a byte. "div" is the integer quotient.
+ * Per sequence, over the live frames in any order:
+ * 1. Similarity. iou is yh_mot_eval's rule 1 (fp32). s = (int)(iou * 65536.0f), at most 65536, and 0
+ *    unless that product is positive; s = 0 when class_aware and the classes differ as floats, and
+ *    when either row's id is out of range.
+ * 2. Pass A. In a frame R_i = sum_j s_ij and C_j = sum_i s_ij; for s_ij > 0 the frame's Jaccard term
+ *    is J_ij = (s_ij * 2^16) div (R_i + C_j - s_ij), and P[g_i][t_j] += J_ij (uint32: 65535 frames x
+ *    65536 < 2^32). n_g[g] += 1 and n_t[t] += 1 for every row that takes part.
+ * 3. Alignment. A[g][t] = (P * 2^16) div ((n_g + n_t) * 2^16 - P) in 64 bits, in [0, 65536].
+ * 4. Pass B. In a frame w_ij = 0 when s_ij = 0, else clamp((A[g_i][t_j] * s_ij) >> 16, 1, 65535).
+ *    All ground-truth rows are the slots and all hypothesis rows the columns, in row order, matched
+ *    by yh_assign's algorithm on w. A matched pair counts for every threshold a with iou >= thr[a]
+ *    (fp32 compare; a NaN threshold is met by nothing): TP[a] += 1, LOC[a] += s, M_a[g][t] += 1.
+ * 5. Closing, per threshold, over the identity pairs with m = M_a[g][t] > 0: ASSA = sum (m^2 * 2^20)
+ *    div (n_g + n_t - m), ASSRE = sum (m^2 * 2^20) div n_g, ASSPR = sum (m^2 * 2^20) div n_t, PAIRS =
+ *    their number; FN = GT - TP, FP = HYP - TP with GT, HYP the rows that take part.
+ * out (S, num_thr, 8) int64 in the caller's threshold order: TP, FP, FN, LOC, ASSA, ASSRE, ASSPR, PAIRS.
+ * rows (S, 2) int64: GT, HYP. ignored (S, 2) i32. Every byte of the three is written. The ratios are
+ * the caller's: DetA = TP / (TP + FN + FP), AssA = ASSA / (2^20 TP) (AssRe, AssPr likewise), LocA =
+ * LOC / (65536 TP), HOTA(a) = sqrt(DetA AssA), HOTA = the mean over the thresholds.
+ *
+ * yh_hota_eval: device pointers, asynchronous on `stream`, allocates nothing, never synchronises; four
+ * launches (a clear of the workspace, pass A and pass B with one wave per frame, the closing over the
+ * identity pairs), integer atomics in the workspace. workspace: caller-owned device memory, 16-byte
+ * aligned, of yh_hota_workspace_bytes(sequences, num_thr, n_gt_ids, n_tr_ids) bytes (0 for illegal
+ * arguments), contents undefined before and after. Per sequence it holds P and the matches of every
+ * threshold level as uint32 over the identity pairs, n_g, n_t and 8 (6 num_thr + 4) + 4 bytes of
+ * counters, each part padded to 16 bytes: 329 152 bytes at 64 x 64 ids and 19 thresholds; 138 421 808
+ * bytes (132 MiB) at the caps of 1024 x 1024 ids and 32 thresholds. LDS of pass B per wave at 256 x
+ * 256 rows: 13312 bytes of staged rows, 4096 of solver words and the 131072-byte weight tile =
+ * YH_HOTA_LDS_AT_CAPS; a workgroup holds as many waves as fit 163840 bytes, 16 at most.
+ * yh_hota_eval_host: the same bytes for host pointers, synchronous, sequences in parallel over
+ * `threads` (<= 0: all hardware threads); it needs no workspace.
+ * YH_EINVAL (message in yh_last_error()), nothing launched or written: max_out or max_gt above
+ * YH_MOT_MAX_ROWS, n_gt_ids or n_tr_ids above YH_MOT_MAX_IDS, F above YH_HOTA_MAX_FRAMES, num_thr
+ * outside [1, YH_HOTA_MAX_THR], class_aware neither 0 nor 1, a negative size, a NULL required pointer,
+ * a workspace that is too small or misaligned (device entry). */
+#define YH_HOTA_MAX_THR 32
+#define YH_HOTA_MAX_FRAMES 65535
+#define YH_HOTA_LDS_AT_CAPS 148480
+size_t yh_hota_workspace_bytes(int sequences, int num_thr, int n_gt_ids, int n_tr_ids);
+int yh_hota_eval(const float* tr, const int32_t* tr_ids, const int32_t* tr_counts, int max_out, const float* gt,
+                 const int32_t* gt_ids, const int32_t* gt_counts, int max_gt, int sequences, int F,
+                 const int32_t* frames, const float* thr, int num_thr, int n_gt_ids, int n_tr_ids, int class_aware,
+                 int64_t* out /* (S, num_thr, 8) */, int64_t* rows /* (S, 2) */, int32_t* ignored /* (S, 2) */,
+                 void* workspace, size_t workspace_bytes, void* stream);
+int yh_hota_eval_host(const float* tr, const int32_t* tr_ids, const int32_t* tr_counts, int max_out, const float* gt,
+                      const int32_t* gt_ids, const int32_t* gt_counts, int max_gt, int sequences, int F,
+                      const int32_t* frames, const float* thr, int num_thr, int n_gt_ids, int n_tr_ids,
+                      int class_aware, int64_t* out, int64_t* rows, int32_t* ignored, int threads);
 
 /* Apply a motion to the tracks of a batch's streams before the frame's yh_track* call (no reference
  * counterpart; tests/_motion_cases.py restates the rule). state: yh_track's (reid_dim 0; a stream's

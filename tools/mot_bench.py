@@ -29,7 +29,7 @@ S, F = 8, 600
 THR = np.linspace(0.5, 0.95, 10).astype(np.float32)
 
 
-def scenes(rows, seed):
+def scenes(rows, seed, S=S, F=F):
     rng = np.random.default_rng(seed)
     o = np.arange(rows)
     base = np.stack([70.0 * (o % 16), 90.0 * (o // 16)], 1)                   # neighbours overlap a little

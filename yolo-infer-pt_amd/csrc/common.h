@@ -503,6 +503,26 @@ struct MotEval {
     char* C;
 };
 int launch_mot_eval(const MotEval& p, hipStream_t s);
+// hota.hip: yh_hota_eval, a clear, two launches over (sequence, frame) and a closing one over the
+// identity pairs; ws: the workspace (csrc/hota_host.h's yh_hota_layout per sequence)
+struct HotaEval {
+    const float* tr;
+    const int* tr_ids;
+    const int* tr_counts;
+    int max_out;
+    const float* gt;
+    const int* gt_ids;
+    const int* gt_counts;
+    int max_gt, sequences, F;
+    const int* frames;
+    const float* thr;
+    int num_thr, n_gt_ids, n_tr_ids, class_aware;
+    long long* out;
+    long long* rows;
+    int* ignored;
+    char* ws;
+};
+int launch_hota_eval(const HotaEval& p, hipStream_t s);
 // assign.hip: yh_assign, one wave per problem; the tracker's `optimal` instances above run the same solver
 int launch_assign(const int* weights, int problems, int T, int D, const int* t_counts, const int* d_counts,
                   int* row_of_slot, int* slot_of_row, hipStream_t s);

@@ -1,6 +1,6 @@
 // C ABI of the stages after the forward, none of which needs a handle: yh_nms, yh_match, yh_merge, yh_fuse, yh_track, yh_embed_quantize, yh_embed_similarity,
 // yh_track_reid, yh_gallery_search, yh_gallery_enrol, yh_assign, yh_track2, yh_track_reid2, yh_motion, yh_track_warp,
-// yh_propagate_remember, yh_propagate, yh_mot_eval
+// yh_propagate_remember, yh_propagate, yh_mot_eval, yh_hota_eval
 // and their *_host twins.
 #include <algorithm>
 #include <vector>
@@ -10,6 +10,7 @@
 #include "fuse_host.h"
 #include "gallery_host.h"
 #include "host_util.h"
+#include "hota_host.h"
 #include "match_host.h"
 #include "merge_host.h"
 #include "mot_host.h"
@@ -388,6 +389,47 @@ int yh_mot_eval_host(const float* tr, const int32_t* tr_ids, const int32_t* tr_c
                              n_gt_ids, n_tr_ids, class_aware, out, ignored));
         yh_mot_eval_host_run(tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, sequences, F, frames, thr,
                              num_thr, n_gt_ids, n_tr_ids, class_aware, out, ignored, threads);
+    });
+}
+
+size_t yh_hota_workspace_bytes(int sequences, int num_thr, int n_gt_ids, int n_tr_ids) {
+    if (sequences < 0 || num_thr < 1 || num_thr > YH_HOTA_MAX_THR || n_gt_ids < 0 || n_gt_ids > YH_MOT_MAX_IDS ||
+        n_tr_ids < 0 || n_tr_ids > YH_MOT_MAX_IDS)
+        return 0;
+    return (size_t)sequences * yh_hota_layout(num_thr, n_gt_ids, n_tr_ids).bytes;
+}
+
+int yh_hota_eval(const float* tr, const int32_t* tr_ids, const int32_t* tr_counts, int max_out, const float* gt,
+                 const int32_t* gt_ids, const int32_t* gt_counts, int max_gt, int sequences, int F,
+                 const int32_t* frames, const float* thr, int num_thr, int n_gt_ids, int n_tr_ids, int class_aware,
+                 int64_t* out, int64_t* rows, int32_t* ignored, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        checked(yh_hota_check(tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, sequences, F, thr, num_thr,
+                              n_gt_ids, n_tr_ids, class_aware, out, rows, ignored));
+        const size_t need = yh_hota_workspace_bytes(sequences, num_thr, n_gt_ids, n_tr_ids);
+        yh::require(need == 0 || workspace, "hota_eval: null workspace");
+        yh::require(workspace_bytes >= need, "hota_eval: workspace too small");
+        yh::require((uintptr_t)workspace % 16 == 0, "hota_eval: workspace must be 16-byte aligned");
+        yh::require(((uintptr_t)tr | (uintptr_t)gt | (uintptr_t)tr_ids | (uintptr_t)gt_ids | (uintptr_t)thr) % 4 == 0 &&
+                        ((uintptr_t)out | (uintptr_t)rows) % 8 == 0,
+                    "hota_eval: inputs must be 4-byte and out, rows 8-byte aligned on the device");
+        const yh::HotaEval a{tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, sequences, F, frames, thr,
+                             num_thr, n_gt_ids, n_tr_ids, class_aware, (long long*)out, (long long*)rows, ignored,
+                             (char*)workspace};
+        const int rc = yh::launch_hota_eval(a, (hipStream_t)stream);
+        yh::launched("hota_eval", rc);
+    });
+}
+
+int yh_hota_eval_host(const float* tr, const int32_t* tr_ids, const int32_t* tr_counts, int max_out, const float* gt,
+                      const int32_t* gt_ids, const int32_t* gt_counts, int max_gt, int sequences, int F,
+                      const int32_t* frames, const float* thr, int num_thr, int n_gt_ids, int n_tr_ids,
+                      int class_aware, int64_t* out, int64_t* rows, int32_t* ignored, int threads) {
+    return guarded([&] {
+        checked(yh_hota_check(tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, sequences, F, thr, num_thr,
+                              n_gt_ids, n_tr_ids, class_aware, out, rows, ignored));
+        yh_hota_eval_host_run(tr, tr_ids, tr_counts, max_out, gt, gt_ids, gt_counts, max_gt, sequences, F, frames, thr,
+                              num_thr, n_gt_ids, n_tr_ids, class_aware, out, rows, ignored, threads);
     });
 }
 

@@ -18,7 +18,8 @@ frames from their luma, or with model="similarity" translation plus zoom from a 
 the frames a detector that runs on every N-th frame skips (`Propagated`, `propagate_state`: a template search per track in the
 full-resolution frame, rows in detection format for the unchanged tracker), and `TrackEvaluator` (yolo_hip.mot) scores the
 tracks against ground truth on the device (`mot_eval`, `mot_workspace`: CLEAR-MOT counts and IDF1 of a batch of
-sequences at a list of IoU thresholds in one launch); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
+sequences at a list of IoU thresholds in one launch; `hota_eval`, `hota_workspace`, `hota_ratios` and `TrackEvaluator(hota=True)`:
+HOTA with its detection, association and localisation parts, the frames in parallel); `Classifier` (yolo_hip.classify) runs a YOLO11-cls second stage on
 those crops (`Classified`: class, confidence and embedding per detection); `Gallery` (yolo_hip.gallery)
 turns those embeddings into identities across streams and time (`gallery_search`, `gallery_enrol`,
 `gallery_workspace`: the k best rows of a large int8 gallery per query on the int8 MFMA). The drop-in module API lives in `nets.nn` / `utils.util`.
@@ -59,7 +60,7 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module(".track", __name__)
         return mod if name == "track" else getattr(mod, name)
-    if name in ("TrackEvaluator", "mot_eval", "mot_workspace"):
+    if name in ("TrackEvaluator", "mot_eval", "mot_workspace", "hota_eval", "hota_workspace", "hota_ratios"):
         from . import mot
         return getattr(mot, name)
     if name in ("Gallery", "gallery_search", "gallery_enrol", "gallery_workspace"):

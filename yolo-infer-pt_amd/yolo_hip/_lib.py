@@ -126,6 +126,12 @@ _PROTOS = {
                             c_void_p]),
     "yh_mot_eval_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
+    "yh_hota_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "yh_hota_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                             c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_size_t, c_void_p]),
+    "yh_hota_eval_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     **_twins("yh_embed_quantize", c_void_p, c_int, c_int, c_void_p, c_void_p),
     **_twins("yh_embed_similarity", c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_void_p),
